@@ -4,8 +4,14 @@
 Default (the driver's call): ChaCha20-V3 single 64-byte blocks, one batch of --batch independent statements per GPU per step.
 A "step" is one pass of the hot path (witness -> quotient NTTs -> MSMs -> proof assembly) over that batch.  The other BASELINE
 configs are selected with --workload {chacha20,aes128,aes256,mixed} and --batch {1,64,1024,8192} (--callers: concurrent caller
-threads); every run prints the same JSON line (profiles/r03_bench_*.json hold one per config) and, after the clock stops, checks a
-sample of the LAST timed step's proofs with the product's verifier libverify.so ("verified": n; a rejection fails the run).
+threads); every run prints one JSON line.  A plain run does only what the headline needs: set-up, warm-up, the timed steps, the
+line.  --full adds everything else (the keys listed below; profiles/r03_bench_*.json hold one such line per config): after the
+clock stops it checks a sample of the LAST timed step's proofs with the product's verifier libverify.so ("verified": n; a
+rejection fails the run), prices the dominant kernel and times the CPU baseline.
+
+--dump-outputs DIR writes what the last timed step returned to its caller as float32 .npy files (byte values; a fixed, seeded
+sample of the statements when the whole would pass 64 MB).  To make those outputs comparable between two builds, such a run fixes
+the prover randomness (r, s, commitment mask) and the seed of the AES keys' Setup through the library's test hooks.
 
   * chacha20 / aes128 / aes256 go through gsc_prove_raw (the binary twin of Prove: no JSON on the timed path);
   * mixed sends a JSON array (statement i uses cipher i mod 3) through ProveBatch, all three algorithms resident on the device.
@@ -16,7 +22,7 @@ processes BEFORE anything touches torch or HIP and relays rank 0's line; under `
 RANK / LOCAL_RANK / WORLD_SIZE and the world size must equal --gpus.  `--gpus N --in-library` is the other multi-GPU path: ONE process,
 GSC_DEVICES=0..N-1, one call of N x batch statements per step split over the library's own engine replicas (what a Go / node host does).
 
-The line carries, besides the contract's keys:
+With --full the line carries, besides the contract's keys:
   "roofline"      : the dominant kernel (the Z-table MSM gather-accumulate of the slowest algorithm in the workload; the resident witness
                     kernel for calls of a handful of statements) priced against HBM peak with SURVEY.md §8(d)'s algorithmic bytes of the
                     statements the launch proved, timed live with HIP events on the kernel's own stream;
@@ -42,7 +48,8 @@ ALGOS = {"chacha20": (0, "chacha20", 32), "aes128": (1, "aes-128-ctr", 16), "aes
 # algorithmic bytes per proof — whole path, and the MSM stage alone (AES: the survey's upper bounds)
 BYTES_PER_PROOF = {"chacha20": 28_281_728, "aes128": 115_002_752, "aes256": 129_366_656}
 MSM_BYTES_PER_PROOF = {"chacha20": 10_589_440, "aes128": 46_750_944, "aes256": 57_991_904}
-SETUP_SEEDS = {"aes128": bytes([1] * 32), "aes256": bytes([2] * 32)}      # CPU-baseline keys (oracle Setup; any valid key costs the same to prove with)
+SETUP_SEEDS = {"aes128": bytes([1] * 32), "aes256": bytes([2] * 32)}      # AES keys of the CPU baseline (oracle Setup; any valid key costs the same to prove with)
+                                                                          # and of --dump-outputs runs (the product's Setup)
 
 
 def golden(name):
@@ -194,6 +201,27 @@ def verify_items(g, items, threads=16):
         return g.verify({"cipher": cipher, "proof": base64.b64encode(proof).decode(), "publicSignals": base64.b64encode(sig).decode()})
     with ThreadPoolExecutor(threads) as pool:
         return list(pool.map(check, items))
+
+
+DUMP_BYTES_MAX = 64_000_000                 # --dump-outputs: all files of all ranks together
+DUMP_SEED = 20251015                        # fixed sample of the statements when a step's outputs would pass DUMP_BYTES_MAX
+DUMP_RANDOMNESS = (0x1234567, 0xabcdef0123456789abcdef, 0x5555)      # (r, s, mask) of every proof of a --dump-outputs run
+
+
+def dump_outputs(out_dir, arrays, rank=0, world=1):
+    """Writes the per-statement output arrays of one step (name -> 2-D array, one row per statement, byte values) as float32
+    DIR/<name>.npy, with DIR/statement_index.npy (float64) naming the rows.  Rows are a fixed, seeded sample when the step's outputs
+    would pass this rank's share of DUMP_BYTES_MAX.  With several ranks every file name starts with rank<r>_."""
+    import numpy as np
+    n = len(next(iter(arrays.values())))
+    row_bytes = 4 * sum(a.shape[1] for a in arrays.values()) + 8
+    keep = min(n, (DUMP_BYTES_MAX // world - 4096 * (len(arrays) + 1)) // row_bytes)
+    rows = np.arange(n) if keep == n else np.sort(np.random.default_rng(DUMP_SEED).choice(n, keep, replace=False))
+    prefix = "rank%d_" % rank if world > 1 else ""
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, prefix + "statement_index.npy"), rows.astype(np.float64))
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), np.ascontiguousarray(a[rows], dtype=np.float32))
 
 
 def provable(rec, name):
@@ -386,9 +414,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--workload", choices=["chacha20", "aes128", "aes256", "mixed"], default="chacha20")
     ap.add_argument("--batch", type=int, default=int(os.environ.get("GSC_BENCH_BATCH", "0")), help="proofs per GPU per step (default 8192 ChaCha, 1024 AES, 3072 mixed)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="besides the headline: verify a sample of the last timed step's proofs, the roofline and stage "
+                                                         "figures of the dominant kernel, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="write what the last timed step returned (proofs, ciphertexts) as float32 DIR/<name>.npy; "
+                                                                      "fixes the prover randomness so that two builds can be compared output for output")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
     ap.add_argument("--cpu-cores", type=int, default=0, help="host cores for the CPU baseline (default: all the process may run on)")
-    ap.add_argument("--verify", type=int, default=1024, help="proofs of the LAST timed step checked with libverify.so after the clock stops (0 = none)")
+    ap.add_argument("--verify", type=int, default=1024, help="with --full: proofs of the LAST timed step checked with libverify.so after the clock stops (0 = none)")
     ap.add_argument("--force-dist", action="store_true", help="initialise torch.distributed even with one rank (rehearsal of the multi-GPU code path on a one-GPU box)")
     ap.add_argument("--in-library", action="store_true", help="ONE process drives all --gpus devices through the library's own replicas (GSC_DEVICES=0..N-1): "
                                                                "what a single FFI host (Go / node) would do; one call of N x batch statements per step")
@@ -399,6 +431,8 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if args.in_library:
         devices = [int(x) for x in args.devices.split(",")] if args.devices else list(range(args.gpus))
         if len(devices) != args.gpus:
@@ -451,6 +485,8 @@ def main():
     g = None
     vks = {}
     if not stub:
+        if args.dump_outputs:
+            os.environ["GSC_ENABLE_TEST_HOOKS"] = "1"              # read once, when libprove.so is loaded
         import gsc_loader
         g = gsc_loader.load()
         for name in names:
@@ -458,10 +494,12 @@ def main():
             r1cs = golden("r1cs." + name)
             if name == "chacha20":
                 pk, vks[name] = golden("pk.chacha20"), golden("vk.chacha20")
-            else:
-                pk, vks[name] = g.setup(r1cs)                        # the product's own Groth16 Setup (GPU), CSPRNG toxic waste
+            else:       # the product's own Groth16 Setup (GPU): CSPRNG toxic waste, or seeded keys when the outputs are dumped
+                pk, vks[name] = g.setup(r1cs, SETUP_SEEDS[name] if args.dump_outputs else None)
             if not g.init_algorithm(algo, pk, r1cs):
                 raise SystemExit("InitAlgorithm failed for " + name)
+        if args.dump_outputs:
+            g.set_deterministic_randomness(*DUMP_RANDOMNESS)
 
     # statements of every step are made before the clock starts (112 B each: "inputs resident"); output buffers are reused.
     # Statement number = rank * 2^44 + step id * 2^20 + position in the batch (xoshiro_records: reproducible by anyone).
@@ -484,6 +522,7 @@ def main():
         e.set()
     stubp = StubProver(BT) if stub else None
     last_json = {}
+    last_payload = []
 
     def kernel_stats(n):
         # (the library reports the CALLING thread's own last call: with several callers a step's row is that step's, not a neighbour's)
@@ -524,8 +563,10 @@ def main():
                     local = torch.from_numpy(frame).to(dev)
                 else:
                     local = torch.frombuffer(payload, dtype=torch.uint8).to(dev)
-                if k != last or stats is None:    # the last timed step's buffers stay untouched: they are verified after the clock stops
+                if k != last or stats is None:    # the last timed step's buffers stay untouched: they are verified / dumped after the clock stops
                     free[k % NC].set()
+                else:
+                    last_payload.append(payload)
                 gather_proofs(dist, local, rank, world, use_dist)
                 if stats is not None:
                     stats.append(st)
@@ -548,11 +589,28 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
 
+    if args.dump_outputs:
+        import base64
+        payload = last_payload[-1]
+        if stub:
+            arrays = {"proofs": np.frombuffer(payload, dtype=np.uint8).reshape(BT, -1)}
+        elif workload == "mixed":           # one row per statement; 164-byte ChaCha20 proofs are zero-padded to the 196 bytes of AES
+            proofs, cts = np.zeros((BT, 196), dtype=np.uint8), np.zeros((BT, 64), dtype=np.uint8)
+            for k, o in enumerate(json.loads(payload)):
+                p = base64.b64decode(o["proof"]["proofJson"])
+                proofs[k, :len(p)] = np.frombuffer(p, dtype=np.uint8)
+                cts[k] = np.frombuffer(base64.b64decode(o["publicSignals"]), dtype=np.uint8)
+            arrays = {"proofs": proofs, "ciphertexts": cts}
+        else:
+            pb, lb, cb = bufs[(args.steps - 1) % NC]
+            arrays = {"proofs": np.frombuffer(pb, dtype=np.uint8).reshape(BT, 196)[:, :plen], "ciphertexts": np.frombuffer(cb, dtype=np.uint8).reshape(BT, 64)}
+        dump_outputs(args.dump_outputs, arrays, rank, world)
+
     # ---- parity gate for the timed configuration (libraries/core_test.go:171): a sample of the LAST timed step's proofs,
     # spread over the batch (first / last wave, chunk and replica boundaries), goes through the product's verifier libverify.so under the
     # verifying key that belongs to the proving key in use.  A rejection fails the run: no line is printed.
     verified = 0
-    if not stub and args.verify > 0 and args.steps > 0:
+    if args.full and not stub and args.verify > 0:
         import base64
         for name in names:
             if not g.init_verifier(ALGOS[name][0], vks[name]):
@@ -601,12 +659,13 @@ def main():
             "n_gpus": ngpu, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * elapsed / args.steps, 3),
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u32 limbs (BN254 Fr/Fp, 254-bit modular integers)",
             "data": "synthetic",
-            "config": {"workload": "%s; 1xMI355X per rank: batch of %d independent proofs per GPU per step, CSPRNG (r,s); statements from xoshiro256** seeded 0x9E3779B97F4A7C15 + index" % (desc, B),
+            "config": {"workload": "%s; 1xMI355X per rank: batch of %d independent proofs per GPU per step, %s; statements from xoshiro256** seeded 0x9E3779B97F4A7C15 + index" % (desc, B, "fixed (r,s) (--dump-outputs)" if args.dump_outputs else "CSPRNG (r,s)"),
                        "batch_per_gpu": B, "callers": NC, "parallelism": par, "tables": "library defaults (multi-tenant)" if args.library_defaults else "single algorithm per device" if workload != "mixed" else "library defaults (multi-tenant)",
                        "engine": {n: g.describe(ALGOS[n][0]) for n in names} if g else "stub"},
-            "verified": verified,
         }
-        if not stub:
+        if args.full:
+            line["verified"] = verified
+        if args.full and not stub:
             # dominant kernel of the algorithm whose launch is longest; averaged over the timed steps
             per = {}
             for st in stats:

@@ -74,3 +74,22 @@ def test_engine_env_of_the_timed_run():
     assert bench.engine_env("mixed", 1024) == {"GSC_MAX_BATCH": "1024"}                    # library defaults: all three algorithms resident
     assert bench.engine_env("chacha20", 4096, share=2)["GSC_Z_TABLE_GB"] == "70"           # two replicas rehearsed on one device split its memory
     assert bench.engine_env("aes128", 1000)["GSC_MAX_BATCH"] == "1024"
+
+
+def test_dumped_outputs_stay_under_64_mb_as_a_fixed_sample(tmp_path):
+    import numpy as np
+    n = 150_000                                 # 150 000 x (196 + 64) float32 = 156 MB: more than may be written
+    idx = np.arange(n)
+    proofs = np.zeros((n, 196), dtype=np.uint8)
+    proofs[:, 0], proofs[:, 1], proofs[:, 2] = idx & 0xFF, (idx >> 8) & 0xFF, idx >> 16
+    arrays = {"proofs": proofs, "ciphertexts": np.full((n, 64), 7, dtype=np.uint8)}
+    for d, world in (("a", 1), ("b", 1), ("c", 2)):
+        bench.dump_outputs(str(tmp_path / d), arrays, rank=world - 1, world=world)
+        files = sorted(os.listdir(tmp_path / d))
+        assert sum(os.path.getsize(tmp_path / d / f) for f in files) <= bench.DUMP_BYTES_MAX // world
+        assert all(f.startswith("rank1_") for f in files) if world == 2 else files == ["ciphertexts.npy", "proofs.npy", "statement_index.npy"]
+    rows = np.load(tmp_path / "a" / "statement_index.npy")
+    p = np.load(tmp_path / "a" / "proofs.npy")
+    assert p.dtype == np.float32 and rows.dtype == np.float64 and 0 < len(rows) < n and (np.diff(rows) > 0).all()
+    assert (p[:, 0] + 256 * p[:, 1] + 65536 * p[:, 2] == rows).all()                  # row k of every file is statement rows[k]
+    assert (rows == np.load(tmp_path / "b" / "statement_index.npy")).all()            # the same sample every time

@@ -76,3 +76,31 @@ def test_eight_ranks_and_eight_in_library_replicas():
     line = json.loads([l for l in out.splitlines() if l.strip()][-1])
     assert line["n_gpus"] == 8 and "GSC_DEVICES=0,1,2,3,4,5,6,7" in line["config"]["parallelism"] and "one call of 512 statements per step" in line["config"]["parallelism"]
     assert abs(line["value"] - 8 * 2 * 64 / (line["ms_per_step"] * 2 / 1e3)) / line["value"] < 0.01
+
+
+def test_plain_run_times_its_steps_and_dumps_the_last_ones_outputs(tmp_path):
+    # `bench.py --gpus 1 --steps N --warmup W --dump-outputs DIR`: N timed steps, only the headline in the line (verification, roofline and
+    # CPU baseline belong to --full), and what the last timed step returned as float32 DIR/<name>.npy, identical from run to run.  The stub's
+    # "proof" of a statement is its record's sha256 repeated: the last of three timed steps is step id 2, records from index 2 << 20.
+    import hashlib
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    lines = []
+    for d in ("a", "b"):
+        out = subprocess.check_output([sys.executable, BENCH, "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "64", "--stub-prover",
+                                       "--dump-outputs", str(tmp_path / d)], env=_env(), timeout=300, stderr=subprocess.DEVNULL).decode()
+        lines.append(json.loads(out))
+    line = lines[0]
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and not {"verified", "roofline", "cpu_baseline"} & set(line)
+    assert abs(line["value"] - 3 * 64 / (line["ms_per_step"] * 3 / 1e3)) / line["value"] < 0.01
+    for name in ("proofs", "statement_index"):
+        a, b = np.load(tmp_path / "a" / (name + ".npy")), np.load(tmp_path / "b" / (name + ".npy"))
+        assert a.dtype in (np.float32, np.float64) and (a == b).all()
+    proofs = np.load(tmp_path / "a" / "proofs.npy")
+    recs = bench.xoshiro_records(64, 2 << 20)
+    assert proofs.shape == (64, 164)
+    for k in (0, 5, 63):
+        assert proofs[k].astype(np.uint8).tobytes() == hashlib.sha256(recs[112 * k:112 * (k + 1)]).digest() * 5 + bytes(4)
+    p = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "0", "--stub-prover"], env=_env(), capture_output=True, timeout=120)
+    assert p.returncode != 0 and b"--steps must be >= 1" in p.stderr

@@ -191,7 +191,7 @@ def test_the_timed_mixed_configuration_proves_3x1024_statements_bit_exactly(gsc,
 
 def _bench_line(*args):
     import json
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline"] + list(args), env=dict(os.environ), capture_output=True, text=True, timeout=900)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline"] + list(args), env=dict(os.environ), capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
     return json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
 
@@ -220,3 +220,27 @@ def test_bench_bookkeeping_of_a_single_statement_call():
     one = _bench_line("--steps", "6", "--warmup", "2", "--batch", "1", "--callers", "1", "--verify", "1")["roofline"]      # one caller: concurrent small calls would share a launch
     assert one["kernel"].startswith("k_wit_chain") and one["proofs_per_launch"] == 1 and one["columns_per_launch"] == 64      # ChaCha20-V3: the small-integer witness kernels
     assert one["algorithmic_bytes_per_launch"] == 3012224 and one["traffic"] is None
+
+
+def test_bench_dumps_the_proofs_of_its_last_timed_step(chacha_oracle, oracle, tmp_path):
+    # a plain run (no --full: no verification, no roofline, no CPU baseline) with --dump-outputs writes what the last timed step returned
+    # as float32 arrays; the run fixes (r, s), so statement k's proof is the oracle's proof of that record, byte for byte.  The last of
+    # two timed steps is step id 1: its records start at index 1 << 20 (bench.py: rank << 44 | step id << 20).
+    import json
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    out = tmp_path / "dump"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "256", "--dump-outputs", str(out)],
+                       env=dict(os.environ), capture_output=True, text=True, timeout=900)
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
+    line = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
+    assert line["steps"] == 2 and line["ms_per_step"] > 0 and not {"verified", "roofline", "cpu_baseline"} & set(line)
+    proofs, cts, rows = np.load(out / "proofs.npy"), np.load(out / "ciphertexts.npy"), np.load(out / "statement_index.npy")
+    assert proofs.dtype == cts.dtype == np.float32 and proofs.shape == (256, 164) and cts.shape == (256, 64) and (rows == np.arange(256)).all()
+    recs = bench.xoshiro_records(256, 1 << 20)
+    cs, pk, vk = chacha_oracle
+    for k in (0, 63, 64, 255):
+        rec = recs[112 * k:112 * (k + 1)]
+        want, want_ct = oracle.prove(cs, pk, "chacha20", rec[:32], rec[32:44], int.from_bytes(rec[44:48], "little"), rec[48:], *bench.DUMP_RANDOMNESS)
+        assert proofs[k].astype(np.uint8).tobytes() == want and cts[k].astype(np.uint8).tobytes() == want_ct, k

@@ -5,13 +5,13 @@ set -o pipefail
 export PYTHONUNBUFFERED=1
 O=gpurun_out/r03f; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-python bench.py > $O/bench_chacha20.json 2> $O/bench_chacha20.err && echo "bench chacha20 ok" &&
-for w in aes128 aes256 mixed; do python bench.py --workload $w --steps 5 --warmup 1 > $O/bench_$w.json 2> $O/bench_$w.err && echo "bench $w ok"; done &&
-for b in 1 16 32 64 256 1024; do python bench.py --batch $b --steps 24 --warmup 4 --no-cpu-baseline > $O/bench_chacha20_b$b.json 2> $O/bench_chacha20_b$b.err && echo "bench b$b ok"; done &&
-python bench.py --workload aes128 --batch 1 --steps 24 --warmup 4 --no-cpu-baseline > $O/bench_aes128_b1.json 2> $O/bench_aes128_b1.err && echo "aes b1 ok" &&
-python bench.py --force-dist --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_chacha20_forcedist.json 2> $O/bench_chacha20_forcedist.err && echo "force-dist ok" &&
-python bench.py --gpus 2 --in-library --devices 0,0 --batch 4096 --steps 6 --warmup 2 --no-cpu-baseline > $O/bench_chacha20_inlibrary_2x4096_rehearsal.json 2> $O/inlib1.err && echo "in-library 2x4096 ok" &&
-python bench.py --gpus 2 --in-library --devices 0,0 --batch 64 --callers 4 --steps 30 --warmup 6 --no-cpu-baseline > $O/bench_chacha20_inlibrary_2x64_rehearsal.json 2> $O/inlib2.err && echo "in-library 2x64 ok" &&
+python bench.py --full > $O/bench_chacha20.json 2> $O/bench_chacha20.err && echo "bench chacha20 ok" &&
+for w in aes128 aes256 mixed; do python bench.py --full --workload $w --steps 5 --warmup 1 > $O/bench_$w.json 2> $O/bench_$w.err && echo "bench $w ok"; done &&
+for b in 1 16 32 64 256 1024; do python bench.py --full --batch $b --steps 24 --warmup 4 --no-cpu-baseline > $O/bench_chacha20_b$b.json 2> $O/bench_chacha20_b$b.err && echo "bench b$b ok"; done &&
+python bench.py --full --workload aes128 --batch 1 --steps 24 --warmup 4 --no-cpu-baseline > $O/bench_aes128_b1.json 2> $O/bench_aes128_b1.err && echo "aes b1 ok" &&
+python bench.py --full --force-dist --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_chacha20_forcedist.json 2> $O/bench_chacha20_forcedist.err && echo "force-dist ok" &&
+python bench.py --full --gpus 2 --in-library --devices 0,0 --batch 4096 --steps 6 --warmup 2 --no-cpu-baseline > $O/bench_chacha20_inlibrary_2x4096_rehearsal.json 2> $O/inlib1.err && echo "in-library 2x4096 ok" &&
+python bench.py --full --gpus 2 --in-library --devices 0,0 --batch 64 --callers 4 --steps 30 --warmup 6 --no-cpu-baseline > $O/bench_chacha20_inlibrary_2x64_rehearsal.json 2> $O/inlib2.err && echo "in-library 2x64 ok" &&
 rocprofv3 --kernel-trace --stats -d $O/stats -o run --output-format csv -- python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline --verify 0 > $O/stats_bench.json 2> $O/stats.err && echo "stats ok" &&
 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $O/pmc_fetch -o run --output-format csv -- python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline --verify 0 > $O/pmc_fetch_bench.json 2> $O/pmc_fetch.err && echo "fetch ok" &&
 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $O/pmc_write -o run --output-format csv -- python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline --verify 0 > $O/pmc_write_bench.json 2> $O/pmc_write.err && echo "write ok" &&

@@ -9,7 +9,7 @@ rocprofv3 --kernel-trace --stats -d $O/stats -o run --output-format csv -- pytho
 rm -rf $O/stats/*kernel_trace.csv 2>/dev/null
 find $O -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $O/kernel_stats.csv
 grep -E "k_ntt|k_msm_win<bn254::Fp29f, true>" $O/kernel_stats.csv | cut -d, -f1-4 | cut -c1-200
-python bench.py --steps 10 --warmup 3 > $O/bench_chacha20.json 2> $O/bench_chacha20.err && python - <<'PY'
+python bench.py --full --steps 10 --warmup 3 > $O/bench_chacha20.json 2> $O/bench_chacha20.err && python - <<'PY'
 import json
 d = json.load(open("gpurun_out/r04i/bench_chacha20.json")); print(d["value"], d["ms_per_step"], d["stage_ms_last_step"], d["roofline_valu"]["frac"], d["roofline_valu"]["clock_mhz"])
 PY

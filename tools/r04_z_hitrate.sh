@@ -5,7 +5,7 @@ set -o pipefail
 export PYTHONUNBUFFERED=1 GSC_ENABLE_TEST_HOOKS=1
 O=gpurun_out/r04z; mkdir -p $O
 for b in 0 15 14 13 12 10 4; do
-  GSC_Z_EXP_ENTRY_BITS=$b python bench.py --steps 4 --warmup 1 --no-cpu-baseline --verify 0 > $O/bench_bits$b.json 2> $O/bench_bits$b.err || { tail -3 $O/bench_bits$b.err; exit 1; }
+  GSC_Z_EXP_ENTRY_BITS=$b python bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --verify 0 > $O/bench_bits$b.json 2> $O/bench_bits$b.err || { tail -3 $O/bench_bits$b.err; exit 1; }
   python - $b $O/bench_bits$b.json <<'PY'
 import json, sys
 d = json.load(open(sys.argv[2])); rv = d.get("roofline_valu", {})
