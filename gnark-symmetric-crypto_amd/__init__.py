@@ -20,7 +20,8 @@ CHACHA20, AES_128, AES_256 = 0, 1, 2                       # prove_impl.go:15-19
 ALGORITHM_NAMES = {0: "chacha20", 1: "aes-128-ctr", 2: "aes-256-ctr"}   # prove_impl.go:21-25
 
 EXPORTS = ["enforce_binding", "InitAlgorithm", "Free", "Prove", "ProveBatch", "gsc_prove_raw", "gsc_setup",
-           "gsc_set_deterministic_randomness", "gsc_debug_prove", "gsc_debug_vector", "gsc_describe", "gsc_last_stage_ms", "gsc_last_dominant_kernel", "gsc_last_kernel_clock", "gsc_debug_field_ops", "gsc_debug_compute_h", "gsc_debug_compute_d", "gsc_debug_secret_residue", "gsc_debug_clock_trace", "gsc_debug_glv_split"]
+           "gsc_set_deterministic_randomness", "gsc_debug_prove", "gsc_debug_vector", "gsc_describe", "gsc_last_stage_ms", "gsc_last_dominant_kernel", "gsc_last_kernel_clock", "gsc_debug_field_ops", "gsc_debug_compute_h", "gsc_debug_compute_d", "gsc_debug_secret_residue", "gsc_debug_clock_trace", "gsc_debug_glv_split",
+           "gsc_verify_init", "gsc_verify_raw", "VerifyBatch", "gsc_debug_pairing"]
 
 
 class GoSlice(C.Structure):
@@ -72,6 +73,14 @@ def lib():
         L.gsc_last_kernel_clock.argtypes = [C.c_ubyte, C.POINTER(C.c_float), C.POINTER(C.c_int)]
         L.gsc_debug_field_ops.restype = C.c_int
         L.gsc_debug_field_ops.argtypes = [C.c_int, C.c_int, C.c_char_p, C.c_char_p, C.c_void_p, C.c_size_t, C.c_int]
+        L.gsc_verify_init.restype = C.c_int
+        L.gsc_verify_init.argtypes = [C.c_ubyte, GoSlice]
+        L.gsc_verify_raw.restype = C.c_longlong
+        L.gsc_verify_raw.argtypes = [C.c_ubyte, C.c_char_p, C.c_void_p, C.c_char_p, C.c_size_t, C.c_void_p]
+        L.VerifyBatch.restype = ProveReturn
+        L.VerifyBatch.argtypes = [GoSlice]
+        L.gsc_debug_pairing.restype = C.c_longlong
+        L.gsc_debug_pairing.argtypes = [C.c_char_p, C.c_char_p, C.c_size_t, C.c_void_p]
         L.enforce_binding()
         _lib = L
     return _lib
@@ -297,6 +306,51 @@ def debug_compute_d(algorithm_id: int, ab_be: bytes, m: int) -> bytes:
     if L.gsc_debug_compute_d(algorithm_id, ab_be, m, out, len(out)) != n:
         raise RuntimeError("gsc_debug_compute_d failed")
     return out.raw
+
+
+# ---- GPU verifier in libprove.so (k_verify.hip): verdicts identical to libverify's Verify ----
+def verify_init(algorithm_id: int, verifying_key: bytes) -> bool:
+    """gsc_verify_init: load a verifying key (InitVerifier's bytes) for the GPU verifier."""
+    s, keep = _slice(verifying_key)
+    return bool(lib().gsc_verify_init(algorithm_id, s))
+
+
+def verify_raw(algorithm_id: int, proofs: bytes, lens, signals: bytes, n: int = None):
+    """gsc_verify_raw: n proofs in 196-byte slots (prove_raw's layout), their lengths, n x 144 signal bytes -> list of 0/1 verdicts.
+    Raises RuntimeError when no key is loaded (-1) or on a device error (-2)."""
+    n = len(lens) if n is None else n
+    assert len(proofs) >= 196 * n and len(signals) >= 144 * n
+    lens_arr = (C.c_uint32 * max(n, 1))(*lens[:n])
+    out = C.create_string_buffer(max(n, 1))
+    rc = lib().gsc_verify_raw(algorithm_id, bytes(proofs), lens_arr, bytes(signals), n, out)
+    if rc < 0:
+        raise RuntimeError("gsc_verify_raw failed (%d): %s" % (rc, "no key loaded" if rc == -1 else "device error"))
+    return list(out.raw[:n])
+
+
+def verify_batch(items) -> list:
+    """VerifyBatch: list of Verify inputs (dicts; bytes values become arrays) -> list of bools."""
+    enc = [{k: (list(v) if isinstance(v, (bytes, bytearray)) else v) for k, v in it.items()} if isinstance(it, dict) else it for it in items]
+    s, keep = _slice(json.dumps(enc).encode())
+    return json.loads(_take(lib().VerifyBatch(s)))
+
+
+def verify_batch_bytes(params_json: bytes) -> bytes:
+    """VerifyBatch on already encoded JSON; returns the raw JSON bytes."""
+    s, keep = _slice(params_json)
+    return _take(lib().VerifyBatch(s))
+
+
+def debug_pairing(g1_points, g2_points):
+    """TEST HOOK: reduced pairings on the device.  g1_points: [(x, y)] ints (None = infinity), g2_points: [((x0, x1), (y0, y1))]
+    -> list of 12-tuples of ints, element 2i + j = component j (of 1, u) of the w^i coefficient."""
+    n = len(g1_points)
+    b1 = b"".join(bytes(64) if P is None else P[0].to_bytes(32, "big") + P[1].to_bytes(32, "big") for P in g1_points)
+    b2 = b"".join(bytes(128) if Q is None else Q[0][1].to_bytes(32, "big") + Q[0][0].to_bytes(32, "big") + Q[1][1].to_bytes(32, "big") + Q[1][0].to_bytes(32, "big") for Q in g2_points)
+    out = C.create_string_buffer(384 * max(n, 1))
+    if lib().gsc_debug_pairing(b1, b2, n, out) != n:
+        raise RuntimeError("gsc_debug_pairing failed (test hooks off?)")
+    return [tuple(int.from_bytes(out.raw[384 * i + 32 * c:384 * i + 32 * c + 32], "big") for c in range(12)) for i in range(n)]
 
 
 # ---- libverify (CPU-side, libraries/verifier/libverify.go:14-17) ----

@@ -298,6 +298,8 @@ std::string prove_one_json(const char* data, size_t len, DebugVectors* dbg) {
 
 }  // namespace
 
+long long gsc_verify_debug_pairing_impl(const uint8_t* g1, const uint8_t* g2, size_t n, uint8_t* out);      // verify_gpu.cpp
+
 extern "C" {
 
 void enforce_binding(void) {}
@@ -453,6 +455,10 @@ int gsc_debug_clock_trace(uint32_t n, uint32_t interval_us, unsigned long long* 
     catch (const std::exception& e) { printf("%s\n", e.what()); return -1; }
 }
 
+long long gsc_debug_pairing(const uint8_t* g1, const uint8_t* g2, size_t n, uint8_t* out) {
+    if (hooks_refused("gsc_debug_pairing") || (n && (!g1 || !g2 || !out))) return -1;
+    return gsc_verify_debug_pairing_impl(g1, g2, n, out);
+}
 int gsc_debug_glv_split(const uint8_t* k, uint8_t* out) {
     if (hooks_refused("gsc_debug_glv_split") || !k || !out) return -1;
     uint32_t w[8]; memcpy(w, k, 32);

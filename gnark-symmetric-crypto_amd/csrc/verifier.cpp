@@ -10,6 +10,7 @@
 #include "host_ciphers.hpp"
 #include "host_field.hpp"
 #include "json.hpp"
+#include "verify_common.hpp"
 #include <array>
 #include <cstdio>
 #include <cstdlib>
@@ -294,21 +295,18 @@ bool pairing_product_is_one(const std::vector<std::pair<G1, G2>>& v) {
     return r.is_one();
 }
 
-// ---- verifying key ----
+// ---- verifying key: layout from verify_common, points decoded here ----
 struct VerifyingKey { G1 alpha; G2 beta, gamma, delta; std::vector<G1> K; bool has_commitment = false; G2 ped_g, ped_gsn; };
-uint32_t be32(const uint8_t* p) { return (uint32_t)p[0] << 24 | (uint32_t)p[1] << 16 | (uint32_t)p[2] << 8 | p[3]; }
 std::unique_ptr<VerifyingKey> parse_vk(const uint8_t* b, size_t n) {
-    auto vk = std::make_unique<VerifyingKey>(); size_t i = 0; G1 skip1;
-    auto need = [&](size_t k) { if (i + k > n) throw std::runtime_error("vk: truncated"); };
-    auto g1 = [&](G1& p) { need(32); if (!g1_decode(b + i, p)) throw std::runtime_error("vk: bad G1 point"); i += 32; };
-    auto g2 = [&](G2& p) { need(64); if (!g2_decode(b + i, p)) throw std::runtime_error("vk: bad G2 point"); i += 64; };
-    g1(vk->alpha); g1(skip1); g2(vk->beta); g2(vk->gamma); g1(skip1); g2(vk->delta);
-    need(4); uint32_t nk = be32(b + i); i += 4; vk->K.resize(nk); for (auto& p : vk->K) g1(p);
-    need(4); uint32_t outer = be32(b + i); i += 4; if (outer > 1) throw std::runtime_error("vk: more than one commitment");
-    for (uint32_t o = 0; o < outer; o++) { need(4); uint32_t inner = be32(b + i); i += 4; if (inner) throw std::runtime_error("vk: public committed wires are not supported"); }
-    need(4); uint32_t nck = be32(b + i); i += 4; if (nck != outer) throw std::runtime_error("vk: commitment key count");
-    if (nck) { vk->has_commitment = true; g2(vk->ped_g); g2(vk->ped_gsn); }
-    if (i != n) throw std::runtime_error("vk: trailing bytes");
+    gsc::verify::VkLayout lay; std::string err;
+    if (!gsc::verify::parse_vk_layout(b, n, lay, &err)) throw std::runtime_error(err);
+    auto vk = std::make_unique<VerifyingKey>(); G1 skip1;
+    auto g1 = [&](size_t at, G1& p) { if (!g1_decode(b + at, p)) throw std::runtime_error("vk: bad G1 point"); };
+    auto g2 = [&](size_t at, G2& p) { if (!g2_decode(b + at, p)) throw std::runtime_error("vk: bad G2 point"); };
+    g1(lay.alpha, vk->alpha); g1(lay.g1_beta, skip1); g2(lay.beta, vk->beta); g2(lay.gamma, vk->gamma); g1(lay.g1_delta, skip1); g2(lay.delta, vk->delta);
+    vk->K.resize(lay.K.size()); for (size_t k = 0; k < lay.K.size(); k++) g1(lay.K[k], vk->K[k]);
+    vk->has_commitment = lay.has_commitment;
+    if (lay.has_commitment) { g2(lay.ped_g, vk->ped_g); g2(lay.ped_gsn, vk->ped_gsn); }
     return vk;
 }
 
@@ -333,56 +331,27 @@ Fr hash_to_fr(const uint8_t* msg, size_t n, const char* dst) {      // gnark has
     return acc;
 }
 
-bool bytes_field(const gsc::JsonValue& v, std::vector<uint8_t>& out) {
-    if (v.kind == gsc::JsonValue::String) { size_t bad; return gsc::base64_decode(v.text, out, bad); }
-    if (v.kind == gsc::JsonValue::Null) { out.clear(); return true; }
-    if (v.kind != gsc::JsonValue::Array) return false;
-    out.clear();
-    for (auto& e : v.items) { if (e.kind != gsc::JsonValue::Number || e.text.find_first_not_of("0123456789") != std::string::npos || e.text.size() > 3 || atoi(e.text.c_str()) > 255) return false; out.push_back((uint8_t)atoi(e.text.c_str())); }
-    return true;
-}
-bool fold_eq(const std::string& a, const char* b) { if (a.size() != strlen(b)) return false; for (size_t i = 0; i < a.size(); i++) if ((a[i] | 32) != (b[i] | 32)) return false; return true; }
-
 bool verify_impl(const char* data, size_t len) {
     gsc::JsonValue root = gsc::json_parse(data, len);
-    if (root.kind != gsc::JsonValue::Object) return false;
-    std::string cipher; std::vector<uint8_t> proof, sig;
-    for (auto& kv : root.members) {
-        if (fold_eq(kv.first, "cipher")) { if (kv.second.kind == gsc::JsonValue::String) cipher = kv.second.text; else if (kv.second.kind != gsc::JsonValue::Null) return false; }
-        else if (fold_eq(kv.first, "proof")) { if (!bytes_field(kv.second, proof)) return false; }
-        else if (fold_eq(kv.first, "publicSignals")) { if (!bytes_field(kv.second, sig)) return false; }
-    }
-    int id = -1; for (int k = 0; k < 3; k++) if (cipher == kNames[k]) id = k;
+    std::vector<uint8_t> proof, sig; int id;
+    if (!gsc::verify::parse_request(root, id, proof, sig)) return false;
     if (id < 0) return false;                                   // verify_impl.go:78-81: unknown cipher -> false
     const VerifyingKey* vk;
     { std::lock_guard<std::mutex> l(g_mu); load_dir_once(); vk = g_vk[id].get(); }
     if (!vk) { printf("verifying key for %s is not loaded\n", kNames[id]); return false; }
-    if (sig.size() != 144) { printf("public signals must be 144 bytes, not %zu\n", sig.size()); return false; }   // verifiers.go:52-55
-    const uint8_t *ct = sig.data(), *nonce = ct + 64, *ctr = ct + 76, *pt = ct + 80;
-    // public inputs in circuit order (verifiers.go:18-23 / :35-40), as (base index into vk.K[1..], scalar)
+    if (sig.size() != gsc::verify::kSignalBytes) { printf("public signals must be 144 bytes, not %zu\n", sig.size()); return false; }   // verifiers.go:52-55
+    // public inputs in circuit order (verify_common: verifiers.go:18-23 / :35-40); bits select K points, AES values scale them
+    if (!gsc::verify::key_fits(id, vk->K.size(), vk->has_commitment)) return false;
+    std::vector<uint32_t> vals; gsc::verify::public_inputs(id, sig.data(), vals);
+    const size_t npub = vals.size();
     std::vector<G1> terms; terms.push_back(vk->K.at(0));
-    size_t npub = 0;
-    if (id == 0) {        // bits: Counter[32] (LE value), Nonce[3][32] (LE words), In[16][32] (BE words), Out[16][32] (BE words)
-        auto word = [](const uint8_t* p, bool be) { return be ? (uint32_t)p[0] << 24 | (uint32_t)p[1] << 16 | (uint32_t)p[2] << 8 | p[3] : (uint32_t)p[3] << 24 | (uint32_t)p[2] << 16 | (uint32_t)p[1] << 8 | p[0]; };
-        std::vector<uint32_t> words; words.push_back(word(ctr, false));
-        for (int i = 0; i < 3; i++) words.push_back(word(nonce + 4 * i, false));
-        for (int i = 0; i < 16; i++) words.push_back(word(pt + 4 * i, true));
-        for (int i = 0; i < 16; i++) words.push_back(word(ct + 4 * i, true));
-        npub = 32 * words.size();
-        if (vk->K.size() != 1 + npub) return false;
-        for (size_t w = 0; w < words.size(); w++) for (int bit = 0; bit < 32; bit++) if ((words[w] >> bit) & 1) terms.push_back(vk->K[1 + 32 * w + bit]);
-    } else {              // bytes: Nonce[12], Counter (BE u32), Plaintext[64], Ciphertext[64]
-        std::vector<uint32_t> vals; for (int i = 0; i < 12; i++) vals.push_back(nonce[i]);
-        vals.push_back((uint32_t)ctr[0] << 24 | (uint32_t)ctr[1] << 16 | (uint32_t)ctr[2] << 8 | ctr[3]);
-        for (int i = 0; i < 64; i++) vals.push_back(pt[i]);
-        for (int i = 0; i < 64; i++) vals.push_back(ct[i]);
-        npub = vals.size();
-        if (vk->K.size() != 1 + npub + (vk->has_commitment ? 1 : 0)) return false;
-        for (size_t i = 0; i < npub; i++) if (vals[i]) terms.push_back(g1_mul(vk->K[1 + i], U256{{vals[i], 0, 0, 0}}));
+    for (size_t i = 0; i < npub; i++) {
+        if (!vals[i]) continue;
+        terms.push_back(id == 0 ? vk->K[1 + i] : g1_mul(vk->K[1 + i], U256{{vals[i], 0, 0, 0}}));
     }
     // proof (App. B.3)
     const size_t nc = vk->has_commitment ? 1 : 0;
-    if (proof.size() != 164 + 32 * nc || be32(proof.data() + 128) != nc) return false;
+    if (!gsc::verify::proof_shape_ok(proof.data(), proof.size(), vk->has_commitment)) return false;
     G1 Ar, Krs, D{Fp::zero(), Fp::zero(), true}, pok; G2 Bs;
     if (!g1_decode(proof.data(), Ar) || !g2_decode(proof.data() + 32, Bs) || !g1_decode(proof.data() + 96, Krs)) return false;
     if (nc && !g1_decode(proof.data() + 132, D)) return false;

@@ -1,0 +1,252 @@
+// GPU verifier in libprove.so: gsc_verify_init, gsc_verify_raw, VerifyBatch, gsc_debug_pairing (include/libprove.h).
+// Verdicts are those of libverify.so's Verify (verifier.cpp); the host only checks sizes and packs bytes (verify_common),
+// decoding and every curve operation run in k_verify.hip.  Each key owns a non-blocking stream and chunk buffers on one device
+// (GSC_DEVICE, or the first of GSC_DEVICES); calls on the same key are serialised, and nothing here synchronises the device.
+#include "../../include/libprove.h"
+#include "json.hpp"
+#include "verify_common.hpp"
+#include "verify_kernels.hpp"
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <fstream>
+#include <iterator>
+#include <memory>
+#include <mutex>
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+namespace {
+
+using namespace gsc;
+using namespace gsc::vfy;
+namespace V = gsc::verify;
+
+constexpr size_t kChunk = 65536;      // proofs per device pass: buffers are allocated once per key, so memory does not grow with n
+
+struct HipError : std::runtime_error { using std::runtime_error::runtime_error; };
+void ck(hipError_t e, const char* what) { if (e != hipSuccess) throw HipError(std::string(what) + ": " + hipGetErrorString(e)); }
+
+int verify_device() {
+    if (const char* dv = getenv("GSC_DEVICES")) { const char* q = dv; while (*q == ',' || *q == ' ') q++; if (*q) return atoi(q); }
+    if (const char* d = getenv("GSC_DEVICE")) return atoi(d);
+    return 0;
+}
+
+template <class T> struct DevBuf {
+    T* p = nullptr;
+    void alloc(size_t n) { ck(hipMalloc(&p, n * sizeof(T) + 1), "hipMalloc"); }
+    ~DevBuf() { if (p) (void)hipFree(p); }
+};
+
+struct GpuKey {
+    int device = 0, algo = 0;
+    hipStream_t stream = nullptr;
+    bool has_commitment = false, fits = false;
+    DevBuf<VP1> K, table, ctable;
+    DevBuf<Line> lines;
+    KeyDev kd{};
+    std::mutex mu;                       // one call at a time on the chunk buffers below
+    DevBuf<uint8_t> proofs, win, pre, verdict;
+    DevBuf<ProofDev> pd;
+    ~GpuKey() { if (stream) { (void)hipStreamSynchronize(stream); (void)hipStreamDestroy(stream); } }
+};
+
+std::mutex g_mu;
+// never destroyed: a key released at process exit would call into a HIP runtime that may already be gone
+std::shared_ptr<GpuKey>* const g_keys = new std::shared_ptr<GpuKey>[3];
+bool g_dir_tried = false;
+const char* kFiles[3] = {"vk.chacha20", "vk.aes128", "vk.aes256"};
+
+std::shared_ptr<GpuKey> build_key(int algo, const uint8_t* b, size_t n) {
+    V::VkLayout lay; std::string err;
+    if (!V::parse_vk_layout(b, n, lay, &err)) { printf("%s\n", err.c_str()); return nullptr; }
+    auto k = std::make_shared<GpuKey>();
+    k->device = verify_device();
+    k->algo = algo;
+    ck(hipSetDevice(k->device), "hipSetDevice");
+    ck(hipStreamCreateWithFlags(&k->stream, hipStreamNonBlocking), "hipStreamCreate");
+    hipStream_t s = k->stream;
+    // compressed points: G1 alpha, beta1, delta1, K...; G2 beta, gamma, delta (, ped_g, ped_gsn)
+    std::vector<uint8_t> g1, g2;
+    auto add = [&](std::vector<uint8_t>& v, size_t at, size_t len) { v.insert(v.end(), b + at, b + at + len); };
+    add(g1, lay.alpha, 32); add(g1, lay.g1_beta, 32); add(g1, lay.g1_delta, 32);
+    for (size_t at : lay.K) add(g1, at, 32);
+    add(g2, lay.beta, 64); add(g2, lay.gamma, 64); add(g2, lay.delta, 64);
+    if (lay.has_commitment) { add(g2, lay.ped_g, 64); add(g2, lay.ped_gsn, 64); }
+    const size_t n1 = g1.size() / 32, n2 = g2.size() / 64;
+    DevBuf<uint8_t> d1, d2; DevBuf<VP1> p1; DevBuf<VP2> p2; DevBuf<int8_t> st;
+    d1.alloc(g1.size()); d2.alloc(g2.size()); p1.alloc(n1); p2.alloc(5); st.alloc(n1 + n2);
+    ck(hipMemcpyAsync(d1.p, g1.data(), g1.size(), hipMemcpyHostToDevice, s), "copy");
+    ck(hipMemcpyAsync(d2.p, g2.data(), g2.size(), hipMemcpyHostToDevice, s), "copy");
+    launch_verify_key_points(d1.p, n1, d2.p, n2, p1.p, p2.p, st.p, s);
+    std::vector<int8_t> hs(n1 + n2);
+    std::vector<VP1> h1(n1); VP2 h2[5];
+    ck(hipMemcpyAsync(hs.data(), st.p, hs.size(), hipMemcpyDeviceToHost, s), "copy");
+    ck(hipMemcpyAsync(h1.data(), p1.p, n1 * sizeof(VP1), hipMemcpyDeviceToHost, s), "copy");
+    ck(hipMemcpyAsync(h2, p2.p, n2 * sizeof(VP2), hipMemcpyDeviceToHost, s), "copy");
+    ck(hipStreamSynchronize(s), "key points");
+    for (int8_t v : hs) if (v < 0) { printf("vk: bad point\n"); return nullptr; }
+    k->has_commitment = lay.has_commitment;
+    k->fits = V::key_fits(algo, lay.K.size(), lay.has_commitment);
+    KeyDev& kd = k->kd;
+    kd.has_commitment = lay.has_commitment; kd.fits = k->fits;
+    kd.alpha = h1[0];
+    for (int i = 0; i < 5; i++) kd.qinf[i] = (i < (int)n2) ? h2[i].inf : 1;
+    k->lines.alloc(5 * kLineSteps);
+    launch_verify_lines(p2.p, n2, k->lines.p, s);
+    for (int i = 0; i < 5; i++) kd.lines[i] = k->lines.p + i * kLineSteps;
+    k->table.alloc(V::kWindows * 256); k->ctable.alloc(kCommitWindows * 256);
+    kd.table = k->table.p; kd.ctable = k->ctable.p;
+    if (k->fits) {
+        kd.k0 = h1[3];
+        std::vector<uint32_t> desc(2 * V::kWindows), cdesc(2 * kCommitWindows);
+        for (size_t j = 0; j < V::kWindows; j++) { uint32_t f, sh; V::window_base(algo, j, f, sh); desc[2 * j] = f; desc[2 * j + 1] = sh | (algo == 0 ? 1u << 16 : 0u); }
+        for (int j = 0; j < kCommitWindows; j++) { cdesc[2 * j] = (uint32_t)(1 + V::num_public(algo)); cdesc[2 * j + 1] = 8 * j; }
+        DevBuf<uint32_t> dd, dc; dd.alloc(desc.size()); dc.alloc(cdesc.size());
+        ck(hipMemcpyAsync(dd.p, desc.data(), desc.size() * 4, hipMemcpyHostToDevice, s), "copy");
+        ck(hipMemcpyAsync(dc.p, cdesc.data(), cdesc.size() * 4, hipMemcpyHostToDevice, s), "copy");
+        const VP1* Kd = p1.p + 3;     // K[0] is the fourth G1 point of the upload
+        launch_verify_tables(Kd, dd.p, V::kWindows, k->table.p, s);
+        if (lay.has_commitment) launch_verify_tables(Kd, dc.p, kCommitWindows, k->ctable.p, s);
+        ck(hipStreamSynchronize(s), "key tables");
+    }
+    ck(hipStreamSynchronize(s), "key lines");
+    k->proofs.alloc(kChunk * kProofSlot); k->win.alloc(kChunk * V::kWindows); k->pre.alloc(kChunk); k->verdict.alloc(kChunk); k->pd.alloc(kChunk);
+    return k;
+}
+
+void load_dir_once() {      // like libverify: keys from GSC_VK_DIR on first use (g_mu held)
+    if (g_dir_tried) return;
+    g_dir_tried = true;
+    const char* dir = getenv("GSC_VK_DIR"); if (!dir) return;
+    for (int a = 0; a < 3; a++) if (!g_keys[a]) {
+        std::ifstream f(std::string(dir) + "/" + kFiles[a], std::ios::binary); if (!f) continue;
+        std::vector<uint8_t> buf((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+        try { g_keys[a] = build_key(a, buf.data(), buf.size()); } catch (const std::exception& e) { printf("%s\n", e.what()); }
+    }
+}
+std::shared_ptr<GpuKey> key_for(int algo) { std::lock_guard<std::mutex> l(g_mu); load_dir_once(); return g_keys[algo]; }
+
+// verdicts for n items; proofs in 196-byte slots.  Returns the number accepted; throws HipError on a device error.
+long long run_verify(GpuKey& k, const uint8_t* proofs, const uint32_t* lens, const uint8_t* signals, size_t n, uint8_t* verdicts) {
+    std::lock_guard<std::mutex> l(k.mu);
+    ck(hipSetDevice(k.device), "hipSetDevice");
+    long long accepted = 0;
+    std::vector<uint8_t> win(kChunk * V::kWindows), pre(kChunk);
+    for (size_t off = 0; off < n; off += kChunk) {
+        const size_t m = std::min(kChunk, n - off);
+        if (!k.fits) { memset(verdicts + off, 0, m); continue; }
+        for (size_t i = 0; i < m; i++) {
+            const size_t j = off + i;
+            pre[i] = lens[j] <= (uint32_t)kProofSlot && V::proof_shape_ok(proofs + kProofSlot * j, lens[j], k.has_commitment);
+            V::public_windows(k.algo, signals + V::kSignalBytes * j, win.data() + V::kWindows * i);
+        }
+        hipStream_t s = k.stream;
+        ck(hipMemcpyAsync(k.proofs.p, proofs + kProofSlot * off, m * kProofSlot, hipMemcpyHostToDevice, s), "copy");
+        ck(hipMemcpyAsync(k.win.p, win.data(), m * V::kWindows, hipMemcpyHostToDevice, s), "copy");
+        ck(hipMemcpyAsync(k.pre.p, pre.data(), m, hipMemcpyHostToDevice, s), "copy");
+        launch_verify_prep(k.kd, k.proofs.p, k.win.p, k.pre.p, k.pd.p, m, s);
+        ck(hipGetLastError(), "k_verify_prep");
+        launch_verify_pairing(k.kd, k.pd.p, k.verdict.p, nullptr, m, s);
+        ck(hipGetLastError(), "k_verify_pairing");
+        ck(hipMemcpyAsync(verdicts + off, k.verdict.p, m, hipMemcpyDeviceToHost, s), "copy");
+        ck(hipStreamSynchronize(s), "verify");
+        for (size_t i = 0; i < m; i++) accepted += verdicts[off + i];
+    }
+    return accepted;
+}
+
+struct Prove_return to_c(const std::string& s) {
+    char* p = (char*)malloc(s.size() + 1);
+    memcpy(p, s.data(), s.size()); p[s.size()] = 0;
+    return Prove_return{p, (GoInt)s.size()};
+}
+
+}  // namespace
+
+extern "C" {
+
+int gsc_verify_init(GoUint8 algorithmID, GoSlice verifyingKey) {
+    if (algorithmID > 2 || !verifyingKey.data || verifyingKey.len <= 0) return 0;
+    try {
+        auto k = build_key(algorithmID, (const uint8_t*)verifyingKey.data, (size_t)verifyingKey.len);
+        if (!k) return 0;
+        std::lock_guard<std::mutex> l(g_mu);
+        g_keys[algorithmID] = std::move(k);
+        return 1;
+    } catch (const std::exception& e) { printf("gsc_verify_init: %s\n", e.what()); return 0; }
+}
+
+long long gsc_verify_raw(GoUint8 algorithmID, const uint8_t* proofs, const uint32_t* proof_lens, const uint8_t* signals, size_t n, uint8_t* verdicts) {
+    if (n) memset(verdicts, 0, n);
+    if (algorithmID > 2) return -1;
+    auto k = key_for(algorithmID);
+    if (!k) return -1;
+    if (!n) return 0;
+    try { return run_verify(*k, proofs, proof_lens, signals, n, verdicts); }
+    catch (const std::exception& e) { printf("gsc_verify_raw: %s\n", e.what()); memset(verdicts, 0, n); return -2; }
+}
+
+struct Prove_return VerifyBatch(GoSlice params) {
+    std::string out;
+    try {
+        JsonValue root;
+        try { root = json_parse((const char*)params.data, params.len > 0 ? (size_t)params.len : 0); }
+        catch (const JsonSyntaxError& e) { return to_c("{\"Offset\":" + std::to_string(e.offset) + "}"); }
+        if (root.kind != JsonValue::Array) return to_c(json_quote("VerifyBatch expects a JSON array"));
+        const size_t n = root.items.size();
+        std::vector<uint8_t> verdict(n, 0);
+        // group the well-formed items by algorithm: one gsc_verify_raw pass each, verdicts put back in place
+        std::vector<size_t> where[3];
+        std::vector<uint8_t> slots[3], sigs[3]; std::vector<uint32_t> lens[3];
+        for (size_t i = 0; i < n; i++) {
+            int algo; std::vector<uint8_t> proof, sig;
+            if (!V::parse_request(root.items[i], algo, proof, sig) || algo < 0 || sig.size() != V::kSignalBytes) continue;
+            where[algo].push_back(i);
+            std::vector<uint8_t> slot(kProofSlot, 0);
+            memcpy(slot.data(), proof.data(), std::min(proof.size(), (size_t)kProofSlot));
+            slots[algo].insert(slots[algo].end(), slot.begin(), slot.end());
+            sigs[algo].insert(sigs[algo].end(), sig.begin(), sig.end());
+            lens[algo].push_back(proof.size() > kProofSlot ? UINT32_MAX : (uint32_t)proof.size());
+        }
+        for (int a = 0; a < 3; a++) {
+            const size_t m = where[a].size();
+            if (!m) continue;
+            std::vector<uint8_t> v(m);
+            if (gsc_verify_raw((GoUint8)a, slots[a].data(), lens[a].data(), sigs[a].data(), m, v.data()) < 0) continue;   // no key: false
+            for (size_t i = 0; i < m; i++) verdict[where[a][i]] = v[i];
+        }
+        out = "[";
+        for (size_t i = 0; i < n; i++) { if (i) out += ","; out += verdict[i] ? "true" : "false"; }
+        out += "]";
+    } catch (const std::exception& e) { out = json_quote(e.what()); }
+    return to_c(out);
+}
+
+}  // extern "C"
+
+// gsc_debug_pairing's body: capi.cpp exports the hook behind its GSC_ENABLE_TEST_HOOKS gate and calls this
+long long gsc_verify_debug_pairing_impl(const uint8_t* g1, const uint8_t* g2, size_t n, uint8_t* out) {
+    if (!n) return 0;
+    try {
+        ck(hipSetDevice(verify_device()), "hipSetDevice");
+        hipStream_t s; ck(hipStreamCreateWithFlags(&s, hipStreamNonBlocking), "hipStreamCreate");
+        std::unique_ptr<void, void (*)(void*)> guard((void*)s, [](void* p) { (void)hipStreamSynchronize((hipStream_t)p); (void)hipStreamDestroy((hipStream_t)p); });
+        DevBuf<uint8_t> d1, d2, dout, verdict; DevBuf<ProofDev> pd; DevBuf<F12> f;
+        d1.alloc(64 * n); d2.alloc(128 * n); dout.alloc(384 * n); verdict.alloc(n); pd.alloc(n); f.alloc(n);
+        ck(hipMemcpyAsync(d1.p, g1, 64 * n, hipMemcpyHostToDevice, s), "copy");
+        ck(hipMemcpyAsync(d2.p, g2, 128 * n, hipMemcpyHostToDevice, s), "copy");
+        KeyDev kd{};
+        kd.fits = 1; kd.has_commitment = 0;
+        for (int i = 0; i < 5; i++) kd.qinf[i] = 1;
+        kd.alpha.inf = 1;
+        launch_verify_debug_points(d1.p, d2.p, pd.p, n, s);
+        launch_verify_pairing(kd, pd.p, verdict.p, f.p, n, s);
+        launch_verify_f12_bytes(f.p, dout.p, n, s);
+        ck(hipMemcpyAsync(out, dout.p, 384 * n, hipMemcpyDeviceToHost, s), "copy");
+        ck(hipStreamSynchronize(s), "debug pairing");
+        return (long long)n;
+    } catch (const std::exception& e) { printf("gsc_debug_pairing: %s\n", e.what()); return -1; }
+}

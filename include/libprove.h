@@ -120,6 +120,28 @@ extern int gsc_last_dominant_kernel(GoUint8 algorithmID, char *name, size_t cap,
  * that made none, the chunk that finished last on any replica. */
 extern int gsc_last_kernel_clock(GoUint8 algorithmID, float *clock_mhz, int *windows);
 
+/* ---- GPU verifier (k_verify.hip): verdicts identical to libverify.so's Verify, computed on the device ---- */
+/* Loads a verifying key (gnark VerifyingKey.WriteTo bytes, as InitVerifier takes) for the GPU verifier.  algorithmID: 0 chacha20,
+ * 1 aes-128-ctr, 2 aes-256-ctr.  Needs no InitAlgorithm.  1 on success, 0 on a bad key (a point that does not decode, a beta / gamma /
+ * delta outside G2, as libverify refuses it).  Loading again replaces the key.  Without a call, keys load on first use from
+ * GSC_VK_DIR (vk.chacha20, vk.aes128, vk.aes256), as libverify does.  Device: GSC_DEVICE, or the first of GSC_DEVICES. */
+extern int gsc_verify_init(GoUint8 algorithmID, GoSlice verifyingKey);
+/* n proofs of one algorithm.  proofs: n x 196-byte slots (gsc_prove_raw's layout), proof_lens[i] the length of proof i; signals:
+ * n x 144 bytes (ct | nonce | counter | pt, as Verify's publicSignals).  verdicts[i] = 1 iff Verify would accept item i.  Returns the
+ * number accepted, -1 if no key is loaded for the algorithm, -2 on a device error (then every verdict is 0).  Thread-safe; calls on
+ * one key run one after the other on the verifier's own stream, beside any proving. */
+extern long long gsc_verify_raw(GoUint8 algorithmID, const uint8_t *proofs, const uint32_t *proof_lens, const uint8_t *signals, size_t n,
+                                uint8_t *verdicts);
+/* JSON array of Verify inputs ({"cipher","proof","publicSignals"}; ciphers may be mixed) -> malloc'd JSON array of true/false,
+ * element i == Verify(element i).  A top-level syntax error gives {"Offset":n}, a non-array the quoted string
+ * "VerifyBatch expects a JSON array" (ProveBatch's shapes).  Release with Free. */
+extern struct Prove_return VerifyBatch(GoSlice params);
+/* TEST HOOK: n reduced pairings e(P_i, Q_i) = f^((p^12-1)/r) on the device.  P: 64 bytes x | y, Q: 128 bytes x.A1 | x.A0 | y.A1 | y.A0,
+ * big-endian canonical; all zero = infinity; points must lie on their curves.  out: 12 x 32 big-endian bytes per result, coefficient
+ * 2i + j = component j (of 1, u) of the w^i coefficient in Fp12 = Fp2[w]/(w^6 - (9+u)), Fp2 = Fp[u]/(u^2+1).  Returns n, -1 when hooks
+ * are off or on error. */
+extern long long gsc_debug_pairing(const uint8_t *g1_uncompressed, const uint8_t *g2_uncompressed, size_t n, uint8_t *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,105 @@
+"""Times the GPU verifier (gsc_verify_raw in libprove.so) against libverify.so's Verify on up to 16 host threads.
+
+Proofs come from gsc_prove_raw.  One JSON line per configuration: ChaCha20 at n = 1024, 8192, 65536 and AES-128 at 8192.  Every GPU
+verdict is checked (all proofs valid must be accepted; the same proofs with the signals of the next statement must be rejected), and
+the CPU rate is measured on a sample of the same proofs with the same check.
+
+    python tools/bench_verify.py [--sizes 1024,8192,65536] [--aes 8192] [--cpu-sample 2048] [--out FILE]
+"""
+import argparse
+import json
+import os
+import random
+import sys
+import time
+from concurrent.futures import ThreadPoolExecutor
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import gsc_loader  # noqa: E402
+from conftest import golden_bytes  # noqa: E402
+
+NAMES = {0: "chacha20", 1: "aes-128-ctr"}
+THREADS = 16
+
+
+def make_items(g, algo, n, seed):
+    rnd = random.Random(seed)
+    recs = b"".join(rnd.randbytes(32) + rnd.randbytes(12) + rnd.getrandbits(31).to_bytes(4, "little") + rnd.randbytes(64) for _ in range(n))
+    proofs, lens, cts = g.raw_buffers(n)
+    done = 0
+    while done < n:                                   # prove in calls of at most 16384 statements
+        m = min(16384, n - done)
+        sub = g.raw_buffers(m)
+        assert g.prove_raw_into(algo, recs[112 * done:112 * (done + m)], m, *sub) == m
+        proofs[196 * done:196 * (done + m)] = sub[0].raw
+        for k in range(m):
+            lens[done + k] = sub[1][k]
+        cts[64 * done:64 * (done + m)] = sub[2].raw
+        done += m
+    sig = bytearray()
+    for k in range(n):
+        rec = recs[112 * k:112 * k + 112]
+        ctr = rec[44:48] if algo == 0 else rec[44:48][::-1]
+        sig += cts.raw[64 * k:64 * k + 64] + rec[32:44] + ctr + rec[48:]
+    return proofs.raw, list(lens), bytes(sig)
+
+
+def run(g, algo, n, cpu_sample, seed):
+    proofs, lens, sig = make_items(g, algo, n, seed)
+    g.verify_raw(algo, proofs[:196 * 64], lens[:64], sig[:144 * 64])          # warm-up (kernel load)
+    t0 = time.perf_counter()
+    v = g.verify_raw(algo, proofs, lens, sig)
+    gpu_s = time.perf_counter() - t0
+    shifted = sig[144:] + sig[:144]
+    w = g.verify_raw(algo, proofs, lens, shifted)
+    ok = v == [1] * n and w == [0] * n
+    m = min(cpu_sample, n)
+    items = [{"cipher": NAMES[algo], "proof": list(proofs[196 * k:196 * k + lens[k]]), "publicSignals": list(sig[144 * k:144 * k + 144])} for k in range(m)]
+    enc = [json.dumps(it).encode() for it in items]
+    t0 = time.perf_counter()
+    with ThreadPoolExecutor(THREADS) as ex:
+        cpu = list(ex.map(g.verify, enc))
+    cpu_s = time.perf_counter() - t0
+    ok = ok and all(cpu)
+    return {"tool": "bench_verify", "cipher": NAMES[algo], "n": n, "gpu_s": round(gpu_s, 4), "gpu_proofs_per_s": round(n / gpu_s, 1),
+            "cpu_threads": THREADS, "cpu_sample": m, "cpu_proofs_per_s": round(m / cpu_s, 1), "speedup": round((n / gpu_s) / (m / cpu_s), 1),
+            "verdicts_ok": ok, "device": os.environ.get("GSC_DEVICE", "0")}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sizes", default="1024,8192,65536")
+    ap.add_argument("--aes", type=int, default=8192, help="AES-128 batch (0: skip)")
+    ap.add_argument("--cpu-sample", type=int, default=2048)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    g = gsc_loader.load()
+    lines = []
+    assert g.init_algorithm(0, golden_bytes("pk.chacha20"), golden_bytes("r1cs.chacha20"))
+    vk = golden_bytes("vk.chacha20")
+    assert g.verify_init(0, vk) and g.init_verifier(0, vk)
+    for n in [int(x) for x in a.sizes.split(",") if x]:
+        lines.append(run(g, 0, n, a.cpu_sample, n)); print(json.dumps(lines[-1]), flush=True)
+    if a.aes:
+        cache = os.path.join(ROOT, "build", "keys")
+        pkp, vkp = os.path.join(cache, "pk.aes128"), os.path.join(cache, "vk.aes128")
+        r1cs = golden_bytes("r1cs.aes128")
+        if not (os.path.exists(pkp) and os.path.exists(vkp)):       # the test suite's AES-128 test keys (same seed, same cache)
+            from oracle import oracle as O
+            os.makedirs(cache, exist_ok=True)
+            pk, vkb = O.setup(O.R1CS(r1cs), bytes([1] * 32))
+            open(pkp, "wb").write(pk); open(vkp, "wb").write(vkb)
+        pk, vkb = open(pkp, "rb").read(), open(vkp, "rb").read()
+        assert g.init_algorithm(1, pk, r1cs) and g.verify_init(1, vkb) and g.init_verifier(1, vkb)
+        lines.append(run(g, 1, a.aes, min(a.cpu_sample, 1024), 7)); print(json.dumps(lines[-1]), flush=True)
+    if a.out:
+        with open(a.out, "w") as f:
+            for l in lines:
+                f.write(json.dumps(l) + "\n")
+    return 0 if all(l["verdicts_ok"] for l in lines) else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())
