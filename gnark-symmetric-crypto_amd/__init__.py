@@ -21,7 +21,8 @@ ALGORITHM_NAMES = {0: "chacha20", 1: "aes-128-ctr", 2: "aes-256-ctr"}   # prove_
 
 EXPORTS = ["enforce_binding", "InitAlgorithm", "Free", "Prove", "ProveBatch", "gsc_prove_raw", "gsc_setup",
            "gsc_set_deterministic_randomness", "gsc_debug_prove", "gsc_debug_vector", "gsc_describe", "gsc_last_stage_ms", "gsc_last_dominant_kernel", "gsc_last_kernel_clock", "gsc_debug_field_ops", "gsc_debug_compute_h", "gsc_debug_compute_d", "gsc_debug_secret_residue", "gsc_debug_clock_trace", "gsc_debug_glv_split",
-           "gsc_verify_init", "gsc_verify_raw", "VerifyBatch", "gsc_debug_pairing"]
+           "gsc_verify_init", "gsc_verify_raw", "VerifyBatch", "gsc_debug_pairing",
+           "gsc_verify_raw_batched", "gsc_verify_all", "VerifyAll", "gsc_debug_verify_randomizers"]
 
 
 class GoSlice(C.Structure):
@@ -81,6 +82,14 @@ def lib():
         L.VerifyBatch.argtypes = [GoSlice]
         L.gsc_debug_pairing.restype = C.c_longlong
         L.gsc_debug_pairing.argtypes = [C.c_char_p, C.c_char_p, C.c_size_t, C.c_void_p]
+        L.gsc_verify_raw_batched.restype = C.c_longlong
+        L.gsc_verify_raw_batched.argtypes = [C.c_ubyte, C.c_char_p, C.c_void_p, C.c_char_p, C.c_size_t, C.c_void_p]
+        L.gsc_verify_all.restype = C.c_int
+        L.gsc_verify_all.argtypes = [C.c_ubyte, C.c_char_p, C.c_void_p, C.c_char_p, C.c_size_t]
+        L.VerifyAll.restype = C.c_ubyte
+        L.VerifyAll.argtypes = [GoSlice]
+        L.gsc_debug_verify_randomizers.restype = C.c_int
+        L.gsc_debug_verify_randomizers.argtypes = [C.c_char_p, C.c_int]
         L.enforce_binding()
         _lib = L
     return _lib
@@ -339,6 +348,45 @@ def verify_batch_bytes(params_json: bytes) -> bytes:
     """VerifyBatch on already encoded JSON; returns the raw JSON bytes."""
     s, keep = _slice(params_json)
     return _take(lib().VerifyBatch(s))
+
+
+def verify_raw_batched(algorithm_id: int, proofs: bytes, lens, signals: bytes, n: int = None):
+    """gsc_verify_raw_batched: verify_raw's arguments and verdicts, one final exponentiation per chunk when every proof holds.
+    Raises RuntimeError when no key is loaded (-1) or on a device error (-2)."""
+    n = len(lens) if n is None else n
+    assert len(proofs) >= 196 * n and len(signals) >= 144 * n
+    lens_arr = (C.c_uint32 * max(n, 1))(*lens[:n])
+    out = C.create_string_buffer(max(n, 1))
+    rc = lib().gsc_verify_raw_batched(algorithm_id, bytes(proofs), lens_arr, bytes(signals), n, out)
+    if rc < 0:
+        raise RuntimeError("gsc_verify_raw_batched failed (%d): %s" % (rc, "no key loaded" if rc == -1 else "device error"))
+    return list(out.raw[:n])
+
+
+def verify_all(algorithm_id: int, proofs: bytes, lens, signals: bytes, n: int = None) -> int:
+    """gsc_verify_all: 1 iff every item verifies, 0 otherwise, -1 no key loaded, -2 device error."""
+    n = len(lens) if n is None else n
+    assert len(proofs) >= 196 * n and len(signals) >= 144 * n
+    lens_arr = (C.c_uint32 * max(n, 1))(*lens[:n])
+    return lib().gsc_verify_all(algorithm_id, bytes(proofs), lens_arr, bytes(signals), n)
+
+
+def verify_all_json(items) -> bool:
+    """VerifyAll: a list of Verify inputs (dicts; bytes values become arrays), or already encoded JSON bytes / str -> bool."""
+    if isinstance(items, str):
+        items = items.encode()
+    if not isinstance(items, (bytes, bytearray)):
+        items = json.dumps([{k: (list(v) if isinstance(v, (bytes, bytearray)) else v) for k, v in it.items()} if isinstance(it, dict) else it
+                            for it in items]).encode()
+    s, keep = _slice(bytes(items))
+    return bool(lib().VerifyAll(s))
+
+
+def debug_verify_randomizers(seed: bytes = None, all_ones: bool = False) -> int:
+    """TEST HOOK: randomizers of the batched check from a 32-byte seed, or all 1 (the naive sum); no arguments: the OS CSPRNG.
+    Returns 0, -1 when test hooks are disabled."""
+    assert seed is None or len(seed) == 32
+    return lib().gsc_debug_verify_randomizers(None if seed is None else bytes(seed), 1 if all_ones else 0)
 
 
 def debug_pairing(g1_points, g2_points):

@@ -299,6 +299,7 @@ std::string prove_one_json(const char* data, size_t len, DebugVectors* dbg) {
 }  // namespace
 
 long long gsc_verify_debug_pairing_impl(const uint8_t* g1, const uint8_t* g2, size_t n, uint8_t* out);      // verify_gpu.cpp
+int gsc_verify_debug_randomizers_impl(const uint8_t* seed32, int all_ones);                           // verify_gpu.cpp
 
 extern "C" {
 
@@ -458,6 +459,10 @@ int gsc_debug_clock_trace(uint32_t n, uint32_t interval_us, unsigned long long* 
 long long gsc_debug_pairing(const uint8_t* g1, const uint8_t* g2, size_t n, uint8_t* out) {
     if (hooks_refused("gsc_debug_pairing") || (n && (!g1 || !g2 || !out))) return -1;
     return gsc_verify_debug_pairing_impl(g1, g2, n, out);
+}
+int gsc_debug_verify_randomizers(const uint8_t* seed32, int all_ones) {
+    if (hooks_refused("gsc_debug_verify_randomizers")) return -1;
+    return gsc_verify_debug_randomizers_impl(seed32, all_ones);
 }
 int gsc_debug_glv_split(const uint8_t* k, uint8_t* out) {
     if (hooks_refused("gsc_debug_glv_split") || !k || !out) return -1;

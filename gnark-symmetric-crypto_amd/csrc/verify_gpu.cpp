@@ -1,11 +1,15 @@
-// GPU verifier in libprove.so: gsc_verify_init, gsc_verify_raw, VerifyBatch, gsc_debug_pairing (include/libprove.h).
+// GPU verifier in libprove.so: gsc_verify_init, gsc_verify_raw, VerifyBatch, gsc_debug_pairing, and the batched check
+// gsc_verify_raw_batched, gsc_verify_all, VerifyAll (include/libprove.h).
 // Verdicts are those of libverify.so's Verify (verifier.cpp); the host only checks sizes and packs bytes (verify_common),
-// decoding and every curve operation run in k_verify.hip.  Each key owns a non-blocking stream and chunk buffers on one device
+// decoding and every curve operation run in k_verify.hip (k_verify_batch.hip for the batched check).  Each key owns a non-blocking stream and chunk buffers on one device
 // (GSC_DEVICE, or the first of GSC_DEVICES); calls on the same key are serialised, and nothing here synchronises the device.
 #include "../../include/libprove.h"
 #include "json.hpp"
 #include "verify_common.hpp"
+#include "host_ciphers.hpp"
+#include "verify_batch_kernels.hpp"
 #include "verify_kernels.hpp"
+#include <cerrno>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -16,6 +20,7 @@
 #include <stdexcept>
 #include <string>
 #include <vector>
+#include <sys/random.h>
 
 namespace {
 
@@ -50,6 +55,13 @@ struct GpuKey {
     std::mutex mu;                       // one call at a time on the chunk buffers below
     DevBuf<uint8_t> proofs, win, pre, verdict;
     DevBuf<ProofDev> pd;
+    DevBuf<uint32_t> rnd;                // batched check (k_verify_batch.hip): randomizers and the buffers of BatchBufs
+    DevBuf<VP1> ra, fixed;
+    DevBuf<uint8_t> bok, bflag;
+    DevBuf<G1X> part;
+    DevBuf<uint64_t> rpart;
+    DevBuf<F12> f;
+    BatchBufs bufs() const { return BatchBufs{ra.p, bok.p, part.p, rpart.p, fixed.p, f.p, bflag.p}; }
     ~GpuKey() { if (stream) { (void)hipStreamSynchronize(stream); (void)hipStreamDestroy(stream); } }
 };
 
@@ -114,6 +126,9 @@ std::shared_ptr<GpuKey> build_key(int algo, const uint8_t* b, size_t n) {
     }
     ck(hipStreamSynchronize(s), "key lines");
     k->proofs.alloc(kChunk * kProofSlot); k->win.alloc(kChunk * V::kWindows); k->pre.alloc(kChunk); k->verdict.alloc(kChunk); k->pd.alloc(kChunk);
+    const size_t nblk = batch_blocks(kChunk);
+    k->rnd.alloc(kChunk * kRandWords); k->ra.alloc(kChunk); k->fixed.alloc(kBatchFixed); k->bok.alloc(kChunk); k->bflag.alloc(1);
+    k->part.alloc(nblk * kBatchSums); k->rpart.alloc(nblk * 4); k->f.alloc(kChunk + kBatchFixed);
     return k;
 }
 
@@ -129,6 +144,26 @@ void load_dir_once() {      // like libverify: keys from GSC_VK_DIR on first use
 }
 std::shared_ptr<GpuKey> key_for(int algo) { std::lock_guard<std::mutex> l(g_mu); load_dir_once(); return g_keys[algo]; }
 
+// items [off, off + m): the host pre-check and the public-input windows, uploaded, then k_verify_prep into k.pd (k.mu held).
+// Returns how many items passed the host pre-check.
+size_t prep_chunk(GpuKey& k, const uint8_t* proofs, const uint32_t* lens, const uint8_t* signals, size_t off, size_t m,
+                  std::vector<uint8_t>& win, std::vector<uint8_t>& pre) {
+    size_t passed = 0;
+    for (size_t i = 0; i < m; i++) {
+        const size_t j = off + i;
+        pre[i] = lens[j] <= (uint32_t)kProofSlot && V::proof_shape_ok(proofs + kProofSlot * j, lens[j], k.has_commitment);
+        passed += pre[i];
+        V::public_windows(k.algo, signals + V::kSignalBytes * j, win.data() + V::kWindows * i);
+    }
+    hipStream_t s = k.stream;
+    ck(hipMemcpyAsync(k.proofs.p, proofs + kProofSlot * off, m * kProofSlot, hipMemcpyHostToDevice, s), "copy");
+    ck(hipMemcpyAsync(k.win.p, win.data(), m * V::kWindows, hipMemcpyHostToDevice, s), "copy");
+    ck(hipMemcpyAsync(k.pre.p, pre.data(), m, hipMemcpyHostToDevice, s), "copy");
+    launch_verify_prep(k.kd, k.proofs.p, k.win.p, k.pre.p, k.pd.p, m, s);
+    ck(hipGetLastError(), "k_verify_prep");
+    return passed;
+}
+
 // verdicts for n items; proofs in 196-byte slots.  Returns the number accepted; throws HipError on a device error.
 long long run_verify(GpuKey& k, const uint8_t* proofs, const uint32_t* lens, const uint8_t* signals, size_t n, uint8_t* verdicts) {
     std::lock_guard<std::mutex> l(k.mu);
@@ -138,17 +173,8 @@ long long run_verify(GpuKey& k, const uint8_t* proofs, const uint32_t* lens, con
     for (size_t off = 0; off < n; off += kChunk) {
         const size_t m = std::min(kChunk, n - off);
         if (!k.fits) { memset(verdicts + off, 0, m); continue; }
-        for (size_t i = 0; i < m; i++) {
-            const size_t j = off + i;
-            pre[i] = lens[j] <= (uint32_t)kProofSlot && V::proof_shape_ok(proofs + kProofSlot * j, lens[j], k.has_commitment);
-            V::public_windows(k.algo, signals + V::kSignalBytes * j, win.data() + V::kWindows * i);
-        }
+        prep_chunk(k, proofs, lens, signals, off, m, win, pre);
         hipStream_t s = k.stream;
-        ck(hipMemcpyAsync(k.proofs.p, proofs + kProofSlot * off, m * kProofSlot, hipMemcpyHostToDevice, s), "copy");
-        ck(hipMemcpyAsync(k.win.p, win.data(), m * V::kWindows, hipMemcpyHostToDevice, s), "copy");
-        ck(hipMemcpyAsync(k.pre.p, pre.data(), m, hipMemcpyHostToDevice, s), "copy");
-        launch_verify_prep(k.kd, k.proofs.p, k.win.p, k.pre.p, k.pd.p, m, s);
-        ck(hipGetLastError(), "k_verify_prep");
         launch_verify_pairing(k.kd, k.pd.p, k.verdict.p, nullptr, m, s);
         ck(hipGetLastError(), "k_verify_pairing");
         ck(hipMemcpyAsync(verdicts + off, k.verdict.p, m, hipMemcpyDeviceToHost, s), "copy");
@@ -156,6 +182,112 @@ long long run_verify(GpuKey& k, const uint8_t* proofs, const uint32_t* lens, con
         for (size_t i = 0; i < m; i++) accepted += verdicts[off + i];
     }
     return accepted;
+}
+
+// ---- batched check ----
+// Randomizers: OS CSPRNG bytes, drawn afresh for every chunk of every call.  gsc_debug_verify_randomizers (a test hook) can make
+// them a fixed function of a seed, or all 1 (the naive sum the randomizers exist to defeat).
+enum class RandMode { Csprng, Seeded, Ones };
+std::mutex g_rand_mu;
+RandMode g_rand_mode = RandMode::Csprng;
+uint8_t g_rand_seed[32];
+
+void os_random(uint8_t* out, size_t n) {
+    for (size_t got = 0; got < n;) {
+        const ssize_t r = getrandom(out + got, n - got, 0);
+        if (r > 0) got += (size_t)r;
+        else if (r < 0 && errno != EINTR) throw std::runtime_error(std::string("getrandom failed: ") + strerror(errno));
+    }
+}
+// m x kRandWords words: rho_i, then t_i when `with_t` (else 0); uniform, nonzero 128-bit values
+void draw_randomizers(uint32_t* out, size_t m, bool with_t, uint64_t chunk) {
+    RandMode mode; uint8_t seed[32];
+    { std::lock_guard<std::mutex> l(g_rand_mu); mode = g_rand_mode; memcpy(seed, g_rand_seed, 32); }
+    const int nw = with_t ? 8 : 4;
+    std::vector<uint8_t> bytes(16 * (with_t ? 2 : 1) * m, 0);
+    if (mode == RandMode::Csprng) os_random(bytes.data(), bytes.size());
+    else if (mode == RandMode::Seeded) {
+        uint8_t nonce[12] = {0};
+        for (int b = 0; b < 8; b++) nonce[b] = (uint8_t)(chunk >> (8 * b));
+        chacha20_xor_stream(seed, nonce, 0, bytes.data(), bytes.data(), bytes.size());
+    }
+    for (size_t i = 0; i < m; i++) {
+        uint32_t* r = out + (size_t)kRandWords * i;
+        for (int w = 0; w < kRandWords; w++) r[w] = 0;
+        for (int h = 0; h < nw / 4; h++) {
+            uint32_t* v = r + 4 * h;
+            if (mode == RandMode::Ones) { v[0] = 1; continue; }
+            uint8_t* b = bytes.data() + 16 * ((nw / 4) * i + h);
+            for (;;) {
+                uint32_t any = 0;
+                for (int w = 0; w < 4; w++) { memcpy(&v[w], b + 4 * w, 4); any |= v[w]; }
+                if (any) break;
+                if (mode == RandMode::Seeded) { v[0] = 1; break; }
+                os_random(b, 16);
+            }
+        }
+    }
+}
+
+// the batched check over n items.  all == false: verdicts as run_verify's, returns the number accepted.  all == true (verdicts
+// unused): returns 1 iff every item is accepted, else 0, stopping at the first failing chunk.  Throws HipError on a device error.
+long long run_verify_batched(GpuKey& k, const uint8_t* proofs, const uint32_t* lens, const uint8_t* signals, size_t n, uint8_t* verdicts, bool all) {
+    std::lock_guard<std::mutex> l(k.mu);
+    ck(hipSetDevice(k.device), "hipSetDevice");
+    long long accepted = 0;
+    std::vector<uint8_t> win(kChunk * V::kWindows), pre(kChunk), okh(all ? kChunk : 0);
+    std::vector<uint32_t> rnd(kChunk * kRandWords);
+    for (size_t off = 0; off < n; off += kChunk) {
+        const size_t m = std::min(kChunk, n - off);
+        if (!k.fits) { if (all) return 0; memset(verdicts + off, 0, m); continue; }
+        const size_t passed = prep_chunk(k, proofs, lens, signals, off, m, win, pre);
+        if (all && passed < m) { ck(hipStreamSynchronize(k.stream), "verify"); return 0; }
+        draw_randomizers(rnd.data(), m, k.has_commitment, off / kChunk);      // on the host while k_verify_prep runs
+        hipStream_t s = k.stream;
+        ck(hipMemcpyAsync(k.rnd.p, rnd.data(), m * kRandWords * sizeof(uint32_t), hipMemcpyHostToDevice, s), "copy");
+        launch_verify_batch(k.kd, k.pd.p, k.rnd.p, m, k.bufs(), s);
+        ck(hipGetLastError(), "k_verify_batch");
+        uint8_t* okv = all ? okh.data() : verdicts + off;
+        uint8_t flag = 0;
+        ck(hipMemcpyAsync(okv, k.bok.p, m, hipMemcpyDeviceToHost, s), "copy");
+        ck(hipMemcpyAsync(&flag, k.bflag.p, 1, hipMemcpyDeviceToHost, s), "copy");
+        ck(hipStreamSynchronize(s), "verify batch");
+        size_t nok = 0;
+        for (size_t i = 0; i < m; i++) nok += okv[i];
+        if (all) { if (!flag || nok < m) return 0; continue; }
+        if (!flag) {      // some proof with ok fails: the per-proof pairings of the same ProofDev decide, as in run_verify
+            launch_verify_pairing(k.kd, k.pd.p, k.verdict.p, nullptr, m, s);
+            ck(hipGetLastError(), "k_verify_pairing");
+            ck(hipMemcpyAsync(verdicts + off, k.verdict.p, m, hipMemcpyDeviceToHost, s), "copy");
+            ck(hipStreamSynchronize(s), "verify");
+            nok = 0;
+            for (size_t i = 0; i < m; i++) nok += verdicts[off + i];
+        }
+        accepted += (long long)nok;
+    }
+    return all ? 1 : accepted;
+}
+
+// VerifyBatch / VerifyAll: the well-formed items of a JSON array grouped by algorithm, as gsc_verify_raw's arguments
+struct Grouped {
+    std::vector<size_t> where[3];
+    std::vector<uint8_t> slots[3], sigs[3];
+    std::vector<uint32_t> lens[3];
+    size_t bad = 0;           // items that do not parse as a Verify request
+};
+Grouped group_requests(const JsonValue& root) {
+    Grouped g;
+    for (size_t i = 0; i < root.items.size(); i++) {
+        int algo; std::vector<uint8_t> proof, sig;
+        if (!V::parse_request(root.items[i], algo, proof, sig) || algo < 0 || sig.size() != V::kSignalBytes) { g.bad++; continue; }
+        g.where[algo].push_back(i);
+        std::vector<uint8_t> slot(kProofSlot, 0);
+        memcpy(slot.data(), proof.data(), std::min(proof.size(), (size_t)kProofSlot));
+        g.slots[algo].insert(g.slots[algo].end(), slot.begin(), slot.end());
+        g.sigs[algo].insert(g.sigs[algo].end(), sig.begin(), sig.end());
+        g.lens[algo].push_back(proof.size() > kProofSlot ? UINT32_MAX : (uint32_t)proof.size());
+    }
+    return g;
 }
 
 struct Prove_return to_c(const std::string& s) {
@@ -198,25 +330,14 @@ struct Prove_return VerifyBatch(GoSlice params) {
         if (root.kind != JsonValue::Array) return to_c(json_quote("VerifyBatch expects a JSON array"));
         const size_t n = root.items.size();
         std::vector<uint8_t> verdict(n, 0);
-        // group the well-formed items by algorithm: one gsc_verify_raw pass each, verdicts put back in place
-        std::vector<size_t> where[3];
-        std::vector<uint8_t> slots[3], sigs[3]; std::vector<uint32_t> lens[3];
-        for (size_t i = 0; i < n; i++) {
-            int algo; std::vector<uint8_t> proof, sig;
-            if (!V::parse_request(root.items[i], algo, proof, sig) || algo < 0 || sig.size() != V::kSignalBytes) continue;
-            where[algo].push_back(i);
-            std::vector<uint8_t> slot(kProofSlot, 0);
-            memcpy(slot.data(), proof.data(), std::min(proof.size(), (size_t)kProofSlot));
-            slots[algo].insert(slots[algo].end(), slot.begin(), slot.end());
-            sigs[algo].insert(sigs[algo].end(), sig.begin(), sig.end());
-            lens[algo].push_back(proof.size() > kProofSlot ? UINT32_MAX : (uint32_t)proof.size());
-        }
+        // the well-formed items grouped by algorithm: one gsc_verify_raw pass each, verdicts put back in place
+        Grouped g = group_requests(root);
         for (int a = 0; a < 3; a++) {
-            const size_t m = where[a].size();
+            const size_t m = g.where[a].size();
             if (!m) continue;
             std::vector<uint8_t> v(m);
-            if (gsc_verify_raw((GoUint8)a, slots[a].data(), lens[a].data(), sigs[a].data(), m, v.data()) < 0) continue;   // no key: false
-            for (size_t i = 0; i < m; i++) verdict[where[a][i]] = v[i];
+            if (gsc_verify_raw((GoUint8)a, g.slots[a].data(), g.lens[a].data(), g.sigs[a].data(), m, v.data()) < 0) continue;   // no key: false
+            for (size_t i = 0; i < m; i++) verdict[g.where[a][i]] = v[i];
         }
         out = "[";
         for (size_t i = 0; i < n; i++) { if (i) out += ","; out += verdict[i] ? "true" : "false"; }
@@ -225,7 +346,49 @@ struct Prove_return VerifyBatch(GoSlice params) {
     return to_c(out);
 }
 
+long long gsc_verify_raw_batched(GoUint8 algorithmID, const uint8_t* proofs, const uint32_t* proof_lens, const uint8_t* signals, size_t n,
+                                 uint8_t* verdicts) {
+    if (n) memset(verdicts, 0, n);
+    if (algorithmID > 2) return -1;
+    auto k = key_for(algorithmID);
+    if (!k) return -1;
+    if (!n) return 0;
+    try { return run_verify_batched(*k, proofs, proof_lens, signals, n, verdicts, false); }
+    catch (const std::exception& e) { printf("gsc_verify_raw_batched: %s\n", e.what()); memset(verdicts, 0, n); return -2; }
+}
+
+int gsc_verify_all(GoUint8 algorithmID, const uint8_t* proofs, const uint32_t* proof_lens, const uint8_t* signals, size_t n) {
+    if (algorithmID > 2) return -1;
+    auto k = key_for(algorithmID);
+    if (!k) return -1;
+    try { return (int)run_verify_batched(*k, proofs, proof_lens, signals, n, nullptr, true); }
+    catch (const std::exception& e) { printf("gsc_verify_all: %s\n", e.what()); return -2; }
+}
+
+GoUint8 VerifyAll(GoSlice params) {
+    try {
+        const JsonValue root = json_parse((const char*)params.data, params.len > 0 ? (size_t)params.len : 0);
+        if (root.kind != JsonValue::Array || root.items.empty()) return 0;
+        Grouped g = group_requests(root);
+        if (g.bad) return 0;
+        for (int a = 0; a < 3; a++) {
+            const size_t m = g.where[a].size();
+            if (m && gsc_verify_all((GoUint8)a, g.slots[a].data(), g.lens[a].data(), g.sigs[a].data(), m) != 1) return 0;
+        }
+        return 1;
+    } catch (const std::exception&) { return 0; }
+}
+
 }  // extern "C"
+
+// gsc_debug_verify_randomizers' body (capi.cpp gates the hook): NULL seed and !all_ones: the OS CSPRNG again
+int gsc_verify_debug_randomizers_impl(const uint8_t* seed32, int all_ones) {
+    std::lock_guard<std::mutex> l(g_rand_mu);
+    if (all_ones) g_rand_mode = RandMode::Ones;
+    else if (seed32) { g_rand_mode = RandMode::Seeded; memcpy(g_rand_seed, seed32, 32); }
+    else g_rand_mode = RandMode::Csprng;
+    return 0;
+}
 
 // gsc_debug_pairing's body: capi.cpp exports the hook behind its GSC_ENABLE_TEST_HOOKS gate and calls this
 long long gsc_verify_debug_pairing_impl(const uint8_t* g1, const uint8_t* g2, size_t n, uint8_t* out) {

@@ -141,6 +141,24 @@ extern struct Prove_return VerifyBatch(GoSlice params);
  * 2i + j = component j (of 1, u) of the w^i coefficient in Fp12 = Fp2[w]/(w^6 - (9+u)), Fp2 = Fp[u]/(u^2+1).  Returns n, -1 when hooks
  * are off or on error. */
 extern long long gsc_debug_pairing(const uint8_t *g1_uncompressed, const uint8_t *g2_uncompressed, size_t n, uint8_t *out);
+/* Batched check (k_verify_batch.hip): per chunk of 65 536 items, with fresh random nonzero 128-bit rho_i (and t_i for the AES
+ * keys' proof of knowledge) from the OS CSPRNG, one final exponentiation decides
+ *   prod_i e(rho_i A_i, B_i) e(-(sum rho_i) alpha, beta) e(-sum rho_i L_i, gamma) e(-sum rho_i C_i, delta)
+ *   (* e(sum t_i D_i, ped_gsn) e(sum t_i PoK_i, ped_g)) == 1.
+ * Same arguments, return values and verdicts as gsc_verify_raw.  A chunk whose check fails is verified again proof by proof, so the
+ * verdicts are gsc_verify_raw's; when it holds, every item that decodes is accepted (wrong with probability about 2^-128). */
+extern long long gsc_verify_raw_batched(GoUint8 algorithmID, const uint8_t *proofs, const uint32_t *proof_lens, const uint8_t *signals,
+                                        size_t n, uint8_t *verdicts);
+/* The same check as a yes / no answer for a whole set: 1 iff Verify would accept every item (n = 0: 1), 0 otherwise (no
+ * proof-by-proof pass: it stops at the first failing chunk), -1 if no key is loaded for the algorithm, -2 on a device error. */
+extern int gsc_verify_all(GoUint8 algorithmID, const uint8_t *proofs, const uint32_t *proof_lens, const uint8_t *signals, size_t n);
+/* JSON array of Verify inputs (VerifyBatch's; ciphers may be mixed, each cipher checked with gsc_verify_all) -> 1 iff Verify would
+ * accept every element.  Malformed JSON, a non-array, an empty array, an element that does not parse or a cipher without a key: 0. */
+extern GoUint8 VerifyAll(GoSlice params);
+/* TEST HOOK: the randomizers of the batched check.  seed32 (32 bytes): a fixed function of the seed from now on; all_ones != 0:
+ * every rho_i = t_i = 1 (the naive sum, which swapped public inputs of two proofs pass; it takes precedence over a seed); NULL
+ * seed and all_ones == 0: the OS CSPRNG again (the default).  Returns 0, -1 when hooks are off. */
+extern int gsc_debug_verify_randomizers(const uint8_t *seed32, int all_ones);
 
 #ifdef __cplusplus
 }

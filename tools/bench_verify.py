@@ -5,6 +5,10 @@ verdict is checked (all proofs valid must be accepted; the same proofs with the 
 the CPU rate is measured on a sample of the same proofs with the same check.
 
     python tools/bench_verify.py [--sizes 1024,8192,65536] [--aes 8192] [--cpu-sample 2048] [--out FILE]
+
+--batched times gsc_verify_raw_batched (one final exponentiation per chunk) against gsc_verify_raw on the same all-valid proofs
+instead, each the median of --repeat calls, and checks that the verdicts are equal.  One more ChaCha20 line at the largest size has a
+single bad proof (signals of another statement): the price of the proof-by-proof pass that follows a failing chunk.
 """
 import argparse
 import json
@@ -68,20 +72,53 @@ def run(g, algo, n, cpu_sample, seed):
             "verdicts_ok": ok, "device": os.environ.get("GSC_DEVICE", "0")}
 
 
+def _median_call(fn, repeat):
+    times, out = [], None
+    for _ in range(repeat):
+        t0 = time.perf_counter()
+        out = fn()
+        times.append(time.perf_counter() - t0)
+    return sorted(times)[len(times) // 2], out
+
+
+def run_batched(g, algo, n, seed, repeat, bad=None):
+    proofs, lens, sig = make_items(g, algo, n, seed)
+    if bad is not None:                               # item `bad` gets the signals of the next statement
+        sig = sig[:144 * bad] + sig[144 * (bad + 1):144 * (bad + 2)] + sig[144 * (bad + 1):]
+    g.verify_raw(algo, proofs[:196 * 64], lens[:64], sig[:144 * 64])          # warm-up (kernel load)
+    g.verify_raw_batched(algo, proofs[:196 * 64], lens[:64], sig[:144 * 64])
+    plain_s, want = _median_call(lambda: g.verify_raw(algo, proofs, lens, sig), repeat)
+    batched_s, got = _median_call(lambda: g.verify_raw_batched(algo, proofs, lens, sig), repeat)
+    expect = [1] * n
+    if bad is not None:
+        expect[bad] = 0
+    ok = got == want == expect and g.verify_all(algo, proofs, lens, sig) == (1 if bad is None else 0)
+    return {"tool": "bench_verify", "mode": "batched", "cipher": NAMES[algo], "n": n, "bad": 0 if bad is None else 1,
+            "plain_s": round(plain_s, 4), "plain_proofs_per_s": round(n / plain_s, 1), "batched_s": round(batched_s, 4),
+            "batched_proofs_per_s": round(n / batched_s, 1), "speedup": round(plain_s / batched_s, 2), "repeat": repeat,
+            "verdicts_ok": ok, "device": os.environ.get("GSC_DEVICE", "0")}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="1024,8192,65536")
     ap.add_argument("--aes", type=int, default=8192, help="AES-128 batch (0: skip)")
     ap.add_argument("--cpu-sample", type=int, default=2048)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--batched", action="store_true", help="gsc_verify_raw_batched against gsc_verify_raw")
+    ap.add_argument("--repeat", type=int, default=3, help="--batched: calls per timing (median)")
     a = ap.parse_args()
     g = gsc_loader.load()
     lines = []
     assert g.init_algorithm(0, golden_bytes("pk.chacha20"), golden_bytes("r1cs.chacha20"))
     vk = golden_bytes("vk.chacha20")
     assert g.verify_init(0, vk) and g.init_verifier(0, vk)
-    for n in [int(x) for x in a.sizes.split(",") if x]:
-        lines.append(run(g, 0, n, a.cpu_sample, n)); print(json.dumps(lines[-1]), flush=True)
+    sizes = [int(x) for x in a.sizes.split(",") if x]
+    for n in sizes:
+        lines.append(run_batched(g, 0, n, n, a.repeat) if a.batched else run(g, 0, n, a.cpu_sample, n)); print(json.dumps(lines[-1]), flush=True)
+    if a.batched and sizes:
+        n = max(sizes)
+        lines.append(run_batched(g, 0, n, n, a.repeat, bad=n // 2)); print(json.dumps(lines[-1]), flush=True)
     if a.aes:
         cache = os.path.join(ROOT, "build", "keys")
         pkp, vkp = os.path.join(cache, "pk.aes128"), os.path.join(cache, "vk.aes128")
@@ -93,7 +130,7 @@ def main():
             open(pkp, "wb").write(pk); open(vkp, "wb").write(vkb)
         pk, vkb = open(pkp, "rb").read(), open(vkp, "rb").read()
         assert g.init_algorithm(1, pk, r1cs) and g.verify_init(1, vkb) and g.init_verifier(1, vkb)
-        lines.append(run(g, 1, a.aes, min(a.cpu_sample, 1024), 7)); print(json.dumps(lines[-1]), flush=True)
+        lines.append(run_batched(g, 1, a.aes, 7, a.repeat) if a.batched else run(g, 1, a.aes, min(a.cpu_sample, 1024), 7)); print(json.dumps(lines[-1]), flush=True)
     if a.out:
         with open(a.out, "w") as f:
             for l in lines:
