@@ -321,10 +321,110 @@ struct Fp2x {
     DEVFN static void store(fe* p, const E& a) { Fp29::store(p, a.a0); Fp29::store(p + 1, a.a1); }
     static constexpr int WORDS = 2;     // field elements per coordinate in memory
 };
-// helpers so that the curve template can treat both fields alike
+// ---- Montgomery products with the carry folded into the multiply-add chain (device code) ----
+// Field29::mul writes every column as acc += x_i y_i; the compiler reassociates that into a separate column sum that starts at 0 and
+// merges it with the carry by a 64-bit add (v_lshl_add_u64): 16 extra 64-bit instructions per product.  Here every multiply-add is
+// written in inline assembly with the running accumulator as its addend, so the column continues from acc >> 29 of the previous one and
+// the merges are gone.  The terms are the same, only added in another order, and no partial sum leaves (-2^63, 2^63): the limbs, and
+// everything computed from them, are bit-identical to Field29's.  hipcc pads one wait state after each asm statement whose output is read
+// next, so the terms go four to a statement.  vcc takes the (unused) carry-out of each multiply-add.
+namespace madc {
+#if defined(__HIP_DEVICE_COMPILE__)
+DEVFN void s1(int64_t& c, int32_t a0, int32_t b0) { asm("v_mad_i64_i32 %0, vcc, %1, %2, %0" : "+v"(c) : "v"(a0), "v"(b0) : "vcc"); }
+DEVFN void s2(int64_t& c, int32_t a0, int32_t b0, int32_t a1, int32_t b1) {
+    asm("v_mad_i64_i32 %0, vcc, %1, %2, %0\n\tv_mad_i64_i32 %0, vcc, %3, %4, %0" : "+v"(c) : "v"(a0), "v"(b0), "v"(a1), "v"(b1) : "vcc");
+}
+DEVFN void s3(int64_t& c, int32_t a0, int32_t b0, int32_t a1, int32_t b1, int32_t a2, int32_t b2) {
+    asm("v_mad_i64_i32 %0, vcc, %1, %2, %0\n\tv_mad_i64_i32 %0, vcc, %3, %4, %0\n\tv_mad_i64_i32 %0, vcc, %5, %6, %0"
+        : "+v"(c) : "v"(a0), "v"(b0), "v"(a1), "v"(b1), "v"(a2), "v"(b2) : "vcc");
+}
+DEVFN void s4(int64_t& c, int32_t a0, int32_t b0, int32_t a1, int32_t b1, int32_t a2, int32_t b2, int32_t a3, int32_t b3) {
+    asm("v_mad_i64_i32 %0, vcc, %1, %2, %0\n\tv_mad_i64_i32 %0, vcc, %3, %4, %0\n\tv_mad_i64_i32 %0, vcc, %5, %6, %0\n\tv_mad_i64_i32 %0, vcc, %7, %8, %0"
+        : "+v"(c) : "v"(a0), "v"(b0), "v"(a1), "v"(b1), "v"(a2), "v"(b2), "v"(a3), "v"(b3) : "vcc");
+}
+// m_i * P_j: m in [0, 2^29), P a constant below 2^29 held in an SGPR
+DEVFN void u1(int64_t& c, int32_t a0, int32_t b0) { asm("v_mad_u64_u32 %0, vcc, %1, %2, %0" : "+v"(c) : "v"(a0), "s"(b0) : "vcc"); }
+DEVFN void u2(int64_t& c, int32_t a0, int32_t b0, int32_t a1, int32_t b1) {
+    asm("v_mad_u64_u32 %0, vcc, %1, %2, %0\n\tv_mad_u64_u32 %0, vcc, %3, %4, %0" : "+v"(c) : "v"(a0), "s"(b0), "v"(a1), "s"(b1) : "vcc");
+}
+DEVFN void u3(int64_t& c, int32_t a0, int32_t b0, int32_t a1, int32_t b1, int32_t a2, int32_t b2) {
+    asm("v_mad_u64_u32 %0, vcc, %1, %2, %0\n\tv_mad_u64_u32 %0, vcc, %3, %4, %0\n\tv_mad_u64_u32 %0, vcc, %5, %6, %0"
+        : "+v"(c) : "v"(a0), "s"(b0), "v"(a1), "s"(b1), "v"(a2), "s"(b2) : "vcc");
+}
+DEVFN void u4(int64_t& c, int32_t a0, int32_t b0, int32_t a1, int32_t b1, int32_t a2, int32_t b2, int32_t a3, int32_t b3) {
+    asm("v_mad_u64_u32 %0, vcc, %1, %2, %0\n\tv_mad_u64_u32 %0, vcc, %3, %4, %0\n\tv_mad_u64_u32 %0, vcc, %5, %6, %0\n\tv_mad_u64_u32 %0, vcc, %7, %8, %0"
+        : "+v"(c) : "v"(a0), "s"(b0), "v"(a1), "s"(b1), "v"(a2), "s"(b2), "v"(a3), "s"(b3) : "vcc");
+}
+#else       // host builds of the headers (tests): the same sums in plain C
+DEVFN void s1(int64_t& c, int32_t a0, int32_t b0) { c += (int64_t)a0 * b0; }
+DEVFN void s2(int64_t& c, int32_t a0, int32_t b0, int32_t a1, int32_t b1) { s1(c, a0, b0); s1(c, a1, b1); }
+DEVFN void s3(int64_t& c, int32_t a0, int32_t b0, int32_t a1, int32_t b1, int32_t a2, int32_t b2) { s2(c, a0, b0, a1, b1); s1(c, a2, b2); }
+DEVFN void s4(int64_t& c, int32_t a0, int32_t b0, int32_t a1, int32_t b1, int32_t a2, int32_t b2, int32_t a3, int32_t b3) { s2(c, a0, b0, a1, b1); s2(c, a2, b2, a3, b3); }
+DEVFN void u1(int64_t& c, int32_t a0, int32_t b0) { c += (int64_t)((uint64_t)(uint32_t)a0 * (uint32_t)b0); }
+DEVFN void u2(int64_t& c, int32_t a0, int32_t b0, int32_t a1, int32_t b1) { u1(c, a0, b0); u1(c, a1, b1); }
+DEVFN void u3(int64_t& c, int32_t a0, int32_t b0, int32_t a1, int32_t b1, int32_t a2, int32_t b2) { u2(c, a0, b0, a1, b1); u1(c, a2, b2); }
+DEVFN void u4(int64_t& c, int32_t a0, int32_t b0, int32_t a1, int32_t b1, int32_t a2, int32_t b2, int32_t a3, int32_t b3) { u2(c, a0, b0, a1, b1); u2(c, a2, b2, a3, b3); }
+#endif
+// c += sum a.l[i] * b.l[k - i] over i0 <= i < i1 (signed), four terms per statement; i0, i1, k constant after unrolling
+DEVFN void col(int64_t& c, const fe9& a, const fe9& b, int k, int i0, int i1) {
+#pragma unroll
+    for (int i = i0; i < i1; i += 4) {
+        const int n = i1 - i;
+        if (n >= 4) s4(c, a.l[i], b.l[k - i], a.l[i + 1], b.l[k - i - 1], a.l[i + 2], b.l[k - i - 2], a.l[i + 3], b.l[k - i - 3]);
+        else if (n == 3) s3(c, a.l[i], b.l[k - i], a.l[i + 1], b.l[k - i - 1], a.l[i + 2], b.l[k - i - 2]);
+        else if (n == 2) s2(c, a.l[i], b.l[k - i], a.l[i + 1], b.l[k - i - 1]);
+        else s1(c, a.l[i], b.l[k - i]);
+    }
+}
+// the reduction terms of column k: c += sum m[i] * p_(k-i) over i0 <= i < i1 (unsigned, p in SGPRs)
+template <class Q> DEVFN void col_red(int64_t& c, const int32_t* m, int k, int i0, int i1) {
+#pragma unroll
+    for (int i = i0; i < i1; i += 4) {
+        const int n = i1 - i;
+        if (n >= 4) u4(c, m[i], Q::PK(0, k - i), m[i + 1], Q::PK(0, k - i - 1), m[i + 2], Q::PK(0, k - i - 2), m[i + 3], Q::PK(0, k - i - 3));
+        else if (n == 3) u3(c, m[i], Q::PK(0, k - i), m[i + 1], Q::PK(0, k - i - 1), m[i + 2], Q::PK(0, k - i - 2));
+        else if (n == 2) u2(c, m[i], Q::PK(0, k - i), m[i + 1], Q::PK(0, k - i - 1));
+        else u1(c, m[i], Q::PK(0, k - i));
+    }
+}
+// (a * b [+ c * d]) / 2^261 with one reduction (TWO: c, d present); SQR: a^2 with the cross products taken once against 2a
+// (then b must be 2a).  Field29::mul / fmms (with c negated) / sqr's terms, each column continuing from the carry of the one before.
+template <class Q, bool TWO, bool SQR>
+DEVFN fe9 mont(const fe9& a, const fe9& b, const fe9& c, const fe9& d) {
+    constexpr int32_t MASK = (1 << 29) - 1;
+    int32_t m[9]; fe9 r; int64_t acc = 0;
+#pragma unroll
+    for (int k = 0; k < 17; k++) {
+        const int lo = k < 9 ? 0 : k - 8, hi = k < 9 ? k : 8;
+        if (SQR) {
+            col(acc, a, b, k, lo, (k + 1) / 2);                     // a_i * (2a)_(k-i), 2i < k
+            if (k % 2 == 0) s1(acc, a.l[k / 2], a.l[k / 2]);
+        } else {
+            col(acc, a, b, k, lo, hi + 1);
+            if (TWO) col(acc, c, d, k, lo, hi + 1);
+        }
+        col_red<Q>(acc, m, k, lo, k < 9 ? k : 9);
+        if (k < 9) {
+            m[k] = (int32_t)(((uint32_t)acc * Q::NINV) & (uint32_t)MASK);
+            acc += (int64_t)m[k] * Q::PK(0, 0);
+        } else r.l[k - 9] = (int32_t)((uint32_t)acc & (uint32_t)MASK);
+        acc >>= 29;
+    }
+    r.l[8] = (int32_t)acc;
+    return r;
+}
+}  // namespace madc
+
+// helpers so that the curve template can treat both fields alike.  The G1 curve (all MSM kernels) takes its products from the
+// chained forms above in device code; the host build of the same headers keeps Field29's.
 struct Fp29f : Fp29 {
     DEVFN static E load(const fe* p) { return Fp29::load(p); }
     static constexpr int WORDS = 1;
+#if defined(__HIP_DEVICE_COMPILE__)
+    DEVFN static E mul(const E& a, const E& b) { return madc::mont<Fp29Q, false, false>(a, b, a, b); }
+    DEVFN static E sqr(const E& a) { return madc::mont<Fp29Q, false, true>(a, Fp29::dbl(a), a, a); }
+    DEVFN static E fmms(const E& a, const E& b, const E& c, const E& d) { return madc::mont<Fp29Q, true, false>(a, b, Fp29::neg(c), d); }   // c * d enters as (-c) * d
+#endif
 };
 
 // ---- points: affine (finite) and XYZZ with an explicit infinity flag (a lazily reduced ZZ cannot be tested for zero cheaply) ----
