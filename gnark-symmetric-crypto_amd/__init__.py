@@ -20,7 +20,7 @@ CHACHA20, AES_128, AES_256 = 0, 1, 2                       # prove_impl.go:15-19
 ALGORITHM_NAMES = {0: "chacha20", 1: "aes-128-ctr", 2: "aes-256-ctr"}   # prove_impl.go:21-25
 
 EXPORTS = ["enforce_binding", "InitAlgorithm", "Free", "Prove", "ProveBatch", "gsc_prove_raw", "gsc_setup",
-           "gsc_set_deterministic_randomness", "gsc_debug_prove", "gsc_debug_vector", "gsc_describe", "gsc_last_stage_ms", "gsc_last_dominant_kernel", "gsc_last_kernel_clock", "gsc_debug_field_ops", "gsc_debug_compute_h", "gsc_debug_compute_d", "gsc_debug_secret_residue", "gsc_debug_clock_trace", "gsc_debug_glv_split",
+           "gsc_set_deterministic_randomness", "gsc_debug_prove", "gsc_debug_vector", "gsc_describe", "gsc_last_stage_ms", "gsc_last_dominant_kernel", "gsc_last_kernel_clock", "gsc_debug_field_ops", "gsc_debug_limb_ops", "gsc_debug_curve_ops", "gsc_debug_compute_h", "gsc_debug_compute_d", "gsc_debug_secret_residue", "gsc_debug_clock_trace", "gsc_debug_glv_split",
            "gsc_verify_init", "gsc_verify_raw", "VerifyBatch", "gsc_debug_pairing",
            "gsc_verify_raw_batched", "gsc_verify_all", "VerifyAll", "gsc_debug_verify_randomizers"]
 
@@ -74,6 +74,10 @@ def lib():
         L.gsc_last_kernel_clock.argtypes = [C.c_ubyte, C.POINTER(C.c_float), C.POINTER(C.c_int)]
         L.gsc_debug_field_ops.restype = C.c_int
         L.gsc_debug_field_ops.argtypes = [C.c_int, C.c_int, C.c_char_p, C.c_char_p, C.c_void_p, C.c_size_t, C.c_int]
+        L.gsc_debug_limb_ops.restype = C.c_int
+        L.gsc_debug_limb_ops.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+        L.gsc_debug_curve_ops.restype = C.c_int
+        L.gsc_debug_curve_ops.argtypes = [C.c_int, C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]
         L.gsc_verify_init.restype = C.c_int
         L.gsc_verify_init.argtypes = [C.c_ubyte, GoSlice]
         L.gsc_verify_raw.restype = C.c_longlong
@@ -271,6 +275,29 @@ def debug_field_ops(field: int, op: int, a, b, chain=1):
     if rc:
         raise RuntimeError("gsc_debug_field_ops failed")
     return [int.from_bytes(out.raw[32 * i:32 * i + 32], "little") for i in range(n)]
+
+
+def debug_limb_ops(field: int, op: int, a, b=None, c=None, d=None):
+    """TEST HOOK: a (b, c, d): lists of 9-tuples of raw int32 limbs -> list of 9-tuples computed by the device's radix-2^29 code on
+    exactly these limbs.  op: 0 mul, 1 sqr, 2 fmms, 3 norm, 4 freeze, 5 freeze_near."""
+    n = len(a)
+    arrs = [None if v is None else (C.c_int32 * (9 * n))(*[l for e in v for l in e]) for v in (a, b, c, d)]
+    out = (C.c_int32 * (9 * n))()
+    if lib().gsc_debug_limb_ops(field, op, arrs[0], arrs[1], arrs[2], arrs[3], out, n):
+        raise RuntimeError("gsc_debug_limb_ops failed")
+    return [tuple(out[9 * i:9 * i + 9]) for i in range(n)]
+
+
+def debug_curve_ops(group: int, op: int, pts: bytes, inf: bytes, lam: bytes, n: int, k: int):
+    """TEST HOOK: the device's XYZZ group law on packed canonical affine points (layout: include/libprove.h gsc_debug_curve_ops)
+    -> (packed affine results, flag bytes)."""
+    w = 64 if group == 0 else 128
+    assert len(pts) == w * n * k and len(inf) == n * k and len(lam) == w * n
+    out = C.create_string_buffer(w * n)
+    flags = C.create_string_buffer(n)
+    if lib().gsc_debug_curve_ops(group, op, pts, inf, lam, n, k, out, flags):
+        raise RuntimeError("gsc_debug_curve_ops failed")
+    return out.raw, flags.raw
 
 
 def debug_glv_split(k: int):

@@ -96,7 +96,7 @@ struct Field29 {
         for (int i = 0; i < 9; i++) r.l[i] = -a.l[i];
         return r; }
     DEVFN static E dbl(const E& a) { return add(a, a); }
-    // carry propagation: any |limb| < 2^31 -> tight
+    // carry propagation: any |limb| <= 2^31 - 4 -> tight (a carry is in [-4, 3] and must still fit beside the next limb)
     DEVFN static E norm(const E& a) {
         E r; int32_t c = 0;
 #pragma unroll

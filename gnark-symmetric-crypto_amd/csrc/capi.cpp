@@ -450,6 +450,17 @@ int gsc_debug_field_ops(int field, int op, const uint8_t* a, const uint8_t* b, u
     catch (const std::exception& e) { printf("%s\n", e.what()); return -1; }
 }
 
+int gsc_debug_limb_ops(int field, int op, const int32_t* a, const int32_t* b, const int32_t* c, const int32_t* d, int32_t* out, size_t n) {
+    if (hooks_refused("gsc_debug_limb_ops") || !a || !out) return -1;
+    try { debug_limb_ops(config_from_env().device, field, op, a, b, c, d, out, n); return 0; }
+    catch (const std::exception& e) { printf("%s\n", e.what()); return -1; }
+}
+int gsc_debug_curve_ops(int group, int op, const uint8_t* pts, const uint8_t* inf, const uint8_t* lam, size_t n, size_t k, uint8_t* out, uint8_t* flags) {
+    if (hooks_refused("gsc_debug_curve_ops") || !pts || !inf || !lam || !out || !flags) return -1;
+    try { debug_curve_ops(config_from_env().device, group, op, pts, inf, lam, n, k, out, flags); return 0; }
+    catch (const std::exception& e) { printf("%s\n", e.what()); return -1; }
+}
+
 int gsc_debug_clock_trace(uint32_t n, uint32_t interval_us, unsigned long long* out) {
     if (hooks_refused("gsc_debug_clock_trace") || !out || !n) return -1;
     try { debug_clock_trace(config_from_env().device, n, interval_us, out); return 0; }

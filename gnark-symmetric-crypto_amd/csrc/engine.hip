@@ -73,9 +73,51 @@ void debug_field_ops(int device, int field, int op, const uint8_t* a, const uint
     HIP_CHECK(hipSetDevice(device));
     DevBuf<fe> da(n), db(n), dout(n);
     HIP_CHECK(hipMemcpy(da.p, a, 32 * n, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(db.p, b, 32 * n, hipMemcpyHostToDevice));
-    launch_field_ops(field, op, da.p, db.p, dout.p, n, chain, nullptr);
+    if (!launch_field_ops(field, op, da.p, db.p, dout.p, n, chain, nullptr)) throw std::runtime_error("gsc_debug_field_ops: field " + std::to_string(field) + " has no op " + std::to_string(op));
+    HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipDeviceSynchronize());
     HIP_CHECK(hipMemcpy(out, dout.p, 32 * n, hipMemcpyDeviceToHost));
+}
+
+void debug_limb_ops(int device, int field, int op, const int32_t* a, const int32_t* b, const int32_t* c, const int32_t* d, int32_t* out, size_t n) {
+    const int operands = op == 0 ? 2 : op == 2 ? 4 : 1;      // mul: a, b; fmms: a, b, c, d; sqr / norm / freeze / freeze_near: a
+    const int32_t* src[4] = {a, b, c, d};
+    for (int j = 0; j < operands; j++) if (!src[j]) throw std::runtime_error("gsc_debug_limb_ops: operand missing");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) throw std::runtime_error("no HIP device available");
+    HIP_CHECK(hipSetDevice(device));
+    DevBuf<int32_t> din[4], dout(9 * n);
+    for (int j = 0; j < 4; j++) {      // an operand the op does not read is a copy of a
+        din[j].alloc(9 * n);
+        HIP_CHECK(hipMemcpy(din[j].p, j < operands ? src[j] : a, 36 * n, hipMemcpyHostToDevice));
+    }
+    if (!launch_limb_ops(field, op, din[0].p, din[1].p, din[2].p, din[3].p, dout.p, n, nullptr)) throw std::runtime_error("gsc_debug_limb_ops: field " + std::to_string(field) + " has no op " + std::to_string(op));
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipMemcpy(out, dout.p, 36 * n, hipMemcpyDeviceToHost));
+}
+
+void debug_curve_ops(int device, int group, int op, const uint8_t* pts, const uint8_t* inf, const uint8_t* lam, size_t n, size_t k, uint8_t* out, uint8_t* flags) {
+    // dbl, to_aff: one point; add: two; the accumulations: at least two (madd) / one (partial sums)
+    const bool k_ok = op == 0 || op == 4 ? k == 1 : op == 3 ? k == 2 : op == 5 ? k >= 1 : k >= 2;
+    if (group < 0 || group > 1 || op < 0 || op > 5 || !k_ok || k > 4096 || n > (1u << 20)) throw std::runtime_error("gsc_debug_curve_ops: no such group / op / point count");
+    // an AFFINE operand cannot be the point at infinity: every point of madd but the first, every point of the partial sums
+    if (op == 1 || op == 2 || op == 5)
+        for (size_t i = 0; i < n; i++) for (size_t j = op == 5 ? 0 : 1; j < k; j++) if (inf[k * i + j]) throw std::runtime_error("gsc_debug_curve_ops: infinity as an affine operand");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) throw std::runtime_error("no HIP device available");
+    HIP_CHECK(hipSetDevice(device));
+    const size_t w = group == 0 ? 1 : 2;      // 32-byte values per coordinate
+    DevBuf<fe> dpts(2 * w * k * n), dlam(2 * w * n), dout(2 * w * n);
+    DevBuf<uint8_t> dinf(k * n), dflags(n);
+    HIP_CHECK(hipMemcpy(dpts.p, pts, 32 * 2 * w * k * n, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(dlam.p, lam, 32 * 2 * w * n, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(dinf.p, inf, k * n, hipMemcpyHostToDevice));
+    if (!launch_curve_ops(group, op, k, dpts.p, dinf.p, dlam.p, dout.p, dflags.p, n, nullptr)) throw std::runtime_error("gsc_debug_curve_ops: no such group / op");
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipMemcpy(out, dout.p, 32 * 2 * w * n, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(flags, dflags.p, n, hipMemcpyDeviceToHost));
 }
 
 void debug_clock_trace(int device, uint32_t n, uint32_t interval_us, unsigned long long* out) {

@@ -124,8 +124,11 @@ class Algorithm {
 // TEST HOOK: samples the device's shader clock for n x interval_us microseconds beside whatever else runs (a resident one-wave kernel on a
 // stream of its own); out: n pairs {100 MHz clock, shader clock}.  Blocks until the samples are in.
 void debug_clock_trace(int device, uint32_t n, uint32_t interval_us, unsigned long long* out);
-// TEST HOOK: runs element-wise operations of the device's radix-2^29 field implementation (see kernels.hpp launch_field_ops).
-// a, b, out: n x 32 bytes little-endian canonical values (host memory).  Throws on HIP errors / missing GPU.
+// TEST HOOK: runs element-wise operations of the device's field implementations (see k_init.hip k_field_ops).
+// a, b, out: n x 32 bytes little-endian canonical values (host memory).  Throws on HIP errors / missing GPU and on a field / op that does not exist.
 void debug_field_ops(int device, int field, int op, const uint8_t* a, const uint8_t* b, uint8_t* out, size_t n, int chain);
+// TEST HOOKS: gsc_debug_limb_ops / gsc_debug_curve_ops of include/libprove.h (host memory in and out); they throw like debug_field_ops.
+void debug_limb_ops(int device, int field, int op, const int32_t* a, const int32_t* b, const int32_t* c, const int32_t* d, int32_t* out, size_t n);
+void debug_curve_ops(int device, int group, int op, const uint8_t* pts, const uint8_t* inf, const uint8_t* lam, size_t n, size_t k, uint8_t* out, uint8_t* flags);
 
 }  // namespace gsc

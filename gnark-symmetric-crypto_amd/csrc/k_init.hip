@@ -6,6 +6,7 @@
 // the 288 GB of HBM for the bucket pass of Pippenger.
 #include "kernels.hpp"
 #include "bn254_fp29.hpp"
+#include "debug_ops.hpp"
 
 namespace gsc {
 using namespace bn254;
@@ -234,8 +235,13 @@ __global__ void k_ntt_constants(const fe* omega, const fe* omega_inv, const fe* 
     }
 }
 
-// TEST HOOK kernel: element-wise field operations on canonical inputs, through the radix-2^29 implementation, canonical outputs.
-// op: 0 mul, 1 add, 2 sub, 3 sqr, 4 inv, 5 fmms(a,b,b,a+... see host doc), 6 neg, 8 (Fr only) wave_batch_inverse of k_solver.hip; lazy: apply the op `chain` times on a running value
+// TEST HOOK kernels (gsc_debug_field_ops / gsc_debug_limb_ops / gsc_debug_curve_ops of include/libprove.h).  No production path launches them.
+//
+// k_field_ops<F>: element-wise operations on canonical inputs through a radix-2^29 field F, canonical outputs.  The running value r
+// starts at a and the op is applied `chain` times:
+//   0 r*b   1 r+b   2 r-b   3 r^2   4 1/r   5 r*b - b*a (fmms)   6 -r   7 (r-b)*(a+b) (signed-tight x loose operands)
+// Sums and differences stay lazy (carries only, a freeze every 4 steps).  F: field 0 = Fp29, 1 = Fr29 (plain-C products), 2 = Fp29f (the
+// carry-chained products of namespace madc, what every G1 kernel multiplies with).  Field 1, op 8 is k_solver.hip's wave_batch_inverse.
 template <class F>
 __global__ void k_field_ops(int op, const fe* a, const fe* b, fe* out, size_t n, int chain) {
     size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
@@ -257,15 +263,79 @@ __global__ void k_field_ops(int op, const fe* a, const fe* b, fe* out, size_t n,
     }
     out[i] = F::pack(F::from_mont(r));
 }
+// k_field_ops_sat<F>: the same for the saturated 8 x 32-bit Field<FpParams> (field 3) / Field<FrParams> (field 4) of bn254_dev.hpp, whose
+// values are always canonical: ops 0 mul, 1 add, 2 sub, 3 sqr, 4 inv, 6 neg.
+template <class F>
+__global__ void k_field_ops_sat(int op, const fe* a, const fe* b, fe* out, size_t n, int chain) {
+    size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const fe y = F::to_mont(b[i]);
+    fe r = F::to_mont(a[i]);
+    for (int c = 0; c < chain; c++) {
+        switch (op) {
+            case 0: r = F::mul(r, y); break;
+            case 1: r = F::add(r, y); break;
+            case 2: r = F::sub(r, y); break;
+            case 3: r = F::sqr(r); break;
+            case 4: r = F::inv(r); break;
+            case 6: r = F::neg(r); break;
+        }
+    }
+    out[i] = F::from_mont(r);
+}
+// k_limb_ops<F>: raw limbs in (9 x int32 per operand and element), raw limbs out; see dbg::limb_op
+template <class F>
+__global__ void k_limb_ops(int op, const fe9* a, const fe9* b, const fe9* c, const fe9* d, fe9* out, size_t n) {
+    size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    out[i] = dbg::limb_op<F>(op, a[i], b[i], c[i], d[i]);
+}
+// k_curve_ops<F>: Curve9<F> on k canonical affine points per element; see dbg::curve_op
+template <class F>
+__global__ void k_curve_ops(int op, size_t k, const fe* pts, const uint8_t* inf, const fe* lam, fe* out, uint8_t* flags, size_t n) {
+    size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    constexpr size_t W = F::WORDS;
+    flags[i] = (uint8_t)dbg::curve_op<F>(op, k, pts + 2 * W * k * i, inf + k * i, lam + 2 * W * i, out + 2 * W * i);
+}
 
 }  // namespace
 
-void launch_field_ops(int field, int op, const fe* a, const fe* b, fe* out, size_t n, int chain, hipStream_t s) {
-    if (!n) return;
-    if (field == 1 && op == 8) { launch_wave_inverse(a, out, n, s); return; }      // the generic solver's own inversion (8 x 32-bit limbs; k_solver.hip)
+bool launch_field_ops(int field, int op, const fe* a, const fe* b, fe* out, size_t n, int chain, hipStream_t s) {
+    const bool wave_inverse = field == 1 && op == 8;
+    if (field < 0 || field > 4 || op < 0 || (op > 7 && !wave_inverse) || (field >= 3 && (op == 5 || op == 7))) return false;
+    if (!n) return true;
+    if (wave_inverse) { launch_wave_inverse(a, out, n, s); return true; }      // the generic solver's own inversion (8 x 32-bit limbs; k_solver.hip)
     const dim3 grid((unsigned)((n + 63) / 64)), block(64);
-    if (field == 0) hipLaunchKernelGGL(k_field_ops<Fp29>, grid, block, 0, s, op, a, b, out, n, chain);
-    else hipLaunchKernelGGL(k_field_ops<Fr29>, grid, block, 0, s, op, a, b, out, n, chain);
+    switch (field) {
+        case 0: hipLaunchKernelGGL(k_field_ops<Fp29>, grid, block, 0, s, op, a, b, out, n, chain); break;
+        case 1: hipLaunchKernelGGL(k_field_ops<Fr29>, grid, block, 0, s, op, a, b, out, n, chain); break;
+        case 2: hipLaunchKernelGGL(k_field_ops<Fp29f>, grid, block, 0, s, op, a, b, out, n, chain); break;
+        case 3: hipLaunchKernelGGL(k_field_ops_sat<Fp>, grid, block, 0, s, op, a, b, out, n, chain); break;
+        default: hipLaunchKernelGGL(k_field_ops_sat<Fr>, grid, block, 0, s, op, a, b, out, n, chain); break;
+    }
+    return true;
+}
+bool launch_limb_ops(int field, int op, const int32_t* a, const int32_t* b, const int32_t* c, const int32_t* d, int32_t* out, size_t n, hipStream_t s) {
+    if (field < 0 || field > 2 || op < 0 || op >= dbg::LIMB_OPS) return false;
+    if (!n) return true;
+    const dim3 grid((unsigned)((n + 63) / 64)), block(64);
+    const fe9 *pa = reinterpret_cast<const fe9*>(a), *pb = reinterpret_cast<const fe9*>(b), *pc = reinterpret_cast<const fe9*>(c), *pd = reinterpret_cast<const fe9*>(d);
+    fe9* po = reinterpret_cast<fe9*>(out);
+    switch (field) {
+        case 0: hipLaunchKernelGGL(k_limb_ops<Fp29>, grid, block, 0, s, op, pa, pb, pc, pd, po, n); break;
+        case 1: hipLaunchKernelGGL(k_limb_ops<Fr29>, grid, block, 0, s, op, pa, pb, pc, pd, po, n); break;
+        default: hipLaunchKernelGGL(k_limb_ops<Fp29f>, grid, block, 0, s, op, pa, pb, pc, pd, po, n); break;
+    }
+    return true;
+}
+bool launch_curve_ops(int group, int op, size_t k, const fe* pts, const uint8_t* inf, const fe* lam, fe* out, uint8_t* flags, size_t n, hipStream_t s) {
+    if (group < 0 || group > 1 || op < 0 || op >= dbg::CURVE_OPS) return false;
+    if (!n) return true;
+    const dim3 grid((unsigned)((n + 63) / 64)), block(64);
+    if (group == 0) hipLaunchKernelGGL(k_curve_ops<Fp29f>, grid, block, 0, s, op, k, pts, inf, lam, out, flags, n);
+    else hipLaunchKernelGGL(k_curve_ops<Fp2x>, grid, block, 0, s, op, k, pts, inf, lam, out, flags, n);
+    return true;
 }
 
 namespace {

@@ -35,7 +35,10 @@ void launch_ntt_constants(const fe* omega, const fe* omega_inv, const fe* n_inv,
                           int32_t* tw_fwd, int32_t* tw_inv, fe* scale_mid, fe* scale_out, fe* half_c, int32_t* qr, uint32_t* flag, int32_t* tw_inv_plain, fe* scale_mid_plain, hipStream_t s);
 
 // TEST HOOK: radix-2^29 field self-test.  field 0 = Fp, 1 = Fr; a, b, out: n canonical 32-byte little-endian values (device memory).
-void launch_field_ops(int field, int op, const fe* a, const fe* b, fe* out, size_t n, int chain, hipStream_t s);
+// TEST HOOKS (k_init.hip): false when the selector names no field / group or an op that field does not have (nothing is launched then)
+bool launch_field_ops(int field, int op, const fe* a, const fe* b, fe* out, size_t n, int chain, hipStream_t s);
+bool launch_limb_ops(int field, int op, const int32_t* a, const int32_t* b, const int32_t* c, const int32_t* d, int32_t* out, size_t n, hipStream_t s);
+bool launch_curve_ops(int group, int op, size_t k, const fe* pts, const uint8_t* inf, const fe* lam, fe* out, uint8_t* flags, size_t n, hipStream_t s);
 void launch_wave_inverse(const fe* a, fe* out, size_t n, hipStream_t s);      // TEST HOOK (field 1, op 8 of launch_field_ops): k_solver's division, 64 values per inversion
 
 // TEST HOOK / diagnostics: one resident wave records n samples {100 MHz clock, shader clock} `interval` 100 MHz ticks apart into out[2 n]

@@ -77,10 +77,31 @@ extern int gsc_set_deterministic_randomness(const uint8_t *r_be32, const uint8_t
 extern long long gsc_debug_prove(GoSlice params);
 extern long long gsc_debug_vector(int which, uint8_t *out, size_t cap);
 
-/* TEST HOOK: element-wise operations of the device's radix-2^29 field arithmetic, for unit tests against big integers.
- * field: 0 = Fp, 1 = Fr.  op: 0 mul, 1 add, 2 sub, 3 sqr, 4 inverse, 5 r*b - b*a (fused), 6 neg, 7 (r-b)*(a+b); the op is applied
- * `chain` times to a running value r that starts at a.  a, b, out: n canonical 32-byte little-endian values.  0 on success. */
+/* TEST HOOK: element-wise operations of the device's field arithmetic, for unit tests against big integers.
+ * field: 0 = Fp, 1 = Fr in radix 2^29 (plain-C products); 2 = Fp in radix 2^29 with the carry-chained multiply-add products that every
+ *        G1 kernel uses; 3 = Fp, 4 = Fr in the saturated 8 x 32-bit form (decompression, Setup, the generic solver).
+ * op: 0 mul, 1 add, 2 sub, 3 sqr, 4 inverse, 5 r*b - b*a (fused), 6 neg, 7 (r-b)*(a+b); fields 3 and 4 have no ops 5 and 7; field 1 alone
+ *     has op 8, the solver's inversion of 64 values at once.  The op is applied `chain` times to a running value r that starts at a.
+ * a, b, out: n canonical 32-byte little-endian values.  0 on success; -1 for a field / op that does not exist (nothing runs then). */
 extern int gsc_debug_field_ops(int field, int op, const uint8_t *a, const uint8_t *b, uint8_t *out, size_t n, int chain);
+
+/* TEST HOOK: one radix-2^29 operation on RAW limbs: every operand and the result are n x 9 int32 limbs (value = sum l[i] 2^(29 i)), used
+ * exactly as given, in the 2^261 Montgomery domain, without conversion, freeze or pack; this is how operands of every class the field code
+ * admits (tight, signed-tight, loose) reach its instructions.  field: 0, 1, 2 as above.  op: 0 mul(a, b), 1 sqr(a), 2 fmms(a, b, c, d) =
+ * a*b - c*d, 3 norm(a), 4 freeze(a), 5 freeze_near(a); operands an op does not read may be NULL.  The caller keeps the operands inside the
+ * domains bn254_fp29.hpp documents.  0 on success, -1 on error. */
+extern int gsc_debug_limb_ops(int field, int op, const int32_t *a, const int32_t *b, const int32_t *c, const int32_t *d, int32_t *out, size_t n);
+
+/* TEST HOOK: the XYZZ group law of the device (Curve9), one operation or accumulation per element.  group: 0 = G1 (over field 2 above),
+ * 1 = G2 (over Fp2).  A coordinate is one (G1) or two (G2: real, imaginary) canonical 32-byte little-endian values.
+ * pts: n x k affine points (x, y); inf: n x k flags, non-zero = the point at infinity (coordinates ignored); lam: n x 2 non-zero field
+ * elements, the scales under which points 0 and 1 enter where they are XYZZ operands: (x l^2, y l^3, l^2, l^3).
+ * op: 0 dbl(P0), k = 1;  1 P0 + P1 + ... with madd<true> (exact), k >= 2;  2 the same with madd<false> (no equality tests), k >= 2;
+ *     3 add(P0, P1), k = 2;  4 to_aff(P0), k = 1;  5 k >= 1 points into four partial sums with madd<true>, the sums joined with add.
+ *     Points that enter as affine operands (ops 1, 2: all but P0; op 5: all) must not be infinity.
+ * out: n affine results (zeros when there is none); flags: n bytes, bit 0 the result is infinity, bit 1 (op 2) ZZ was 0 mod p after the
+ * first addition, bit 2 (op 2) ZZ was 0 mod p after the last one: then there is no result.  0 on success, -1 on error. */
+extern int gsc_debug_curve_ops(int group, int op, const uint8_t *pts, const uint8_t *inf, const uint8_t *lam, size_t n, size_t k, uint8_t *out, uint8_t *flags);
 
 /* TEST HOOK: the quotient-polynomial kernels (computeH) alone, on caller-supplied vectors, 64 independent columns at once.
  * abc_be: a, b, c one after the other, each [m][64] canonical big-endian 32-byte values (m <= constraints of the algorithm).

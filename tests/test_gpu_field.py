@@ -1,5 +1,7 @@
 """GPU unit tests of the radix-2^29 lazy-limb field arithmetic (bn254_fp29.hpp) against Python big integers: random
-values plus the boundary values where carry / range handling can go wrong, single operations and lazy chains."""
+values plus the boundary values where carry / range handling can go wrong, single operations and lazy chains.  Field 0 / 1 are the
+plain-C products of Fp29 / Fr29, field 2 the carry-chained products of Fp29f (what the G1 kernels run); fields 3 / 4 are the saturated
+8 x 32-bit Field<FpParams> / Field<FrParams> of bn254_dev.hpp."""
 import random
 
 import pytest
@@ -15,7 +17,7 @@ def _values(mod, rnd, n):
     return [e % mod for e in edge] + [rnd.randrange(mod) for _ in range(n - len(edge))]
 
 
-@pytest.mark.parametrize("field,mod", [(0, P), (1, R)])
+@pytest.mark.parametrize("field,mod", [(0, P), (1, R), (2, P)])
 def test_single_operations_match_big_integers(gsc, field, mod):
     rnd = random.Random(field)
     a = _values(mod, rnd, 512); b = list(reversed(_values(mod, rnd, 512)))
@@ -27,7 +29,31 @@ def test_single_operations_match_big_integers(gsc, field, mod):
         assert got == [f(x, y) for x, y in zip(a, b)], op
 
 
-@pytest.mark.parametrize("field,mod", [(0, P), (1, R)])
+@pytest.mark.parametrize("field,mod", [(3, P), (4, R)])
+def test_saturated_field_operations_match_big_integers(gsc, field, mod):
+    rnd = random.Random(field)
+    a = _values(mod, rnd, 517); b = list(reversed(_values(mod, rnd, 517)))
+    rnd.shuffle(b)
+    a += [0, 0, mod - 1, mod - 1, 1, (1 << 253) % mod, 0xffffffff, mod - 0xffffffff]; b += [0, mod - 1, mod - 1, 1, mod - 1, (1 << 253) % mod, 0xffffffff, 0xffffffff]
+    ops = {0: lambda x, y: x * y % mod, 1: lambda x, y: (x + y) % mod, 2: lambda x, y: (x - y) % mod, 3: lambda x, y: x * x % mod,
+           4: lambda x, y: pow(x, mod - 2, mod), 6: lambda x, y: (-x) % mod}
+    for op, f in ops.items():
+        got = gsc.debug_field_ops(field, op, a, b)
+        assert got == [f(x, y) for x, y in zip(a, b)], op
+    # dependent products, squarings, sums and differences
+    assert gsc.debug_field_ops(field, 0, a, b, chain=16) == [x * pow(y, 16, mod) % mod for x, y in zip(a, b)]
+    assert gsc.debug_field_ops(field, 3, a, b, chain=10) == [pow(x, 2 ** 10, mod) for x in a]
+    assert gsc.debug_field_ops(field, 1, a, b, chain=12) == [(x + 12 * y) % mod for x, y in zip(a, b)]
+    assert gsc.debug_field_ops(field, 2, a, b, chain=12) == [(x - 12 * y) % mod for x, y in zip(a, b)]
+
+
+def test_an_op_a_field_does_not_have_is_refused(gsc):
+    for field, op in ((3, 5), (3, 7), (4, 5), (4, 7), (4, 8), (0, 8), (2, 8), (0, 9), (5, 0), (-1, 0), (2, -1)):
+        with pytest.raises(RuntimeError):
+            gsc.debug_field_ops(field, op, [1], [1])
+
+
+@pytest.mark.parametrize("field,mod", [(0, P), (1, R), (2, P)])
 def test_operation_chains_stay_exact(gsc, field, mod):
     rnd = random.Random(10 + field)
     a = _values(mod, rnd, 256); b = _values(mod, rnd, 256)[::-1]
