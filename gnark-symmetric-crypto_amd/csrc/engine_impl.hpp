@@ -185,10 +185,6 @@ class AlgorithmImpl {
     // rows of multiples for `n` bases (row i: len[i] entries at off[i]); work is cut into segments of at most 256 multiples
     template <class AffT, class XyzzT>
     void build_rows(const AffT* bases, size_t n, const std::vector<uint64_t>& off, const std::vector<uint32_t>& len, AffT* table);
-    void launch_build_rows(const G1Aff* b, const MsmRowSeg* sg, size_t n, uint32_t cap, G1Aff* t, G1Xyzz* sc) { launch_build_rows_g1(b, sg, n, cap, t, sc, stream); }
-    void launch_build_rows(const G2Aff* b, const MsmRowSeg* sg, size_t n, uint32_t cap, G2Aff* t, G2Xyzz* sc) { launch_build_rows_g2(b, sg, n, cap, t, sc, stream); }
-    void launch_shift(const G1Aff* in, const uint32_t* src, const uint32_t* sh, size_t n, G1Aff* out) { launch_shift_bases_g1(in, src, sh, n, out, stream); }
-    void launch_shift(const G2Aff* in, const uint32_t* src, const uint32_t* sh, size_t n, G2Aff* out) { launch_shift_bases_g2(in, src, sh, n, out, stream); }
 
     // Lays out one MSM set and builds its tables.  uniform = true (Z): every base gets a full row, windowed kernel.  Otherwise the
     // bases are sorted by what calibrate() saw on their wires: values in {-1, 0, 1} -> bit groups of eight; values of up to
@@ -200,8 +196,8 @@ class AlgorithmImpl {
     void build_set(MsmSet<AffT>& set, const std::vector<uint8_t>& raw, size_t point_bytes, const std::vector<uint32_t>& rows, int c, const char* what, Decomp decomp, bool uniform, int expand_cv = 0,
                    const std::vector<uint8_t>* classes = nullptr, uint32_t zero_row = 0xFFFFFFFFu, bool latency_layout = true);
     // group tables are built in chunks so that the projective scratch stays below ~2 GiB
-    void build_subset(const G1Aff* b, size_t ng, G1Aff* t, uint8_t* ok);
-    void build_subset(const G2Aff* b, size_t ng, G2Aff* t, uint8_t* ok);
+    template <class AffT, class XyzzT>
+    void build_subset(const AffT* b, size_t ng, AffT* t, uint8_t* ok);
 
     void init_key(const R1csFile& cs, const PkFile& key);
 
@@ -228,24 +224,23 @@ class AlgorithmImpl {
         else if (scalars == ln.d_C.p) { c.plane = ln.d_C8.p; c.plane_rows = n_constraints; c.plane_stride = n_constraints; }
         return c;
     }
-    template <class XyzzT, class LR>
-    void reduce_slices(hipStream_t st, XyzzT* pa, XyzzT* pb, size_t nslices, size_t cols, XyzzT* out, LR launch_reduce);
+    template <class XyzzT>
+    void reduce_slices(hipStream_t st, XyzzT* pa, XyzzT* pb, size_t nslices, size_t cols, XyzzT* out);
     // the same for the first `npr` columns of every row of `stride` (latency path: nobody reads the padding proofs' columns)
-    template <class XyzzT, class LRF>
-    void reduce_slices_few(hipStream_t st, XyzzT* pa, XyzzT* pb, size_t nslices, size_t cols, size_t stride, size_t npr, XyzzT* out, LRF launch_reduce_few);
+    template <class XyzzT>
+    void reduce_slices_few(hipStream_t st, XyzzT* pa, XyzzT* pb, size_t nslices, size_t cols, size_t stride, size_t npr, XyzzT* out);
     // scalars: the wire matrix W (Montgomery; wire sets) or h (canonical; Z)
     // The Horner pass of the windowed part is NOT launched here: it is queued in `pending` and flushed together with those of other
-    // sets (flush_horner_*), because each is a serial chain of 254 doublings whose duration does not depend on the batch.
-    template <class AffT, class XyzzT, class LF, class LFF, class LW, class LWF, class LR, class LRF>
+    // sets (flush_horner), because each is a serial chain of 254 doublings whose duration does not depend on the batch.
+    template <class AffT, class XyzzT>
     void run_msm(Lane& ln, const MsmCtx& ctx, const MsmSet<AffT>& set, const fe* scalars, bool wires, size_t B, size_t n_real, XyzzT* pa, XyzzT* pb, XyzzT* sj, XyzzT* flat, XyzzT* sum, bool timed, bool digits_ready,
-                 MsmHornerJobs& pending, LF launch_flat, LFF launch_flat_few, LW launch_win, LWF launch_win_few, LR launch_reduce, LRF launch_reduce_few);
+                 MsmHornerJobs& pending);
     int set_index(const MsmSet<G1Aff>& set) const { const MsmSet<G1Aff>* all[Lane::NSETS] = {&mA, &mB1, &mK, &mZ, &mPed, &mPedSigma, &mZfew, &mC}; for (int k = 0; k < Lane::NSETS; k++) if (all[k] == &set) return k; return 0; }
     // side = true: on the lane's side stream with scratch buffers of its own (flat sets of calls with a handful of statements only)
     // digits_ready: the windowed part's digits are already in the lane's digit buffer (fuse_z_digits): no recoding pass
     void run_msm_g1(Lane& ln, const MsmSet<G1Aff>& set, const fe* scalars, int mont, size_t B, G1Xyzz* sum, bool timed = false, bool side = false, bool digits_ready = false);
     void run_msm_g2(Lane& ln, const MsmSet<G2Aff>& set, const fe* scalars, int mont, size_t B, G2Xyzz* sum, bool side = false);
-    void flush_horner_g1(Lane& ln, size_t B, hipStream_t s) { launch_msm_horner_g1(ln.pending1, B, s); ln.pending1.n = 0; }
-    void flush_horner_g2(Lane& ln, size_t B, hipStream_t s) { launch_msm_horner_g2(ln.pending2, B, s); ln.pending2.n = 0; }
+    template <class AffT> void flush_horner(MsmHornerJobs& pending, size_t B, hipStream_t s) { launch_msm_horner<AffT>(pending, B, s); pending.n = 0; }
 
     void fetch_column(Lane& ln, const fe* mat, size_t rows, size_t B, size_t col, std::vector<uint8_t>& out);
     // The statement's secrets must not outlive the call in device memory (the witness of these circuits IS a cipher key): enqueued behind a

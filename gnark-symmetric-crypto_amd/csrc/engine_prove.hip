@@ -21,33 +21,33 @@ bool be_greater(const uint8_t* a, const uint8_t* b) { int c = memcmp(a, b, 32); 
 bool be_is_zero(const uint8_t* a) { for (int i = 0; i < 32; i++) if (a[i]) return false; return true; }
 }  // namespace
 
-template <class XyzzT, class LR>
-void AlgorithmImpl::reduce_slices(hipStream_t st, XyzzT* pa, XyzzT* pb, size_t nslices, size_t cols, XyzzT* out, LR launch_reduce) {
+template <class XyzzT>
+void AlgorithmImpl::reduce_slices(hipStream_t st, XyzzT* pa, XyzzT* pb, size_t nslices, size_t cols, XyzzT* out) {
     XyzzT* src = pa; XyzzT* alt = pb; size_t ns = nslices;
     for (;;) {
         const size_t groups = msm_reduce_groups(ns, cols);
         XyzzT* dst = groups == 1 ? out : alt;
-        launch_reduce(src, ns, cols, dst, st);
+        launch_msm_reduce(src, ns, cols, dst, st);
         if (groups == 1) break;
         XyzzT* t = src; src = dst; alt = t; ns = groups;
     }
 }
 
-template <class XyzzT, class LRF>
-void AlgorithmImpl::reduce_slices_few(hipStream_t st, XyzzT* pa, XyzzT* pb, size_t nslices, size_t cols, size_t stride, size_t npr, XyzzT* out, LRF launch_reduce_few) {
+template <class XyzzT>
+void AlgorithmImpl::reduce_slices_few(hipStream_t st, XyzzT* pa, XyzzT* pb, size_t nslices, size_t cols, size_t stride, size_t npr, XyzzT* out) {
     XyzzT* src = pa; XyzzT* alt = pb; size_t ns = nslices;
     for (;;) {
         const size_t groups = (ns + 63) / 64;
         XyzzT* dst = groups == 1 ? out : alt;
-        launch_reduce_few(src, ns, cols, stride, npr, dst, st);
+        launch_msm_reduce_few(src, ns, cols, stride, npr, dst, st);
         if (groups == 1) break;
         XyzzT* t = src; src = dst; alt = t; ns = groups;
     }
 }
 
-template <class AffT, class XyzzT, class LF, class LFF, class LW, class LWF, class LR, class LRF>
+template <class AffT, class XyzzT>
 void AlgorithmImpl::run_msm(Lane& ln, const MsmCtx& ctx, const MsmSet<AffT>& set, const fe* scalars, bool wires, size_t B, size_t n_real, XyzzT* pa, XyzzT* pb, XyzzT* sj, XyzzT* flat, XyzzT* sum, bool timed, bool digits_ready,
-             MsmHornerJobs& pending, LF launch_flat, LFF launch_flat_few, LW launch_win, LWF launch_win_few, LR launch_reduce, LRF launch_reduce_few) {
+             MsmHornerJobs& pending) {
     size_t per = 0;
     const bool fewm = n_real <= (size_t)cfg.few_max && cfg.few_path;
     if (fewm && set.latency_flat()) {
@@ -61,13 +61,13 @@ void AlgorithmImpl::run_msm(Lane& ln, const MsmCtx& ctx, const MsmSet<AffT>& set
             launch_msm_recode_flat_few(ra, n_real, ctx.stream);
             MsmFlatArgs a{m.ftable.p, m.rowoff.p, m.rowlen.p, m.nflat, ctx.digits, B, nslices, 512, pa + ns * B, m.nbit, m.sub.p, ctx.gok, scalars, m.frows.p};
             if (stamp) HIP_CHECK(hipEventRecord(ln.ev[5], ctx.stream));
-            launch_flat_few(a, n_real, ctx.stream);
+            launch_msm_flat_few<AffT>(a, n_real, ctx.stream);
             if (stamp) HIP_CHECK(hipEventRecord(ln.ev[6], ctx.stream));
             ns += nslices;
         };
         part(set, timed);
         if (set.few_wide) part(*set.few_wide, false);
-        if (ns) reduce_slices_few(ctx.stream, pa, pb, ns, B, B, n_real, sum, launch_reduce_few);
+        if (ns) reduce_slices_few(ctx.stream, pa, pb, ns, B, B, n_real, sum);
         else HIP_CHECK(hipMemsetAsync(sum, 0, B * sizeof(XyzzT), ctx.stream));
         return;
     }
@@ -78,15 +78,15 @@ void AlgorithmImpl::run_msm(Lane& ln, const MsmCtx& ctx, const MsmSet<AffT>& set
             launch_msm_recode_flat_few(ra, n_real, ctx.stream);
             MsmFlatArgs a{set.ftable.p, set.rowoff.p, set.rowlen.p, set.nflat, ctx.digits, B, nslices, 512, pa, set.nbit, set.sub.p, ctx.gok, scalars, set.frows.p};
             if (timed) HIP_CHECK(hipEventRecord(ln.ev[5], ctx.stream));
-            launch_flat_few(a, n_real, ctx.stream);
+            launch_msm_flat_few<AffT>(a, n_real, ctx.stream);
             if (timed) HIP_CHECK(hipEventRecord(ln.ev[6], ctx.stream));
-            reduce_slices_few(ctx.stream, pa, pb, nslices, B, B, n_real, set.nwide ? flat : sum, launch_reduce_few);
+            reduce_slices_few(ctx.stream, pa, pb, nslices, B, B, n_real, set.nwide ? flat : sum);
         } else {
             const size_t nslices = msm_slices(set.nflat, 1, 256, B, per);
             launch_msm_recode_flat(ra, ctx.stream);
             MsmFlatArgs a{set.ftable.p, set.rowoff.p, set.rowlen.p, set.nflat, ctx.digits, B, nslices, per, pa, set.nbit, set.sub.p, ctx.gok, scalars, set.frows.p};
-            launch_flat(a, ctx.stream);
-            reduce_slices(ctx.stream, pa, pb, nslices, B, set.nwide ? flat : sum, launch_reduce);
+            launch_msm_flat<AffT>(a, ctx.stream);
+            reduce_slices(ctx.stream, pa, pb, nslices, B, set.nwide ? flat : sum);
         }
     }
     if (set.nwide) {
@@ -101,11 +101,11 @@ void AlgorithmImpl::run_msm(Lane& ln, const MsmCtx& ctx, const MsmSet<AffT>& set
         MsmWinArgs a{set.wtable.p, set.c, set.nwin, set.nwide, ctx.digits, B, nslices, per, pa, timed && !few ? ln.d_clk.p : nullptr,
                      timed && cfg.z_exp_entry_bits > 0 && cfg.z_exp_entry_bits < 31 ? (1u << cfg.z_exp_entry_bits) - 1 : 0u};
         if (timed) HIP_CHECK(hipEventRecord(ln.ev[5], ctx.stream));
-        if (few) launch_win_few(a, n_real, ctx.stream);
-        else launch_win(a, ctx.stream);
+        if (few) launch_msm_win_few<AffT>(a, n_real, ctx.stream);
+        else launch_msm_win<AffT>(a, ctx.stream);
         if (timed) HIP_CHECK(hipEventRecord(ln.ev[6], ctx.stream));
-        if (few) reduce_slices_few(ctx.stream, pa, pb, nslices, Bw, B, n_real, sj, launch_reduce_few);
-        else reduce_slices(ctx.stream, pa, pb, nslices, Bw, sj, launch_reduce);      // slices -> one sum per (window, proof)
+        if (few) reduce_slices_few(ctx.stream, pa, pb, nslices, Bw, B, n_real, sj);
+        else reduce_slices(ctx.stream, pa, pb, nslices, Bw, sj);      // slices -> one sum per (window, proof)
         if (pending.n >= MSM_HORNER_JOBS) throw std::runtime_error("internal: too many pending Horner passes");
         pending.job[pending.n++] = MsmHornerJob{sj, set.nflat ? flat : (XyzzT*)nullptr, sum, set.nwin, set.c};
     }
@@ -116,16 +116,15 @@ void AlgorithmImpl::run_msm_g1(Lane& ln, const MsmSet<G1Aff>& set, const fe* sca
     const int k = set_index(set);
     if (side) {
         if (!set.latency_flat() || B != 64) throw std::runtime_error("internal: side-stream MSM on a set with a windowed part");
-        run_msm(ln, with_plane(MsmCtx{ln.side, ln.d_digits_s.p, ln.d_gok_s.p}, ln, scalars), set, scalars, mont != 0, B, ln.n_real, ln.d_part1c.p, ln.d_part1d.p, ln.d_sj1[k].p, ln.d_flat1[k].p, sum, false, false, ln.pending1,
-                launch_msm_flat_g1, launch_msm_flat_few_g1, launch_msm_win_g1, launch_msm_win_few_g1, launch_msm_reduce_g1, launch_msm_reduce_few_g1);
+        run_msm(ln, with_plane(MsmCtx{ln.side, ln.d_digits_s.p, ln.d_gok_s.p}, ln, scalars), set, scalars, mont != 0, B, ln.n_real, ln.d_part1c.p, ln.d_part1d.p, ln.d_sj1[k].p, ln.d_flat1[k].p, sum, false, false, ln.pending1);
         return;
     }
-    run_msm(ln, with_plane(MsmCtx{ln.stream, ln.d_digits_w.p && &set != &mZ ? ln.d_digits_w.p : ln.d_digits.p, ln.d_gok.p}, ln, scalars), set, scalars, mont != 0, B, ln.n_real, ln.d_part1a.p, ln.d_part1b.p, ln.d_sj1[k].p, ln.d_flat1[k].p, sum, timed, digits_ready, ln.pending1, launch_msm_flat_g1, launch_msm_flat_few_g1, launch_msm_win_g1, launch_msm_win_few_g1, launch_msm_reduce_g1, launch_msm_reduce_few_g1);
+    run_msm(ln, with_plane(MsmCtx{ln.stream, ln.d_digits_w.p && &set != &mZ ? ln.d_digits_w.p : ln.d_digits.p, ln.d_gok.p}, ln, scalars), set, scalars, mont != 0, B, ln.n_real, ln.d_part1a.p, ln.d_part1b.p, ln.d_sj1[k].p, ln.d_flat1[k].p, sum, timed, digits_ready, ln.pending1);
 }
 
 void AlgorithmImpl::run_msm_g2(Lane& ln, const MsmSet<G2Aff>& set, const fe* scalars, int mont, size_t B, G2Xyzz* sum, bool side) {
     if (side && (!set.latency_flat() || B != 64)) throw std::runtime_error("internal: side-stream MSM on a set with a windowed part");
-    run_msm(ln, with_plane(side ? MsmCtx{ln.side2, ln.d_digits_s2.p, ln.d_gok_s2.p} : MsmCtx{ln.stream, ln.d_digits_w.p ? ln.d_digits_w.p : ln.d_digits.p, ln.d_gok.p}, ln, scalars), set, scalars, mont != 0, B, ln.n_real, ln.d_part2a.p, ln.d_part2b.p, ln.d_sj2.p, ln.d_flat2.p, sum, false, false, ln.pending2, launch_msm_flat_g2, launch_msm_flat_few_g2, launch_msm_win_g2, launch_msm_win_few_g2, launch_msm_reduce_g2, launch_msm_reduce_few_g2);
+    run_msm(ln, with_plane(side ? MsmCtx{ln.side2, ln.d_digits_s2.p, ln.d_gok_s2.p} : MsmCtx{ln.stream, ln.d_digits_w.p ? ln.d_digits_w.p : ln.d_digits.p, ln.d_gok.p}, ln, scalars), set, scalars, mont != 0, B, ln.n_real, ln.d_part2a.p, ln.d_part2b.p, ln.d_sj2.p, ln.d_flat2.p, sum, false, false, ln.pending2);
 }
 
 void AlgorithmImpl::fetch_column(Lane& ln, const fe* mat, size_t rows, size_t B, size_t col, std::vector<uint8_t>& out) {
@@ -258,7 +257,7 @@ void AlgorithmImpl::prove_chunk(Lane& ln, const ProofRequest* reqs, size_t n, Pr
         // nothing leaves the stream.
         run_levels(0, commit_level);
         run_msm_g1(ln, mPed, ln.d_W.p, 1, B, ln.d_sumD.p);
-        flush_horner_g1(ln, B, ln.stream);
+        flush_horner<G1Aff>(ln.pending1, B, ln.stream);
         launch_points_to_affine_be(ln.d_sumD.p, B, ln.d_cpts.p, ln.d_flags.p, 8, ln.stream);
         launch_challenge_from_point(ln.d_cpts.p, ln.d_commit.p, B, ln.stream);
         run_levels(commit_level, n_levels);
@@ -354,7 +353,7 @@ void AlgorithmImpl::prove_chunk(Lane& ln, const ProofRequest* reqs, size_t n, Pr
     if (!early_ab) {
         run_msm_g1(ln, mA, ln.d_W.p, 1, B, ln.d_sumA.p);
         run_msm_g1(ln, mB1, ln.d_W.p, 1, B, ln.d_sumB1.p);
-        flush_horner_g1(ln, B, ln.stream);                                       // (AES-V2: the wide wires of A and B1; nothing for ChaCha20-V3)
+        flush_horner<G1Aff>(ln.pending1, B, ln.stream);                                       // (AES-V2: the wide wires of A and B1; nothing for ChaCha20-V3)
         HIP_CHECK(hipEventRecord(ln.ev_ab, ln.stream));
         HIP_CHECK(hipStreamWaitEvent(ln.side, ln.ev_ab, 0));
         launch_fin_scalarmul(ln.d_sumA.p, ln.d_sumB1.p, ln.d_rs.p, B, ln.d_out.p, ln.d_flags.p, ln.d_tmp.p, ln.side);
@@ -363,7 +362,7 @@ void AlgorithmImpl::prove_chunk(Lane& ln, const ProofRequest* reqs, size_t n, Pr
     if (ln.pending2.n) {                                                         // the G2 Horner chain (3x a G1 one) also goes beside the MSMs
         HIP_CHECK(hipEventRecord(ln.ev_b2, ln.stream));
         HIP_CHECK(hipStreamWaitEvent(ln.side, ln.ev_b2, 0));
-        flush_horner_g2(ln, B, ln.side);
+        flush_horner<G2Aff>(ln.pending2, B, ln.side);
     }
     HIP_CHECK(hipEventRecord(ln.ev_fs, ln.side));
     run_msm_g1(ln, mK, ln.d_W.p, 1, B, ln.d_sumK.p);
@@ -375,7 +374,7 @@ void AlgorithmImpl::prove_chunk(Lane& ln, const ProofRequest* reqs, size_t n, Pr
     if (overlap_q) { HIP_CHECK(hipEventRecord(ln.ev_ws, ln.stream)); HIP_CHECK(hipStreamWaitEvent(ln.stream, ln.ev[2], 0)); }      // the wire sets are through; wait for d and its digits
     run_msm_g1(ln, use_zfew ? mZfew : mZ, ln.d_A.p, 0, B, ln.d_sumZ.p, !latency_call, false, z_digits_ready);
     if (has_commitment) run_msm_g1(ln, mPedSigma, ln.d_W.p, 1, B, ln.d_sumPok.p);      // proof of knowledge of the commitment: same scalars over sigma * Basis
-    flush_horner_g1(ln, B, ln.stream);                                           // K, Z, PedSigma: one launch
+    flush_horner<G1Aff>(ln.pending1, B, ln.stream);                                           // K, Z, PedSigma: one launch
     if (has_commitment) launch_points_to_affine_be(ln.d_sumPok.p, B, ln.d_cpts.p + 64 * B, ln.d_flags.p, 16, ln.stream);
     HIP_CHECK(hipGetLastError());      // MSM launches
     HIP_CHECK(hipEventRecord(ln.ev[3], ln.stream));

@@ -234,7 +234,7 @@ void AlgorithmImpl::build_rows(const AffT* bases, size_t n, const std::vector<ui
     size_t chunk = ((size_t)4 << 30) / (cap * sizeof(XyzzT)); if (chunk > segs.size()) chunk = segs.size();
     DevBuf<XyzzT> scratch(chunk * cap); DevBuf<MsmRowSeg> d_segs(segs.size());
     d_segs.upload(segs.data(), segs.size(), stream);
-    for (size_t t0 = 0; t0 < segs.size(); t0 += chunk) launch_build_rows(bases, d_segs.p + t0, segs.size() - t0 < chunk ? segs.size() - t0 : chunk, cap, table, scratch.p);
+    for (size_t t0 = 0; t0 < segs.size(); t0 += chunk) launch_build_rows(bases, d_segs.p + t0, segs.size() - t0 < chunk ? segs.size() - t0 : chunk, cap, table, scratch.p, stream);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(stream));
 }
@@ -283,7 +283,7 @@ void AlgorithmImpl::build_set(MsmSet<AffT>& set, const std::vector<uint8_t>& raw
         if (set.nflat) {
             DevBuf<AffT> fb(set.nflat); DevBuf<uint32_t> d_src(set.nflat), d_shift(set.nflat);
             d_src.upload(src.data(), src.size(), stream); d_shift.upload(shift.data(), shift.size(), stream);
-            launch_shift(bases.p, d_src.p, d_shift.p, set.nflat, fb.p);
+            launch_shift_bases(bases.p, d_src.p, d_shift.p, set.nflat, fb.p, stream);
             std::vector<uint64_t> off(set.nflat); size_t entries = 0;
             for (size_t i = 0; i < set.nflat; i++) { off[i] = entries; entries += len[i]; }
             set.ftable.alloc(entries); table_bytes += set.ftable.bytes();
@@ -295,7 +295,7 @@ void AlgorithmImpl::build_set(MsmSet<AffT>& set, const std::vector<uint8_t>& raw
                 const size_t ng = set.nbit / 8;
                 set.sub.alloc(ng * MSM_GROUP_ENTRIES); set.group_ok.alloc(ng);
                 table_bytes += set.sub.bytes();
-                build_subset(fb.p, ng, set.sub.p, set.group_ok.p);
+                build_subset<AffT, XyzzT>(fb.p, ng, set.sub.p, set.group_ok.p);
             }
             HIP_CHECK(hipGetLastError());
             HIP_CHECK(hipStreamSynchronize(stream));      // fb, d_src, d_shift go out of scope
@@ -307,7 +307,7 @@ void AlgorithmImpl::build_set(MsmSet<AffT>& set, const std::vector<uint8_t>& raw
         std::vector<uint32_t> zero(set.nwide, 0u), wrows(set.nwide);
         for (size_t i = 0; i < set.nwide; i++) wrows[i] = rows[wide[i]];
         d_src.upload(wide.data(), set.nwide, stream); d_shift.upload(zero.data(), set.nwide, stream);
-        launch_shift(bases.p, d_src.p, d_shift.p, set.nwide, wb.p);
+        launch_shift_bases(bases.p, d_src.p, d_shift.p, set.nwide, wb.p, stream);
         set.wrows.alloc(set.nwide); set.wrows.upload(wrows.data(), set.nwide, stream);
         set.wtable.alloc(set.nwide * D); table_bytes += set.wtable.bytes();
         std::vector<uint64_t> off(set.nwide); std::vector<uint32_t> len(set.nwide, (uint32_t)D);
@@ -324,17 +324,11 @@ void AlgorithmImpl::build_set(MsmSet<AffT>& set, const std::vector<uint8_t>& raw
     }
 }
 
-void AlgorithmImpl::build_subset(const G1Aff* b, size_t ng, G1Aff* t, uint8_t* ok) {
-    size_t chunk = ((size_t)2 << 30) / (MSM_GROUP_ENTRIES * sizeof(G1Xyzz)); if (chunk > ng) chunk = ng;
-    DevBuf<G1Xyzz> sc(chunk * MSM_GROUP_ENTRIES);
-    for (size_t g0 = 0; g0 < ng; g0 += chunk) launch_build_subset_g1(b + 8 * g0, ng - g0 < chunk ? ng - g0 : chunk, t + g0 * MSM_GROUP_ENTRIES, sc.p, ok + g0, stream);
-    HIP_CHECK(hipStreamSynchronize(stream));
-}
-
-void AlgorithmImpl::build_subset(const G2Aff* b, size_t ng, G2Aff* t, uint8_t* ok) {
-    size_t chunk = ((size_t)2 << 30) / (MSM_GROUP_ENTRIES * sizeof(G2Xyzz)); if (chunk > ng) chunk = ng;
-    DevBuf<G2Xyzz> sc(chunk * MSM_GROUP_ENTRIES);
-    for (size_t g0 = 0; g0 < ng; g0 += chunk) launch_build_subset_g2(b + 8 * g0, ng - g0 < chunk ? ng - g0 : chunk, t + g0 * MSM_GROUP_ENTRIES, sc.p, ok + g0, stream);
+template <class AffT, class XyzzT>
+void AlgorithmImpl::build_subset(const AffT* b, size_t ng, AffT* t, uint8_t* ok) {
+    size_t chunk = ((size_t)2 << 30) / (MSM_GROUP_ENTRIES * sizeof(XyzzT)); if (chunk > ng) chunk = ng;
+    DevBuf<XyzzT> sc(chunk * MSM_GROUP_ENTRIES);
+    for (size_t g0 = 0; g0 < ng; g0 += chunk) launch_build_subset(b + 8 * g0, ng - g0 < chunk ? ng - g0 : chunk, t + g0 * MSM_GROUP_ENTRIES, sc.p, ok + g0, stream);
     HIP_CHECK(hipStreamSynchronize(stream));
 }
 

@@ -373,11 +373,11 @@ void launch_fr_from_be(const uint8_t* in, fe* out, size_t n, hipStream_t s) {
 void launch_fr_inverse(const fe* in, fe* out, size_t n, hipStream_t s) {
     if (n) hipLaunchKernelGGL(k_fr_inverse, dim3(blocks_for(n, 64)), dim3(64), 0, s, in, out, n);
 }
-void launch_build_subset_g1(const G1Aff* bases, size_t ngroups, G1Aff* table, G1Xyzz* scratch, uint8_t* ok, hipStream_t s) {
+void launch_build_subset(const G1Aff* bases, size_t ngroups, G1Aff* table, G1Xyzz* scratch, uint8_t* ok, hipStream_t s) {
     if (ngroups) hipLaunchKernelGGL((k_build_subset<Fp29f, Fp>), dim3(blocks_for(ngroups, 64)), dim3(64), 0, s,
                                     reinterpret_cast<const Aff<Fp>*>(bases), ngroups, reinterpret_cast<fe*>(table), reinterpret_cast<fe*>(scratch), ok);
 }
-void launch_build_subset_g2(const G2Aff* bases, size_t ngroups, G2Aff* table, G2Xyzz* scratch, uint8_t* ok, hipStream_t s) {
+void launch_build_subset(const G2Aff* bases, size_t ngroups, G2Aff* table, G2Xyzz* scratch, uint8_t* ok, hipStream_t s) {
     if (ngroups) hipLaunchKernelGGL((k_build_subset<Fp2x, Fp2>), dim3(blocks_for(ngroups, 64)), dim3(64), 0, s,
                                     reinterpret_cast<const Aff<Fp2>*>(bases), ngroups, reinterpret_cast<fe*>(table), reinterpret_cast<fe*>(scratch), ok);
 }

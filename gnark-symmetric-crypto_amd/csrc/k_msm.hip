@@ -2,42 +2,13 @@
 //
 // The gather-accumulate kernels themselves are in k_msm_win.hip; this file holds what follows them in groth16.Prove
 // (reference libraries/prover/impl/provers.go:148,216; SURVEY.md §8(a) a9 msmReduceChunk, a12 assembly, App. D).
-#include "kernels.hpp"
-#include "bn254_fp29.hpp"
+#include "msm_dev.hpp"
 #include "sha256_dev.hpp"
 
 namespace gsc {
 using namespace bn254;
 
 namespace {
-
-
-// |s| <= (r-1)/2 after sign normalisation; returns true when the point must be negated
-__device__ __forceinline__ bool sign_normalise(fe& s) {
-    // (r-1)/2
-    bool gt = false, decided = false;
-#pragma unroll
-    for (int i = 7; i >= 0; i--) {
-        const uint32_t lo = FrParams::mod(i) - (i == 0 ? 1u : 0u);
-        const uint32_t hi = i < 7 ? FrParams::mod(i + 1) : 0u;
-        const uint32_t h = (lo >> 1) | (hi << 31);
-        if (!decided && s.l[i] != h) { gt = s.l[i] > h; decided = true; }
-    }
-    if (gt) {
-        uint64_t br = 0;
-#pragma unroll
-        for (int i = 0; i < 8; i++) { uint64_t d = (uint64_t)FrParams::mod(i) - s.l[i] - br; s.l[i] = (uint32_t)d; br = (d >> 32) & 1; }
-    }
-    return gt;
-}
-
-__device__ __forceinline__ fe9 shfl_xor_e(const fe9& v, int m) {
-    fe9 r;
-#pragma unroll
-    for (int i = 0; i < 9; i++) r.l[i] = __shfl_xor(v.l[i], m);
-    return r;
-}
-__device__ __forceinline__ fe9x2 shfl_xor_e(const fe9x2& v, int m) { return fe9x2{shfl_xor_e(v.a0, m), shfl_xor_e(v.a1, m)}; }
 
 // one wave sums up to 64 slices of one proof: lanes = slices, butterfly over __shfl_xor
 template <class F>
@@ -46,12 +17,7 @@ __global__ __launch_bounds__(64) void k_msm_reduce(const fe* partial, size_t nsl
     const size_t p = blockIdx.x, grp = blockIdx.y;
     const size_t slice = grp * 64 + threadIdx.x;
     Xyzz9<F> v = slice < nslices ? C::load_xyzz(partial + (slice * batch + p) * (4 * F::WORDS)) : C::infinity();
-    for (int m = 32; m >= 1; m >>= 1) {
-        Xyzz9<F> o;
-        o.x = shfl_xor_e(v.x, m); o.y = shfl_xor_e(v.y, m); o.zz = shfl_xor_e(v.zz, m); o.zzz = shfl_xor_e(v.zzz, m);
-        o.inf = __shfl_xor((int)v.inf, m) != 0;
-        v = C::add(v, o);
-    }
+    v = wave_sum(v);
     if (threadIdx.x == 0) C::store_xyzz(out + (grp * batch + p) * (4 * F::WORDS), v);
 }
 
@@ -63,12 +29,7 @@ __global__ __launch_bounds__(64) void k_msm_reduce_few(const fe* partial, size_t
     const size_t p = (size_t)(blockIdx.x / npr) * stride + blockIdx.x % npr, grp = blockIdx.y;
     const size_t slice = grp * 64 + threadIdx.x;
     Xyzz9<F> v = slice < nslices ? C::load_xyzz(partial + (slice * cols + p) * (4 * F::WORDS)) : C::infinity();
-    for (int m = 32; m >= 1; m >>= 1) {
-        Xyzz9<F> o;
-        o.x = shfl_xor_e(v.x, m); o.y = shfl_xor_e(v.y, m); o.zz = shfl_xor_e(v.zz, m); o.zzz = shfl_xor_e(v.zzz, m);
-        o.inf = __shfl_xor((int)v.inf, m) != 0;
-        v = C::add(v, o);
-    }
+    v = wave_sum(v);
     if (threadIdx.x == 0) C::store_xyzz(out + (grp * cols + p) * (4 * F::WORDS), v);
 }
 
@@ -194,12 +155,7 @@ __global__ __launch_bounds__(64) void k_fin_scalarmul_few(const G1Xyzz* sumA, co
             const Xyzz9<F> t = G1x::add(acc, mine);
             if ((chunk >> b) & 1u) acc = t;
         }
-        for (int m = 32; m >= 1; m >>= 1) {
-            Xyzz9<F> o;
-            o.x = shfl_xor_e(acc.x, m); o.y = shfl_xor_e(acc.y, m); o.zz = shfl_xor_e(acc.zz, m); o.zzz = shfl_xor_e(acc.zzz, m);
-            o.inf = __shfl_xor((int)acc.inf, m) != 0;
-            acc = G1x::add(acc, o);
-        }
+        acc = wave_sum(acc);
     }
     if (lane == 0) G1x::store_xyzz(reinterpret_cast<fe*>(tmp) + ((size_t)role * batch + p) * 4, acc);
 }
@@ -262,29 +218,24 @@ __global__ void k_challenge_from_point(const uint8_t* cpts, fe* commit, size_t b
 }  // namespace
 
 // returns the number of partial sums left per proof (1 = done)
-template <class F>
-static size_t launch_msm_reduce(const fe* partial, size_t nslices, size_t batch, fe* out, hipStream_t s) {
+template <class XyzzT, class F = typename GroupOf<XyzzT>::F>
+static size_t msm_reduce(const XyzzT* partial, size_t nslices, size_t batch, XyzzT* out, hipStream_t s) {
     const size_t groups = msm_reduce_groups(nslices, batch);
-    if (msm_reduce_by_proof(nslices, batch)) hipLaunchKernelGGL(k_msm_reduce_seq<F>, dim3((unsigned)(batch / 64), (unsigned)groups), dim3(64), 0, s, partial, nslices, batch, out);
-    else hipLaunchKernelGGL(k_msm_reduce<F>, dim3((unsigned)batch, (unsigned)groups), dim3(64), 0, s, partial, nslices, batch, out);
+    const fe* in = reinterpret_cast<const fe*>(partial); fe* o = reinterpret_cast<fe*>(out);
+    if (msm_reduce_by_proof(nslices, batch)) hipLaunchKernelGGL(k_msm_reduce_seq<F>, dim3((unsigned)(batch / 64), (unsigned)groups), dim3(64), 0, s, in, nslices, batch, o);
+    else hipLaunchKernelGGL(k_msm_reduce<F>, dim3((unsigned)batch, (unsigned)groups), dim3(64), 0, s, in, nslices, batch, o);
     return groups;
 }
-size_t launch_msm_reduce_few_g1(const G1Xyzz* partial, size_t nslices, size_t cols, size_t stride, size_t npr, G1Xyzz* out, hipStream_t s) {
+template <class XyzzT, class F = typename GroupOf<XyzzT>::F>
+static size_t msm_reduce_few(const XyzzT* partial, size_t nslices, size_t cols, size_t stride, size_t npr, XyzzT* out, hipStream_t s) {
     const size_t groups = (nslices + 63) / 64;
-    hipLaunchKernelGGL(k_msm_reduce_few<Fp29f>, dim3((unsigned)(cols / stride * npr), (unsigned)groups), dim3(64), 0, s, reinterpret_cast<const fe*>(partial), nslices, cols, reinterpret_cast<fe*>(out), (uint32_t)npr, (uint32_t)stride);
+    hipLaunchKernelGGL(k_msm_reduce_few<F>, dim3((unsigned)(cols / stride * npr), (unsigned)groups), dim3(64), 0, s, reinterpret_cast<const fe*>(partial), nslices, cols, reinterpret_cast<fe*>(out), (uint32_t)npr, (uint32_t)stride);
     return groups;
 }
-size_t launch_msm_reduce_few_g2(const G2Xyzz* partial, size_t nslices, size_t cols, size_t stride, size_t npr, G2Xyzz* out, hipStream_t s) {
-    const size_t groups = (nslices + 63) / 64;
-    hipLaunchKernelGGL(k_msm_reduce_few<Fp2x>, dim3((unsigned)(cols / stride * npr), (unsigned)groups), dim3(64), 0, s, reinterpret_cast<const fe*>(partial), nslices, cols, reinterpret_cast<fe*>(out), (uint32_t)npr, (uint32_t)stride);
-    return groups;
-}
-size_t launch_msm_reduce_g1(const G1Xyzz* partial, size_t nslices, size_t batch, G1Xyzz* out, hipStream_t s) {
-    return launch_msm_reduce<Fp29f>(reinterpret_cast<const fe*>(partial), nslices, batch, reinterpret_cast<fe*>(out), s);
-}
-size_t launch_msm_reduce_g2(const G2Xyzz* partial, size_t nslices, size_t batch, G2Xyzz* out, hipStream_t s) {
-    return launch_msm_reduce<Fp2x>(reinterpret_cast<const fe*>(partial), nslices, batch, reinterpret_cast<fe*>(out), s);
-}
+size_t launch_msm_reduce(const G1Xyzz* partial, size_t nslices, size_t batch, G1Xyzz* out, hipStream_t s) { return msm_reduce(partial, nslices, batch, out, s); }
+size_t launch_msm_reduce(const G2Xyzz* partial, size_t nslices, size_t batch, G2Xyzz* out, hipStream_t s) { return msm_reduce(partial, nslices, batch, out, s); }
+size_t launch_msm_reduce_few(const G1Xyzz* partial, size_t nslices, size_t cols, size_t stride, size_t npr, G1Xyzz* out, hipStream_t s) { return msm_reduce_few(partial, nslices, cols, stride, npr, out, s); }
+size_t launch_msm_reduce_few(const G2Xyzz* partial, size_t nslices, size_t cols, size_t stride, size_t npr, G2Xyzz* out, hipStream_t s) { return msm_reduce_few(partial, nslices, cols, stride, npr, out, s); }
 void launch_classify_wires(const fe* W, size_t n_wires, size_t batch, const uint32_t* status, uint8_t* cls, hipStream_t s) {
     if (n_wires) hipLaunchKernelGGL(k_classify_wires, dim3((unsigned)n_wires), dim3(64), 0, s, W, n_wires, batch, status, cls);
 }

@@ -18,8 +18,7 @@
 //   eight ternary wires at a time through a table of their signed subset sums; rows only as long as the wire was seen to need.
 // Both are predictions made at InitAlgorithm and checked for every wave of proofs: a scalar that does not fit is multiplied out
 // by double-and-add, so results never depend on the prediction.
-#include "kernels.hpp"
-#include "bn254_fp29.hpp"
+#include "msm_dev.hpp"
 
 namespace gsc {
 using namespace bn254;
@@ -27,24 +26,6 @@ using namespace bn254;
 namespace {
 
 __device__ __forceinline__ uint32_t uni(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
-
-// |s| <= (r-1)/2 after sign normalisation; returns true when the point must be negated
-__device__ __forceinline__ bool sign_normalise(fe& s) {
-    bool gt = false, decided = false;
-#pragma unroll
-    for (int i = 7; i >= 0; i--) {
-        const uint32_t lo = FrParams::mod(i) - (i == 0 ? 1u : 0u);
-        const uint32_t hi = i < 7 ? FrParams::mod(i + 1) : 0u;
-        const uint32_t h = (lo >> 1) | (hi << 31);
-        if (!decided && s.l[i] != h) { gt = s.l[i] > h; decided = true; }
-    }
-    if (gt) {
-        uint64_t br = 0;
-#pragma unroll
-        for (int i = 0; i < 8; i++) { uint64_t d = (uint64_t)FrParams::mod(i) - s.l[i] - br; s.l[i] = (uint32_t)d; br = (d >> 32) & 1; }
-    }
-    return gt;
-}
 
 // ---- signed-digit recoding (windowed sets) --------------------------------------------------------------------------------------
 // One thread per (octet of bases, proof): eight scalars -> for every window one 16-byte word of eight int16 digits.
@@ -67,19 +48,13 @@ __global__ __launch_bounds__(64) void k_recode(MsmRecodeArgs a) {
             if (MONT) { s[i] = Fr::from_mont(s[i]); if (sign_normalise(s[i])) neg |= 1u << i; }
         } else s[i] = fe{};
     }
-    const uint32_t c = (uint32_t)a.c, cmask = (1u << c) - 1, D = 1u << (c - 1);
     for (int j = 0; j < a.nwin; j++) {
         uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
         for (int i = 0; i < 8; i++) {
-            uint32_t raw = (s[i].l[0] & cmask) + ((carry >> i) & 1u);
-#pragma unroll
-            for (int q = 0; q < 7; q++) s[i].l[q] = __builtin_amdgcn_alignbit(s[i].l[q + 1], s[i].l[q], c);
-            s[i].l[7] >>= c;
-            const bool ng = (neg >> i) & 1u;
-            int32_t d = (int32_t)raw;
-            if (raw >= D + (ng ? 1u : 0u)) { d -= (int32_t)(1u << c); carry |= 1u << i; } else carry &= ~(1u << i);
-            if (ng) d = -d;
+            uint32_t cb = (carry >> i) & 1u;
+            const int32_t d = signed_digit_step(s[i], (uint32_t)a.c, cb, (neg >> i) & 1u);
+            carry = cb ? carry | (1u << i) : carry & ~(1u << i);
             if (WIDE) w[i] = (uint32_t)d; else w[i >> 1] |= ((uint32_t)d & 0xFFFFu) << (16 * (i & 1));
         }
         const size_t at = ((size_t)j * noct + o) * a.batch + p;
@@ -125,16 +100,9 @@ __device__ __forceinline__ void recode_flat_octet(const MsmFlatRecodeArgs& a, si
         fe s = load_scalar(U(a.rows[8 * o]), tv);
         if (a.mont) s = Fr::from_mont(s);
         const bool ng = sign_normalise(s);
-        const uint32_t c = (uint32_t)a.c, cmask = (1u << c) - 1, D = 1u << (c - 1);
         uint32_t carry = 0;
         for (int32_t j = 0; j < win0 + 8; j++) {                    // digits below win0 are recomputed for their carry only
-            uint32_t raw = (s.l[0] & cmask) + carry;
-#pragma unroll
-            for (int q = 0; q < 7; q++) s.l[q] = __builtin_amdgcn_alignbit(s.l[q + 1], s.l[q], c);
-            s.l[7] >>= c;
-            int32_t d = (int32_t)raw;
-            if (raw >= D + (ng ? 1u : 0u)) { d -= (int32_t)(1u << c); carry = 1; } else carry = 0;
-            if (ng) d = -d;
+            const int32_t d = signed_digit_step(s, (uint32_t)a.c, carry, ng);
             if (j >= win0) { const int i = j - win0; w[i >> 1] |= ((uint32_t)d & 0xFFFFu) << (16 * (i & 1)); }
         }
         a.digits[o * a.batch + p] = make_uint4(w[0], w[1], w[2], w[3]);
@@ -211,37 +179,10 @@ __global__ __launch_bounds__(64) void k_recode_flat_few(MsmFlatRecodeArgs a) {
 }
 
 // ---- gather-accumulate -------------------------------------------------------------------------------------------------------
-template <class F> struct RawAff { fe w[2 * F::WORDS]; };
-template <class F> __device__ __forceinline__ RawAff<F> load_raw(const fe* p) {
-    RawAff<F> r;
-#pragma unroll
-    for (int i = 0; i < 2 * F::WORDS; i++) r.w[i] = load_fe(p + i);
-    return r;
-}
-__device__ __forceinline__ Aff9<Fp29f> unpack_aff(const RawAff<Fp29f>& r, bool negate) {
-    Aff9<Fp29f> e{Fp29::unpack(r.w[0]), Fp29::unpack(r.w[1])};
-    if (negate) e.y = Fp29::neg(e.y);                      // signed-tight: fine as a product operand
-    return e;
-}
-__device__ __forceinline__ Aff9<Fp2x> unpack_aff(const RawAff<Fp2x>& r, bool negate) {
-    Aff9<Fp2x> e{fe9x2{Fp29::unpack(r.w[0]), Fp29::unpack(r.w[1])}, fe9x2{Fp29::unpack(r.w[2]), Fp29::unpack(r.w[3])}};
-    if (negate) e.y = Fp2x::neg(e.y);
-    return e;
-}
-
 // Bases [k0, k1) of window j for one proof (lane).  EXACT = false is the hot path (no degenerate-case tests inside madd).
 // Software pipelining: the digits of the NEXT octet of bases and the table entry of the NEXT base are requested before the
 // current mixed addition (~2 300 instructions) starts, so neither the coalesced digit stream nor the 64-byte random gathers
 // are on the critical path.  Uniform rows: entry d - 1 of base k is table[k * D + d - 1].
-// digit i (wave-uniform i) of an octet: eight int16 in one 16-byte word, or (WIDE) eight int32 in two
-template <bool WIDE> __device__ __forceinline__ int32_t octet_digit(const uint4& w0, const uint4& w1, uint32_t i) {
-    if (WIDE) {
-        const uint4& w = (i & 4) ? w1 : w0;
-        return (int32_t)((i & 2) ? ((i & 1) ? w.w : w.z) : ((i & 1) ? w.y : w.x));
-    }
-    const uint64_t lo = (uint64_t)w0.x | ((uint64_t)w0.y << 32), hi = (uint64_t)w0.z | ((uint64_t)w0.w << 32);
-    return (int32_t)(int16_t)(uint16_t)(((i & 4) ? hi : lo) >> (16 * (i & 3)));
-}
 template <class F, bool EXACT, bool WIDE>
 __device__ __forceinline__ Xyzz9<F> accumulate_window(const MsmWinArgs& a, size_t k0, size_t k1, uint32_t j, size_t p) {
     using C = Curve9<F>;
@@ -259,7 +200,7 @@ __device__ __forceinline__ Xyzz9<F> accumulate_window(const MsmWinArgs& a, size_
         const uint32_t lim = k1 - kk < 8 ? (uint32_t)(k1 - kk) : 8u;
 #pragma unroll 1
         for (uint32_t i = 0; i < lim; i++) {
-            const int32_t d = octet_digit<WIDE>(cur, cur1, i);
+            const int32_t d = octet_slot<WIDE>(cur, cur1, i);
             // The gather is unconditional (a zero digit fetches entry 0 and drops it): a load inside a branch would have to be
             // waited for at the join, i.e. before the addition it is meant to overlap with.
             const int32_t mag = d < 0 ? -d : d;
@@ -278,22 +219,18 @@ __device__ __forceinline__ Xyzz9<F> accumulate_window(const MsmWinArgs& a, size_
 template <class F, bool WIDE>
 __global__ __launch_bounds__(64, F::WORDS == 1 ? 3 : 1) void k_msm_win(MsmWinArgs a) {      // G1: three waves per SIMD (<= 168 VGPRs); measured in round 3: four (128 VGPRs, 34 spilled) 272.3 ms, two 272.9 ms — the same
     using C = Curve9<F>;
-    // XCD-aware order: workgroups go round-robin over the 8 XCDs by linear id and each XCD has its own L2.  Every wave of a slice
-    // (all windows, all groups of proofs) gathers from the same table rows, so a slice is placed on ONE XCD (consecutive ids there).
-    const size_t G = a.batch / 64, GW = G * (size_t)a.nwin, L = blockIdx.x, S8 = a.nslices & ~(size_t)7;
+    const size_t G = a.batch / 64;
     // clock stamps: eight waves spread over the launch (at 1/16, 3/16, ... of the grid), the k-th shifted by k workgroups so that each lands on another
     // XCD (workgroups go round-robin over the XCDs, which are clocked separately), each record {100 MHz clock, shader clock} at their start and end
     const uint32_t eighth = gridDim.x / 8, k8 = eighth ? blockIdx.x / eighth : 8u;
     const bool stamp = a.clk && eighth >= 16 && threadIdx.x == 0 && k8 < 8 && blockIdx.x % eighth == eighth / 2 + k8;
     unsigned long long* const clk = a.clk + (stamp ? 4 * k8 : 0);
     if (stamp) { clk[0] = wall_clock64(); clk[1] = clock64(); }
-    size_t slice, rem;
-    if (L < S8 * GW) { const size_t xcd = L & 7, i = L >> 3; slice = (i / GW) * 8 + xcd; rem = i % GW; }
-    else { slice = L / GW; rem = L % GW; }
+    const auto [slice, rem] = xcd_slice(blockIdx.x, a.nslices, G * (size_t)a.nwin);      // all windows and all groups of proofs of a slice on one XCD
     // consecutive workgroups of a slice: same window, consecutive groups of proofs
     const uint32_t j = (uint32_t)(rem / G);
     const size_t p = (rem % G) * 64 + threadIdx.x;
-    const size_t k0 = slice * a.per < a.nbases ? slice * a.per : a.nbases, k1 = k0 + a.per < a.nbases ? k0 + a.per : a.nbases;
+    const auto [k0, k1] = slice_bounds(slice, a.per, a.nbases);
     Xyzz9<F> acc = C::infinity();
     if (k0 < k1) {
         acc = accumulate_window<F, false, WIDE>(a, k0, k1, j, p);
@@ -309,19 +246,12 @@ __global__ __launch_bounds__(64, F::WORDS == 1 ? 3 : 1) void k_msm_win(MsmWinArg
 // here lanes are BASES: every lane fetches the entry of its own (base, window) for ONE proof, lanes add up 64-base chunks of the
 // slice independently and a __shfl_xor butterfly of six exact additions folds the wave.  Same partial sums, ~10x less work for
 // one proof; the crossover with the batch kernel is around ten proofs.  grid: (nslices * nwin, nproofs).
-__device__ __forceinline__ fe9 shfl_xor_e(const fe9& v, int m) {
-    fe9 r;
-#pragma unroll
-    for (int i = 0; i < 9; i++) r.l[i] = __shfl_xor(v.l[i], m);
-    return r;
-}
-__device__ __forceinline__ fe9x2 shfl_xor_e(const fe9x2& v, int m) { return fe9x2{shfl_xor_e(v.a0, m), shfl_xor_e(v.a1, m)}; }
 template <class F>
 __global__ __launch_bounds__(64) void k_msm_win_few(MsmWinArgs a) {
     using C = Curve9<F>;
     const size_t slice = blockIdx.x / (uint32_t)a.nwin, p = blockIdx.y, noct = (a.nbases + 7) / 8, D = (size_t)1 << (a.c - 1);
     const uint32_t j = blockIdx.x % (uint32_t)a.nwin, lane = threadIdx.x;
-    const size_t k0 = slice * a.per < a.nbases ? slice * a.per : a.nbases, k1 = k0 + a.per < a.nbases ? k0 + a.per : a.nbases;
+    const auto [k0, k1] = slice_bounds(slice, a.per, a.nbases);
     const fe* table = reinterpret_cast<const fe*>(a.table);
     Xyzz9<F> acc = C::infinity();
     for (size_t kb = k0; kb < k1; kb += 64) {
@@ -330,8 +260,8 @@ __global__ __launch_bounds__(64) void k_msm_win_few(MsmWinArgs a) {
             const size_t at = ((size_t)j * noct + k / 8) * a.batch + p;
             const uint32_t s = (uint32_t)(k & 7);
             int32_t d;
-            if (a.c > 16) { const uint4 w = a.digits[2 * at + (s >> 2)]; d = (int32_t)((s & 2) ? ((s & 1) ? w.w : w.z) : ((s & 1) ? w.y : w.x)); }      // wide digits (k_recode)
-            else { const uint4 w = a.digits[at]; const uint32_t word = s < 2 ? w.x : s < 4 ? w.y : s < 6 ? w.z : w.w; d = (int32_t)(int16_t)(uint16_t)(word >> (16 * (s & 1))); }
+            if (a.c > 16) { const uint4 w = a.digits[2 * at + (s >> 2)]; d = octet_slot<true>(w, w, s & 3); }      // wide digits (k_recode): the half that holds slot s
+            else { const uint4 w = a.digits[at]; d = octet_slot<false>(w, w, s); }
             if (d) {
                 const int32_t mag = d < 0 ? -d : d;
                 const Aff9<F> e = unpack_aff(load_raw<F>(table + (k * D + (size_t)(mag - 1)) * (2 * F::WORDS)), d < 0);
@@ -340,12 +270,7 @@ __global__ __launch_bounds__(64) void k_msm_win_few(MsmWinArgs a) {
             }
         }
     }
-    for (int m = 32; m >= 1; m >>= 1) {
-        Xyzz9<F> o;
-        o.x = shfl_xor_e(acc.x, m); o.y = shfl_xor_e(acc.y, m); o.zz = shfl_xor_e(acc.zz, m); o.zzz = shfl_xor_e(acc.zzz, m);
-        o.inf = __shfl_xor((int)acc.inf, m) != 0;
-        acc = C::add(acc, o);
-    }
+    acc = wave_sum(acc);
     if (lane == 0) C::store_xyzz(reinterpret_cast<fe*>(a.partial) + ((slice * a.nwin + j) * a.batch + p) * (4 * F::WORDS), acc);
 }
 
@@ -379,11 +304,10 @@ __device__ __forceinline__ Xyzz9<F> accumulate_flat(const MsmFlatArgs& a, size_t
         const uint32_t c_lo = roff_lo, c_hi = roff_hi, c_len = rlen;
         if (o + 1 < o1) { nxt = *dig; load_rows(o + 1); }
         const bool grp = o < nbit8 && ((okmask >> (o - o0)) & 1);                                   // wave-uniform
-        const uint64_t lo = (uint64_t)cur.x | ((uint64_t)cur.y << 32), hi = (uint64_t)cur.z | ((uint64_t)cur.w << 32);
         const uint32_t lim = grp ? 1u : (k1 - 8 * o < 8 ? (uint32_t)(k1 - 8 * o) : 8u);
 #pragma unroll 1
         for (uint32_t i = 0; i < lim; i++) {
-            int32_t d = (int32_t)(int16_t)(uint16_t)(((i & 4) ? hi : lo) >> (16 * (i & 3)));
+            int32_t d = octet_slot<false>(cur, cur, i);
             int32_t mag = d < 0 ? -d : d;
             const fe* src;
             if (grp) src = sub + (o * MSM_GROUP_ENTRIES + (size_t)(mag ? mag - 1 : 0)) * (2 * F::WORDS);
@@ -392,22 +316,7 @@ __device__ __forceinline__ Xyzz9<F> accumulate_flat(const MsmFlatArgs& a, size_t
                 const uint32_t len = (uint32_t)__builtin_amdgcn_readlane((int)c_len, (int)i);
                 const bool beyond = (uint32_t)mag > len;                                            // MSM_FLAT_ESCAPE has magnitude 32768 > any flat row
                 if (__any(beyond)) {                                                                // wrong prediction: rare, slow, exact
-                    if (beyond) {
-                        fe sc = fe{}; bool sneg = d < 0;
-                        if (d == MSM_FLAT_ESCAPE) { sc = Fr::from_mont(load_fe(a.scalars + (size_t)a.rows[8 * o + i] * a.batch + p)); sneg = sign_normalise(sc); }
-                        else sc.l[0] = (uint32_t)mag;
-                        const Aff9<F> P1 = unpack_aff(load_raw<F>(table + off * (2 * F::WORDS)), sneg);
-                        Xyzz9<F> Q = C::infinity();
-                        for (int b = 253; b >= 0; b--) {
-                            if (!Q.inf) Q = C::dbl(Q);
-                            uint32_t word = sc.l[0];
-#pragma unroll
-                            for (int q = 1; q < 8; q++) word = (b >> 5) == q ? sc.l[q] : word;
-                            if ((word >> (b & 31)) & 1u) Q = C::template madd<true>(Q, P1);
-                        }
-                        acc = C::add(acc, Q);
-                        d = 0; mag = 0;
-                    }
+                    if (beyond) { acc = C::add(acc, mul_out<F>(d, table + off * (2 * F::WORDS), a.scalars, a.rows, 8 * o + i, a.batch, p)); d = 0; mag = 0; }
                 }
                 src = table + (off + (size_t)(mag ? mag - 1 : 0)) * (2 * F::WORDS);
             }
@@ -425,12 +334,9 @@ __device__ __forceinline__ Xyzz9<F> accumulate_flat(const MsmFlatArgs& a, size_t
 template <class F>
 __global__ __launch_bounds__(64, F::WORDS == 1 ? 2 : 1) void k_msm_flat(MsmFlatArgs a) {
     using C = Curve9<F>;
-    const size_t G = a.batch / 64, L = blockIdx.x, S8 = a.nslices & ~(size_t)7;
-    size_t slice, g;                                        // all groups of proofs of a slice on one XCD (see k_msm_win)
-    if (L < S8 * G) { const size_t xcd = L & 7, i = L >> 3; slice = (i / G) * 8 + xcd; g = i % G; }
-    else { slice = L / G; g = L % G; }
+    const auto [slice, g] = xcd_slice(blockIdx.x, a.nslices, a.batch / 64);      // all groups of proofs of a slice on one XCD
     const size_t p = g * 64 + threadIdx.x;
-    const size_t k0 = slice * a.per < a.nbases ? slice * a.per : a.nbases, k1 = k0 + a.per < a.nbases ? k0 + a.per : a.nbases;
+    const auto [k0, k1] = slice_bounds(slice, a.per, a.nbases);
     Xyzz9<F> acc = C::infinity();
     if (k0 < k1) {
         acc = accumulate_flat<F, false>(a, k0, k1, g, p);
@@ -455,30 +361,17 @@ __global__ __launch_bounds__(64) void k_msm_flat_few(MsmFlatArgs a) {
     if (o < noct) {
         const uint4 w = a.digits[o * a.batch + p];
         const bool grp = o < nbit8 && a.gok[o * MSM_FEW_PROOFS + p] != 0;
-        const uint64_t lo = (uint64_t)w.x | ((uint64_t)w.y << 32), hi = (uint64_t)w.z | ((uint64_t)w.w << 32);
         const uint32_t lim = grp ? 1u : (a.nbases - 8 * o < 8 ? (uint32_t)(a.nbases - 8 * o) : 8u);
 #pragma unroll 1
         for (uint32_t i = 0; i < lim; i++) {
-            int32_t d = (int32_t)(int16_t)(uint16_t)(((i & 4) ? hi : lo) >> (16 * (i & 3)));
+            int32_t d = octet_slot<false>(w, w, i);
             int32_t mag = d < 0 ? -d : d;
             const fe* src;
             if (grp) src = sub + (o * MSM_GROUP_ENTRIES + (size_t)(mag ? mag - 1 : 0)) * (2 * F::WORDS);
             else {
                 const uint64_t off = a.rowoff[8 * o + i];
                 if ((uint32_t)mag > a.rowlen[8 * o + i]) {                 // wrong prediction (MSM_FLAT_ESCAPE has magnitude 32768 > any flat row): rare, slow, exact
-                    fe sc = fe{}; bool sneg = d < 0;
-                    if (d == MSM_FLAT_ESCAPE) { sc = Fr::from_mont(load_fe(a.scalars + (size_t)a.rows[8 * o + i] * a.batch + p)); sneg = sign_normalise(sc); }
-                    else sc.l[0] = (uint32_t)mag;
-                    const Aff9<F> P1 = unpack_aff(load_raw<F>(table + off * (2 * F::WORDS)), sneg);
-                    Xyzz9<F> Q = C::infinity();
-                    for (int b = 253; b >= 0; b--) {
-                        if (!Q.inf) Q = C::dbl(Q);
-                        uint32_t word = sc.l[0];
-#pragma unroll
-                        for (int q = 1; q < 8; q++) word = (b >> 5) == q ? sc.l[q] : word;
-                        if ((word >> (b & 31)) & 1u) Q = C::template madd<true>(Q, P1);
-                    }
-                    acc = C::add(acc, Q);
+                    acc = C::add(acc, mul_out<F>(d, table + off * (2 * F::WORDS), a.scalars, a.rows, 8 * o + i, a.batch, p));
                     d = 0; mag = 0;
                 }
                 src = table + (off + (size_t)(mag ? mag - 1 : 0)) * (2 * F::WORDS);
@@ -487,12 +380,7 @@ __global__ __launch_bounds__(64) void k_msm_flat_few(MsmFlatArgs a) {
             if (d) acc = C::template madd<true>(acc, unpack_aff(e, d < 0));
         }
     }
-    for (int m = 32; m >= 1; m >>= 1) {
-        Xyzz9<F> q;
-        q.x = shfl_xor_e(acc.x, m); q.y = shfl_xor_e(acc.y, m); q.zz = shfl_xor_e(acc.zz, m); q.zzz = shfl_xor_e(acc.zzz, m);
-        q.inf = __shfl_xor((int)acc.inf, m) != 0;
-        acc = C::add(acc, q);
-    }
+    acc = wave_sum(acc);
     if (threadIdx.x == 0) C::store_xyzz(reinterpret_cast<fe*>(a.partial) + ((size_t)blockIdx.x * a.batch + p) * (4 * F::WORDS), acc);
 }
 
@@ -591,16 +479,11 @@ __global__ __launch_bounds__(64) void k_fixed_mul(const fe* table, int c, int nw
     const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
     if (i >= n) return;
     fe s = load_fe(scalars + i);
-    const uint32_t cmask = (1u << c) - 1, D = 1u << (c - 1);
+    const uint32_t D = 1u << (c - 1);
     uint32_t carry = 0;
     Xyzz9<F> acc = C::infinity();
     for (int j = 0; j < nwin; j++) {
-        uint32_t raw = (s.l[0] & cmask) + carry;
-#pragma unroll
-        for (int q = 0; q < 7; q++) s.l[q] = __builtin_amdgcn_alignbit(s.l[q + 1], s.l[q], c);
-        s.l[7] >>= c;
-        int32_t d = (int32_t)raw;
-        if (raw >= D) { d -= (int32_t)(1u << c); carry = 1; } else carry = 0;
+        const int32_t d = signed_digit_step(s, (uint32_t)c, carry, false);
         if (d) {
             const int32_t mag = d < 0 ? -d : d;
             acc = C::template madd<true>(acc, unpack_aff(load_raw<F>(table + ((size_t)j * D + (size_t)(mag - 1)) * (2 * F::WORDS)), d < 0));
@@ -613,12 +496,12 @@ __global__ __launch_bounds__(64) void k_fixed_mul(const fe* table, int c, int nw
 
 }  // namespace
 
-void launch_fixed_mul_g1(const G1Aff* table, int c, int nwin, const fe* scalars, size_t n, fe* out, uint8_t* inf, hipStream_t s) {
-    if (n) hipLaunchKernelGGL(k_fixed_mul<Fp29f>, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, reinterpret_cast<const fe*>(table), c, nwin, scalars, n, out, inf);
+template <class AffT>
+static void fixed_mul(const AffT* table, int c, int nwin, const fe* scalars, size_t n, fe* out, uint8_t* inf, hipStream_t s) {
+    if (n) hipLaunchKernelGGL(k_fixed_mul<typename GroupOf<AffT>::F>, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, reinterpret_cast<const fe*>(table), c, nwin, scalars, n, out, inf);
 }
-void launch_fixed_mul_g2(const G2Aff* table, int c, int nwin, const fe* scalars, size_t n, fe* out, uint8_t* inf, hipStream_t s) {
-    if (n) hipLaunchKernelGGL(k_fixed_mul<Fp2x>, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, reinterpret_cast<const fe*>(table), c, nwin, scalars, n, out, inf);
-}
+void launch_fixed_mul(const G1Aff* table, int c, int nwin, const fe* scalars, size_t n, fe* out, uint8_t* inf, hipStream_t s) { fixed_mul(table, c, nwin, scalars, n, out, inf, s); }
+void launch_fixed_mul(const G2Aff* table, int c, int nwin, const fe* scalars, size_t n, fe* out, uint8_t* inf, hipStream_t s) { fixed_mul(table, c, nwin, scalars, n, out, inf, s); }
 void launch_msm_recode(const MsmRecodeArgs& a, hipStream_t s) {
     if (!a.nbases) return;
     const dim3 grid((unsigned)(a.batch / 64), (unsigned)((a.nbases + 7) / 8));
@@ -629,42 +512,52 @@ void launch_msm_recode(const MsmRecodeArgs& a, hipStream_t s) {
 void launch_msm_recode_flat_few(const MsmFlatRecodeArgs& a, size_t nproofs, hipStream_t s) {
     if (a.nbases) hipLaunchKernelGGL(k_recode_flat_few, dim3((unsigned)(((a.nbases + 7) / 8 + 63) / 64), (unsigned)nproofs), dim3(64), 0, s, a);
 }
-void launch_msm_flat_few_g1(const MsmFlatArgs& a, size_t nproofs, hipStream_t s) { hipLaunchKernelGGL(k_msm_flat_few<Fp29f>, dim3((unsigned)a.nslices, (unsigned)nproofs), dim3(64), 0, s, a); }
-void launch_msm_flat_few_g2(const MsmFlatArgs& a, size_t nproofs, hipStream_t s) { hipLaunchKernelGGL(k_msm_flat_few<Fp2x>, dim3((unsigned)a.nslices, (unsigned)nproofs), dim3(64), 0, s, a); }
 void launch_msm_recode_flat(const MsmFlatRecodeArgs& a, hipStream_t s) {
     if (a.nbases) hipLaunchKernelGGL(k_recode_flat, dim3((unsigned)(a.batch / 64), (unsigned)((a.nbases + 7) / 8)), dim3(64), 0, s, a);
 }
-void launch_msm_win_g1(const MsmWinArgs& a, hipStream_t s) {
+template <class AffT> void launch_msm_flat_few(const MsmFlatArgs& a, size_t nproofs, hipStream_t s) {
+    hipLaunchKernelGGL(k_msm_flat_few<typename GroupOf<AffT>::F>, dim3((unsigned)a.nslices, (unsigned)nproofs), dim3(64), 0, s, a);
+}
+template <class AffT> void launch_msm_win(const MsmWinArgs& a, hipStream_t s) {
+    using F = typename GroupOf<AffT>::F;
     const dim3 grid((unsigned)(a.nslices * a.nwin * (a.batch / 64)));
-    if (a.c > 16) hipLaunchKernelGGL((k_msm_win<Fp29f, true>), grid, dim3(64), 0, s, a); else hipLaunchKernelGGL((k_msm_win<Fp29f, false>), grid, dim3(64), 0, s, a);
+    if (a.c > 16) hipLaunchKernelGGL((k_msm_win<F, true>), grid, dim3(64), 0, s, a); else hipLaunchKernelGGL((k_msm_win<F, false>), grid, dim3(64), 0, s, a);
 }
-void launch_msm_win_g2(const MsmWinArgs& a, hipStream_t s) {
-    const dim3 grid((unsigned)(a.nslices * a.nwin * (a.batch / 64)));
-    if (a.c > 16) hipLaunchKernelGGL((k_msm_win<Fp2x, true>), grid, dim3(64), 0, s, a); else hipLaunchKernelGGL((k_msm_win<Fp2x, false>), grid, dim3(64), 0, s, a);
+template <class AffT> void launch_msm_win_few(const MsmWinArgs& a, size_t nproofs, hipStream_t s) {
+    hipLaunchKernelGGL(k_msm_win_few<typename GroupOf<AffT>::F>, dim3((unsigned)(a.nslices * a.nwin), (unsigned)nproofs), dim3(64), 0, s, a);
 }
-void launch_msm_win_few_g1(const MsmWinArgs& a, size_t nproofs, hipStream_t s) { hipLaunchKernelGGL(k_msm_win_few<Fp29f>, dim3((unsigned)(a.nslices * a.nwin), (unsigned)nproofs), dim3(64), 0, s, a); }
-void launch_msm_win_few_g2(const MsmWinArgs& a, size_t nproofs, hipStream_t s) { hipLaunchKernelGGL(k_msm_win_few<Fp2x>, dim3((unsigned)(a.nslices * a.nwin), (unsigned)nproofs), dim3(64), 0, s, a); }
-void launch_msm_flat_g1(const MsmFlatArgs& a, hipStream_t s) { hipLaunchKernelGGL(k_msm_flat<Fp29f>, dim3((unsigned)(a.nslices * (a.batch / 64))), dim3(64), 0, s, a); }
-void launch_msm_flat_g2(const MsmFlatArgs& a, hipStream_t s) { hipLaunchKernelGGL(k_msm_flat<Fp2x>, dim3((unsigned)(a.nslices * (a.batch / 64))), dim3(64), 0, s, a); }
-void launch_msm_horner_g1(const MsmHornerJobs& jobs, size_t batch, hipStream_t s) {
-    if (jobs.n) hipLaunchKernelGGL(k_msm_horner<Fp29f>, dim3((unsigned)(batch / 64), (unsigned)jobs.n), dim3(64), 0, s, jobs, batch);
+template <class AffT> void launch_msm_flat(const MsmFlatArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(k_msm_flat<typename GroupOf<AffT>::F>, dim3((unsigned)(a.nslices * (a.batch / 64))), dim3(64), 0, s, a);
 }
-void launch_msm_horner_g2(const MsmHornerJobs& jobs, size_t batch, hipStream_t s) {
-    if (jobs.n) hipLaunchKernelGGL(k_msm_horner<Fp2x>, dim3((unsigned)(batch / 64), (unsigned)jobs.n), dim3(64), 0, s, jobs, batch);
+template <class AffT> void launch_msm_horner(const MsmHornerJobs& jobs, size_t batch, hipStream_t s) {
+    if (jobs.n) hipLaunchKernelGGL(k_msm_horner<typename GroupOf<AffT>::F>, dim3((unsigned)(batch / 64), (unsigned)jobs.n), dim3(64), 0, s, jobs, batch);
 }
-void launch_build_rows_g1(const G1Aff* bases, const MsmRowSeg* segs, size_t nsegs, uint32_t cap, G1Aff* table, G1Xyzz* scratch, hipStream_t s) {
-    if (nsegs) hipLaunchKernelGGL((k_build_rows<Fp29f, Fp>), dim3((unsigned)((nsegs + 63) / 64)), dim3(64), 0, s,
-                                  reinterpret_cast<const Aff<Fp>*>(bases), segs, nsegs, cap, reinterpret_cast<fe*>(table), reinterpret_cast<fe*>(scratch));
+template void launch_msm_flat<G1Aff>(const MsmFlatArgs&, hipStream_t);
+template void launch_msm_flat<G2Aff>(const MsmFlatArgs&, hipStream_t);
+template void launch_msm_flat_few<G1Aff>(const MsmFlatArgs&, size_t, hipStream_t);
+template void launch_msm_flat_few<G2Aff>(const MsmFlatArgs&, size_t, hipStream_t);
+template void launch_msm_win<G1Aff>(const MsmWinArgs&, hipStream_t);
+template void launch_msm_win<G2Aff>(const MsmWinArgs&, hipStream_t);
+template void launch_msm_win_few<G1Aff>(const MsmWinArgs&, size_t, hipStream_t);
+template void launch_msm_win_few<G2Aff>(const MsmWinArgs&, size_t, hipStream_t);
+template void launch_msm_horner<G1Aff>(const MsmHornerJobs&, size_t, hipStream_t);
+template void launch_msm_horner<G2Aff>(const MsmHornerJobs&, size_t, hipStream_t);
+
+template <class AffT, class XyzzT>
+static void build_rows(const AffT* bases, const MsmRowSeg* segs, size_t nsegs, uint32_t cap, AffT* table, XyzzT* scratch, hipStream_t s) {
+    using G = GroupOf<AffT>;
+    if (nsegs) hipLaunchKernelGGL((k_build_rows<typename G::F, typename G::Old>), dim3((unsigned)((nsegs + 63) / 64)), dim3(64), 0, s,
+                                  reinterpret_cast<const Aff<typename G::Old>*>(bases), segs, nsegs, cap, reinterpret_cast<fe*>(table), reinterpret_cast<fe*>(scratch));
 }
-void launch_build_rows_g2(const G2Aff* bases, const MsmRowSeg* segs, size_t nsegs, uint32_t cap, G2Aff* table, G2Xyzz* scratch, hipStream_t s) {
-    if (nsegs) hipLaunchKernelGGL((k_build_rows<Fp2x, Fp2>), dim3((unsigned)((nsegs + 63) / 64)), dim3(64), 0, s,
-                                  reinterpret_cast<const Aff<Fp2>*>(bases), segs, nsegs, cap, reinterpret_cast<fe*>(table), reinterpret_cast<fe*>(scratch));
+void launch_build_rows(const G1Aff* bases, const MsmRowSeg* segs, size_t nsegs, uint32_t cap, G1Aff* table, G1Xyzz* scratch, hipStream_t s) { build_rows(bases, segs, nsegs, cap, table, scratch, s); }
+void launch_build_rows(const G2Aff* bases, const MsmRowSeg* segs, size_t nsegs, uint32_t cap, G2Aff* table, G2Xyzz* scratch, hipStream_t s) { build_rows(bases, segs, nsegs, cap, table, scratch, s); }
+template <class AffT>
+static void shift_bases(const AffT* in, const uint32_t* src, const uint32_t* shift, size_t n, AffT* out, hipStream_t s) {
+    using G = GroupOf<AffT>;
+    if (n) hipLaunchKernelGGL((k_shift_bases<typename G::F, typename G::Old>), dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s,
+                              reinterpret_cast<const Aff<typename G::Old>*>(in), src, shift, n, reinterpret_cast<Aff<typename G::Old>*>(out));
 }
-void launch_shift_bases_g1(const G1Aff* in, const uint32_t* src, const uint32_t* shift, size_t n, G1Aff* out, hipStream_t s) {
-    if (n) hipLaunchKernelGGL((k_shift_bases<Fp29f, Fp>), dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, reinterpret_cast<const Aff<Fp>*>(in), src, shift, n, reinterpret_cast<Aff<Fp>*>(out));
-}
-void launch_shift_bases_g2(const G2Aff* in, const uint32_t* src, const uint32_t* shift, size_t n, G2Aff* out, hipStream_t s) {
-    if (n) hipLaunchKernelGGL((k_shift_bases<Fp2x, Fp2>), dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, reinterpret_cast<const Aff<Fp2>*>(in), src, shift, n, reinterpret_cast<Aff<Fp2>*>(out));
-}
+void launch_shift_bases(const G1Aff* in, const uint32_t* src, const uint32_t* shift, size_t n, G1Aff* out, hipStream_t s) { shift_bases(in, src, shift, n, out, s); }
+void launch_shift_bases(const G2Aff* in, const uint32_t* src, const uint32_t* shift, size_t n, G2Aff* out, hipStream_t s) { shift_bases(in, src, shift, n, out, s); }
 
 }  // namespace gsc

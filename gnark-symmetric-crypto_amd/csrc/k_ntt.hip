@@ -28,8 +28,7 @@
 //     pairs whose twiddle is 1 for every thread cost no product);
 //   * K3 runs its last two forward stages in registers straight into the pointwise product, canonicalises with three conditional subtractions and takes
 //     the digits of the bench configuration's width (c = 17) at compile-time bit offsets.
-#include "kernels.hpp"
-#include "bn254_fp29.hpp"
+#include "msm_dev.hpp"
 
 namespace gsc {
 using namespace bn254;
@@ -432,9 +431,10 @@ __global__ __launch_bounds__(512) void k_ntt_pointwise_strided(NttPlan pl, fe* v
     if (EVAL == 2) {
         fe s[4] = {F::pack(F::freeze_near(lo0)), F::pack(F::freeze_near(lo1)), F::pack(F::freeze_near(hi0)), F::pack(F::freeze_near(hi1))};      // elements u4 + {0, 1, 2, 3} * G/4; a*b in (-1.4 r, 2.4 r)
         const size_t mq = (size_t)g * (G / 4) + u4, o = mq >> 1, half = mq & 1, noct = ((size_t)1 << L) / 8, p = q0 + q;
-        const uint32_t c = (uint32_t)qd.c, cmask = (1u << c) - 1, D = 1u << (c - 1);
+        const uint32_t c = (uint32_t)qd.c;
         uint32_t carry = 0;
         if (c == 17 && qd.nwin == 15) {      // the bench configuration's digit width: window j sits at a compile-time bit offset — one funnel shift instead of shifting the whole scalar down every window
+            // (a measured specialisation; its digits must equal signed_digit_step's, msm_dev.hpp)
 #pragma unroll
             for (int j = 0; j < 15; j++) {
                 uint32_t w[4];
@@ -457,13 +457,9 @@ __global__ __launch_bounds__(512) void k_ntt_pointwise_strided(NttPlan pl, fe* v
             uint32_t w[4];
 #pragma unroll
             for (int i = 0; i < 4; i++) {
-                const uint32_t raw = (s[i].l[0] & cmask) + ((carry >> i) & 1u);
-#pragma unroll
-                for (int k = 0; k < 7; k++) s[i].l[k] = __builtin_amdgcn_alignbit(s[i].l[k + 1], s[i].l[k], c);
-                s[i].l[7] >>= c;
-                int32_t dg = (int32_t)raw;
-                if (raw >= D) { dg -= (int32_t)(1u << c); carry |= 1u << i; } else carry &= ~(1u << i);
-                w[i] = (uint32_t)dg;
+                uint32_t cb = (carry >> i) & 1u;
+                w[i] = (uint32_t)signed_digit_step(s[i], c, cb, false);
+                carry = cb ? carry | (1u << i) : carry & ~(1u << i);
             }
             const size_t at = ((size_t)j * noct + o) * batch + p;
             if (c > 16) qd.digits[2 * at + half] = make_uint4(w[0], w[1], w[2], w[3]);

@@ -142,7 +142,7 @@ hipError_t launch_compute_h(const NttPlan& p, fe* a, fe* b, fe* c, size_t m, siz
 // The quotient in EVALUATION form: only the four transforms of a and b; on return a[i] = A(zeta w^i) B(zeta w^i) * 2^261 mod r as a
 // canonical integer, natural order (b overwritten, c not touched): the scalars of the bases V_i of launch_quot_bases.
 hipError_t launch_compute_d(const NttPlan& p, fe* a, fe* b, size_t m, size_t batch, hipStream_t s, size_t ncols = 0, const NttNarrow* narrow = nullptr);
-// The same, but the last kernel recodes d itself: it writes the signed c-bit digits of the windowed MSM (launch_msm_win_g1's format, see
+// The same, but the last kernel recodes d itself: it writes the signed c-bit digits of the windowed MSM (launch_msm_win's format, see
 // launch_msm_recode) instead of d — no scalar vector in memory, no recoding pass.  A thread of that kernel holds d at four indices, which
 // become four consecutive bases: table position t of the MSM set belongs to the index quot_digit_index(L, t) (the engine lays the bases
 // V out in that order).  Whole batches only (ncols = 0).
@@ -162,6 +162,8 @@ void launch_quot_bases(const G1Aff* zfile, const uint8_t* zstatus, int L, int mo
                        fe* tw, G1Xyzz* scratch, const uint32_t* perm, G1Aff* out, uint8_t* status, hipStream_t s);
 
 // ---- multi-scalar multiplication (k_msm_win.hip, k_msm.hip) ----
+// Launchers are typed by group: overloads where the point pointers say which one is meant, templates on the affine point type (G1Aff, G2Aff;
+// instantiated next to the kernels) where the arguments are untyped.
 // Every MSM of the prover is a fixed-base sum over a set of the proving key (A, B1, B2, K, Z, commitment bases) for a batch of
 // independent proofs.  Each base has ONE table row of multiples, T_k[d - 1] = d * P_k (affine).  Two kernels (k_msm_win.hip):
 //   windowed: full-width scalars.  sum_k s_k P_k = sum_j 2^(c j) S_j,  S_j = sum_k sign(e_kj) T_k[|e_kj| - 1], signed c-bit digits
@@ -171,11 +173,11 @@ void launch_quot_bases(const G1Aff* zfile, const uint8_t* zstatus, int L, int mo
 //             subset sums.
 struct MsmRowSeg { uint32_t base, first, count, pad; uint64_t entry; };     // build work item: `count` multiples of base, from `first`, written at table entry `entry`
 // Builds the rows described by segs (each at most `cap` entries); scratch: nsegs * cap projective points.
-void launch_build_rows_g1(const G1Aff* bases, const MsmRowSeg* segs, size_t nsegs, uint32_t cap, G1Aff* table, G1Xyzz* scratch, hipStream_t s);
-void launch_build_rows_g2(const G2Aff* bases, const MsmRowSeg* segs, size_t nsegs, uint32_t cap, G2Aff* table, G2Xyzz* scratch, hipStream_t s);
+void launch_build_rows(const G1Aff* bases, const MsmRowSeg* segs, size_t nsegs, uint32_t cap, G1Aff* table, G1Xyzz* scratch, hipStream_t s);
+void launch_build_rows(const G2Aff* bases, const MsmRowSeg* segs, size_t nsegs, uint32_t cap, G2Aff* table, G2Xyzz* scratch, hipStream_t s);
 // out[i] = 2^shift[i] * in[src[i]]
-void launch_shift_bases_g1(const G1Aff* in, const uint32_t* src, const uint32_t* shift, size_t n, G1Aff* out, hipStream_t s);
-void launch_shift_bases_g2(const G2Aff* in, const uint32_t* src, const uint32_t* shift, size_t n, G2Aff* out, hipStream_t s);
+void launch_shift_bases(const G1Aff* in, const uint32_t* src, const uint32_t* shift, size_t n, G1Aff* out, hipStream_t s);
+void launch_shift_bases(const G2Aff* in, const uint32_t* src, const uint32_t* shift, size_t n, G2Aff* out, hipStream_t s);
 
 // Windowed sets.  Signed-digit recoding once per batch: digits[(j * noct + o) * batch + p] holds the eight int16 digits
 // e_{8o..8o+7, j} of proof p (noct = ceil(nbases / 8); bases beyond nbases get zero digits).  nwin = msm_windows(c).  c = 17 (MSM_MAX_WINDOW):
@@ -213,19 +215,16 @@ struct MsmWinArgs {
     // 2^bits entries — the L2 hit rate it would have with that many lanes per entry in flight.  0 = off.
     uint32_t exp_entry_mask = 0;
 };
-void launch_msm_win_g1(const MsmWinArgs& a, hipStream_t s);
-void launch_msm_win_g2(const MsmWinArgs& a, hipStream_t s);
+template <class AffT> void launch_msm_win(const MsmWinArgs& a, hipStream_t s);
 // The same partial sums for the first `nproofs` proofs only (columns nproofs .. batch-1 of `partial` are not written): lanes are bases
 // instead of proofs — the latency path of a single Prove call.  Worth it below MSM_FEW_PROOFS proofs.
 constexpr size_t MSM_FEW_PROOFS = 32;     // layout bound of the latency kernels; the engine's threshold is EngineConfig::few_max
-void launch_msm_win_few_g1(const MsmWinArgs& a, size_t nproofs, hipStream_t s);
-void launch_msm_win_few_g2(const MsmWinArgs& a, size_t nproofs, hipStream_t s);
+template <class AffT> void launch_msm_win_few(const MsmWinArgs& a, size_t nproofs, hipStream_t s);
 // out[p] = sum_j 2^(c j) S[j * batch + p] (+ addend[p] when addend != nullptr), for up to MSM_HORNER_JOBS independent sets in one launch
 constexpr int MSM_HORNER_JOBS = 6;
 struct MsmHornerJob { const void* S; const void* addend; void* out; int nwin, c; };
 struct MsmHornerJobs { MsmHornerJob job[MSM_HORNER_JOBS]; int n; };
-void launch_msm_horner_g1(const MsmHornerJobs& jobs, size_t batch, hipStream_t s);
-void launch_msm_horner_g2(const MsmHornerJobs& jobs, size_t batch, hipStream_t s);
+template <class AffT> void launch_msm_horner(const MsmHornerJobs& jobs, size_t batch, hipStream_t s);
 
 // Flat sets.  digits[o * batch + p] = eight int16 values of octet o for proof p (k_recode_flat):
 //   bit groups  the first nbit bases (a multiple of 8) are predicted to carry scalars in {-1, 0, 1} and are taken eight at a time:
@@ -240,8 +239,8 @@ void launch_msm_horner_g2(const MsmHornerJobs& jobs, size_t batch, hipStream_t s
 // rowlen or on the grouping.
 constexpr uint32_t MSM_GROUP_ENTRIES = 3280;      // (3^8 - 1) / 2
 constexpr int32_t MSM_FLAT_ESCAPE = -32768;
-void launch_build_subset_g1(const G1Aff* bases, size_t ngroups, G1Aff* table, G1Xyzz* scratch, uint8_t* ok, hipStream_t s);
-void launch_build_subset_g2(const G2Aff* bases, size_t ngroups, G2Aff* table, G2Xyzz* scratch, uint8_t* ok, hipStream_t s);
+void launch_build_subset(const G1Aff* bases, size_t ngroups, G1Aff* table, G1Xyzz* scratch, uint8_t* ok, hipStream_t s);
+void launch_build_subset(const G2Aff* bases, size_t ngroups, G2Aff* table, G2Xyzz* scratch, uint8_t* ok, hipStream_t s);
 struct MsmFlatRecodeArgs {
     const fe* scalars; const uint32_t* rows; const int32_t* octwin;   // Montgomery wire values [row][batch]; row per base; per octet first window or -1 (nullptr: none)
     size_t nbases, batch; int c;
@@ -253,7 +252,7 @@ struct MsmFlatRecodeArgs {
     const int8_t* plane = nullptr; size_t plane_rows = 0, plane_stride = 0;
 };
 void launch_msm_recode_flat(const MsmFlatRecodeArgs& a, hipStream_t s);
-// lanes = octets of one proof; gok[octet * MSM_FEW_PROOFS + proof]; pairs with launch_msm_flat_few_* (nslices = ceil(octets / 64))
+// lanes = octets of one proof; gok[octet * MSM_FEW_PROOFS + proof]; pairs with launch_msm_flat_few (nslices = ceil(octets / 64))
 void launch_msm_recode_flat_few(const MsmFlatRecodeArgs& a, size_t nproofs, hipStream_t s);
 // partial[slice * batch + p]; one wave per (slice of `per` consecutive bases, 64 proofs); per a multiple of 8, at most 512
 struct MsmFlatArgs {
@@ -264,10 +263,8 @@ struct MsmFlatArgs {
     size_t nbit; const void* sub; const uint8_t* gok;
     const fe* scalars; const uint32_t* rows;          // for escapes
 };
-void launch_msm_flat_g1(const MsmFlatArgs& a, hipStream_t s);
-void launch_msm_flat_g2(const MsmFlatArgs& a, hipStream_t s);
-void launch_msm_flat_few_g1(const MsmFlatArgs& a, size_t nproofs, hipStream_t s);
-void launch_msm_flat_few_g2(const MsmFlatArgs& a, size_t nproofs, hipStream_t s);
+template <class AffT> void launch_msm_flat(const MsmFlatArgs& a, hipStream_t s);
+template <class AffT> void launch_msm_flat_few(const MsmFlatArgs& a, size_t nproofs, hipStream_t s);
 
 // One reduction level over slices: out[g][column] = sum of the partials of group g of slices; returns the number of groups (1 = out
 // is the final sum).  `batch` counts independent columns (proofs, or windows x proofs).  Groups hold 64 slices (butterfly over
@@ -276,18 +273,18 @@ void launch_msm_flat_few_g2(const MsmFlatArgs& a, size_t nproofs, hipStream_t s)
 constexpr size_t MSM_REDUCE_FANIN = 32;
 inline bool msm_reduce_by_proof(size_t nslices, size_t batch) { return (batch / 64) * ((nslices + MSM_REDUCE_FANIN - 1) / MSM_REDUCE_FANIN) >= 128; }   // by-proof does 8x less work; the butterfly only wins when there are too few (proof group, chunk) waves
 inline size_t msm_reduce_groups(size_t nslices, size_t batch) { const size_t f = msm_reduce_by_proof(nslices, batch) ? MSM_REDUCE_FANIN : 64; return (nslices + f - 1) / f; }
-size_t launch_msm_reduce_g1(const G1Xyzz* partial, size_t nslices, size_t batch, G1Xyzz* out, hipStream_t s);
-size_t launch_msm_reduce_g2(const G2Xyzz* partial, size_t nslices, size_t batch, G2Xyzz* out, hipStream_t s);
+size_t launch_msm_reduce(const G1Xyzz* partial, size_t nslices, size_t batch, G1Xyzz* out, hipStream_t s);
+size_t launch_msm_reduce(const G2Xyzz* partial, size_t nslices, size_t batch, G2Xyzz* out, hipStream_t s);
 // calls with a handful of statements: `cols` columns in rows of `stride` (= the batch), only the first npr columns of every row are
 // summed (lanes = slices, 64 per wave); returns ceil(nslices / 64); `out` as above
-size_t launch_msm_reduce_few_g1(const G1Xyzz* partial, size_t nslices, size_t cols, size_t stride, size_t npr, G1Xyzz* out, hipStream_t s);
-size_t launch_msm_reduce_few_g2(const G2Xyzz* partial, size_t nslices, size_t cols, size_t stride, size_t npr, G2Xyzz* out, hipStream_t s);
+size_t launch_msm_reduce_few(const G1Xyzz* partial, size_t nslices, size_t cols, size_t stride, size_t npr, G1Xyzz* out, hipStream_t s);
+size_t launch_msm_reduce_few(const G2Xyzz* partial, size_t nslices, size_t cols, size_t stride, size_t npr, G2Xyzz* out, hipStream_t s);
 
 // Groth16 Setup: out[i] = scalars[i] * G for n independent canonical scalars (8 little-endian words each), from the window rows
 // table[j * D + d - 1] = d * 2^(c j) * G, D = 2^(c-1), nwin = msm_windows(c).  out: affine coordinates as canonical integers
 // (G1: x, y = 2 x 32 B; G2: x.a0, x.a1, y.a0, y.a1 = 4 x 32 B); inf[i] = 1 for a zero scalar.
-void launch_fixed_mul_g1(const G1Aff* table, int c, int nwin, const fe* scalars, size_t n, fe* out, uint8_t* inf, hipStream_t s);
-void launch_fixed_mul_g2(const G2Aff* table, int c, int nwin, const fe* scalars, size_t n, fe* out, uint8_t* inf, hipStream_t s);
+void launch_fixed_mul(const G1Aff* table, int c, int nwin, const fe* scalars, size_t n, fe* out, uint8_t* inf, hipStream_t s);
+void launch_fixed_mul(const G2Aff* table, int c, int nwin, const fe* scalars, size_t n, fe* out, uint8_t* inf, hipStream_t s);
 
 // Commitment helpers (AES-V2).  points: batch XYZZ sums -> out: batch x 64 B big-endian canonical X|Y
 // (gnark's uncompressed G1 encoding, the prefix of the commitment hash); flags[proof] |= bit if the point is infinity.

@@ -17,8 +17,8 @@ struct Buf {
     template <class T> T* as() const { return static_cast<T*>(p); }
 };
 
-template <class AffT, class XyzzT, class Shift, class Build, class Mul>
-void run(const uint8_t* gen_mont, const uint8_t* scalars_le, size_t n, uint8_t* out, uint8_t* inf, Shift shift, Build build, Mul mul) {
+template <class AffT, class XyzzT>
+void run(const uint8_t* gen_mont, const uint8_t* scalars_le, size_t n, uint8_t* out, uint8_t* inf) {
     constexpr int c = 16; const int nwin = msm_windows(c); const size_t D = (size_t)1 << (c - 1);
     hipStream_t s = nullptr;
     Buf gen(sizeof(AffT)), bases(sizeof(AffT) * nwin), d_src(4 * nwin), d_shift(4 * nwin), table(sizeof(AffT) * nwin * D);
@@ -26,17 +26,17 @@ void run(const uint8_t* gen_mont, const uint8_t* scalars_le, size_t n, uint8_t* 
     std::vector<uint32_t> src(nwin, 0u), sh(nwin);
     for (int j = 0; j < nwin; j++) sh[j] = (uint32_t)(c * j);
     HIP_CHECK(hipMemcpy(d_src.p, src.data(), 4 * nwin, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(d_shift.p, sh.data(), 4 * nwin, hipMemcpyHostToDevice));
-    shift(gen.as<AffT>(), d_src.as<uint32_t>(), d_shift.as<uint32_t>(), (size_t)nwin, bases.as<AffT>(), s);
+    launch_shift_bases(gen.as<AffT>(), d_src.as<uint32_t>(), d_shift.as<uint32_t>(), (size_t)nwin, bases.as<AffT>(), s);
     const uint32_t cap = 256;
     std::vector<MsmRowSeg> segs;
     for (int j = 0; j < nwin; j++) for (uint32_t f = 0; f < D; f += cap) segs.push_back(MsmRowSeg{(uint32_t)j, f + 1, cap, 0u, (uint64_t)j * D + f});
     Buf d_segs(sizeof(MsmRowSeg) * segs.size()), scratch(sizeof(XyzzT) * segs.size() * cap);
     HIP_CHECK(hipMemcpy(d_segs.p, segs.data(), sizeof(MsmRowSeg) * segs.size(), hipMemcpyHostToDevice));
-    build(bases.as<AffT>(), d_segs.as<MsmRowSeg>(), segs.size(), cap, table.as<AffT>(), scratch.as<XyzzT>(), s);
+    launch_build_rows(bases.as<AffT>(), d_segs.as<MsmRowSeg>(), segs.size(), cap, table.as<AffT>(), scratch.as<XyzzT>(), s);
     HIP_CHECK(hipGetLastError());
     Buf d_sc(32 * n, true), d_out(sizeof(AffT) * n), d_inf(n);      // the scalars are toxic waste in disguise: never left in freed device memory
     HIP_CHECK(hipMemcpy(d_sc.p, scalars_le, 32 * n, hipMemcpyHostToDevice));
-    mul(table.as<AffT>(), c, nwin, d_sc.as<fe>(), n, d_out.as<fe>(), d_inf.as<uint8_t>(), s);
+    launch_fixed_mul(table.as<AffT>(), c, nwin, d_sc.as<fe>(), n, d_out.as<fe>(), d_inf.as<uint8_t>(), s);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipDeviceSynchronize());
     HIP_CHECK(hipMemcpy(out, d_out.p, sizeof(AffT) * n, hipMemcpyDeviceToHost));
@@ -49,8 +49,8 @@ void setup_generator_muls(int device, bool g2, const uint8_t* gen_mont, const ui
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) throw std::runtime_error("no HIP device available: Setup computes its group elements on the GPU");
     HIP_CHECK(hipSetDevice(device));
     if (!n) return;
-    if (g2) run<G2Aff, G2Xyzz>(gen_mont, scalars_le, n, out, inf, launch_shift_bases_g2, launch_build_rows_g2, launch_fixed_mul_g2);
-    else run<G1Aff, G1Xyzz>(gen_mont, scalars_le, n, out, inf, launch_shift_bases_g1, launch_build_rows_g1, launch_fixed_mul_g1);
+    if (g2) run<G2Aff, G2Xyzz>(gen_mont, scalars_le, n, out, inf);
+    else run<G1Aff, G1Xyzz>(gen_mont, scalars_le, n, out, inf);
 }
 
 }  // namespace gsc

@@ -305,7 +305,9 @@ def test_latency_path_options_do_not_change_the_proofs(aes_keys, algo, counts):
         z, z2 = ("12", "3") if algo == 0 else ("5", "5")
         for extra in ({"GSC_FEW_Z_GB": z, "GSC_FEW_WIDE": "1"}, {"GSC_FEW_Z_GB": "0"}, {"GSC_FEW_Z_GB": z, "GSC_FEW_WGS": "17"},
                       {"GSC_FEW_SOLVER": "0", "GSC_FEW_Z_GB": z2, "GSC_FEW_WIDE": "1"}, {"GSC_FEW_MAX": "2", "GSC_FEW_Z_GB": z2},
-                      {"GSC_FEW_Z_GB": "0", "GSC_QUOTIENT_EVAL": "0"}):      # (without the latency layout such calls take the batch form of the quotient: both forms)
+                      {"GSC_FEW_Z_GB": "0", "GSC_QUOTIENT_EVAL": "0"},      # (without the latency layout such calls take the batch form of the quotient: both forms)
+                      # wrong predictions on the latency path: the flat latency kernel multiplies out escapes (every wire predicted a bit) and values beyond short rows
+                      {"GSC_BIT_GROUPS": "2"}) + (({"GSC_ROW_MARGIN_BITS": "-6"},) if algo else ()):
             assert _digest(dict(small, TEST_STATEMENTS=n, **extra), algo, pk_path) == base, (n, extra)
 
 
