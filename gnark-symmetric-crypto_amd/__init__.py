@@ -22,7 +22,8 @@ ALGORITHM_NAMES = {0: "chacha20", 1: "aes-128-ctr", 2: "aes-256-ctr"}   # prove_
 EXPORTS = ["enforce_binding", "InitAlgorithm", "Free", "Prove", "ProveBatch", "gsc_prove_raw", "gsc_setup",
            "gsc_set_deterministic_randomness", "gsc_debug_prove", "gsc_debug_vector", "gsc_describe", "gsc_last_stage_ms", "gsc_last_dominant_kernel", "gsc_last_kernel_clock", "gsc_debug_field_ops", "gsc_debug_limb_ops", "gsc_debug_curve_ops", "gsc_debug_compute_h", "gsc_debug_compute_d", "gsc_debug_secret_residue", "gsc_debug_clock_trace", "gsc_debug_glv_split",
            "gsc_verify_init", "gsc_verify_raw", "VerifyBatch", "gsc_debug_pairing",
-           "gsc_verify_raw_batched", "gsc_verify_all", "VerifyAll", "gsc_debug_verify_randomizers"]
+           "gsc_verify_raw_batched", "gsc_verify_all", "VerifyAll", "gsc_debug_verify_randomizers",
+           "gsc_verify_json", "gsc_verify_last_path", "gsc_debug_verify_path", "gsc_debug_pairing_few"]
 
 
 class GoSlice(C.Structure):
@@ -94,6 +95,14 @@ def lib():
         L.VerifyAll.argtypes = [GoSlice]
         L.gsc_debug_verify_randomizers.restype = C.c_int
         L.gsc_debug_verify_randomizers.argtypes = [C.c_char_p, C.c_int]
+        L.gsc_verify_json.restype = C.c_ubyte
+        L.gsc_verify_json.argtypes = [GoSlice]
+        L.gsc_verify_last_path.restype = C.c_int
+        L.gsc_verify_last_path.argtypes = [C.c_ubyte]
+        L.gsc_debug_verify_path.restype = C.c_int
+        L.gsc_debug_verify_path.argtypes = [C.c_int]
+        L.gsc_debug_pairing_few.restype = C.c_longlong
+        L.gsc_debug_pairing_few.argtypes = [C.c_char_p, C.c_char_p, C.c_size_t, C.c_void_p]
         L.enforce_binding()
         _lib = L
     return _lib
@@ -416,14 +425,32 @@ def debug_verify_randomizers(seed: bytes = None, all_ones: bool = False) -> int:
     return lib().gsc_debug_verify_randomizers(None if seed is None else bytes(seed), 1 if all_ones else 0)
 
 
-def debug_pairing(g1_points, g2_points):
-    """TEST HOOK: reduced pairings on the device.  g1_points: [(x, y)] ints (None = infinity), g2_points: [((x0, x1), (y0, y1))]
-    -> list of 12-tuples of ints, element 2i + j = component j (of 1, u) of the w^i coefficient."""
+def verify_json(params) -> bool:
+    """gsc_verify_json: Verify's input (bytes/str JSON, or a dict whose bytes values become arrays) answered on the GPU."""
+    if isinstance(params, dict):
+        params = json.dumps({k: (list(v) if isinstance(v, (bytes, bytearray)) else v) for k, v in params.items()})
+    s, keep = _slice(params.encode() if isinstance(params, str) else bytes(params))
+    return bool(lib().gsc_verify_json(s))
+
+
+def verify_last_path(algorithm_id: int) -> int:
+    """gsc_verify_last_path: 1 the last verifier call on this key ran one thread per proof, 2 the few-proof groups, 0 none yet, -1 no key."""
+    return lib().gsc_verify_last_path(algorithm_id)
+
+
+def debug_verify_path(mode: int) -> int:
+    """TEST HOOK: route every later verifier call: 0 automatic, 1 one thread per proof, 2 the few-proof groups.  -1 when hooks are off."""
+    return lib().gsc_debug_verify_path(mode)
+
+
+def debug_pairing(g1_points, g2_points, few: bool = False):
+    """TEST HOOK: reduced pairings on the device (few: by the few-proof kernels).  g1_points: [(x, y)] ints (None = infinity),
+    g2_points: [((x0, x1), (y0, y1))] -> list of 12-tuples of ints, element 2i + j = component j (of 1, u) of the w^i coefficient."""
     n = len(g1_points)
     b1 = b"".join(bytes(64) if P is None else P[0].to_bytes(32, "big") + P[1].to_bytes(32, "big") for P in g1_points)
     b2 = b"".join(bytes(128) if Q is None else Q[0][1].to_bytes(32, "big") + Q[0][0].to_bytes(32, "big") + Q[1][1].to_bytes(32, "big") + Q[1][0].to_bytes(32, "big") for Q in g2_points)
     out = C.create_string_buffer(384 * max(n, 1))
-    if lib().gsc_debug_pairing(b1, b2, n, out) != n:
+    if (lib().gsc_debug_pairing_few if few else lib().gsc_debug_pairing)(b1, b2, n, out) != n:
         raise RuntimeError("gsc_debug_pairing failed (test hooks off?)")
     return [tuple(int.from_bytes(out.raw[384 * i + 32 * c:384 * i + 32 * c + 32], "big") for c in range(12)) for i in range(n)]
 

@@ -298,7 +298,8 @@ std::string prove_one_json(const char* data, size_t len, DebugVectors* dbg) {
 
 }  // namespace
 
-long long gsc_verify_debug_pairing_impl(const uint8_t* g1, const uint8_t* g2, size_t n, uint8_t* out);      // verify_gpu.cpp
+long long gsc_verify_debug_pairing_impl(const uint8_t* g1, const uint8_t* g2, size_t n, uint8_t* out, bool few);      // verify_gpu.cpp
+int gsc_verify_debug_path_impl(int mode);                                                             // verify_gpu.cpp
 int gsc_verify_debug_randomizers_impl(const uint8_t* seed32, int all_ones);                           // verify_gpu.cpp
 
 extern "C" {
@@ -469,7 +470,15 @@ int gsc_debug_clock_trace(uint32_t n, uint32_t interval_us, unsigned long long* 
 
 long long gsc_debug_pairing(const uint8_t* g1, const uint8_t* g2, size_t n, uint8_t* out) {
     if (hooks_refused("gsc_debug_pairing") || (n && (!g1 || !g2 || !out))) return -1;
-    return gsc_verify_debug_pairing_impl(g1, g2, n, out);
+    return gsc_verify_debug_pairing_impl(g1, g2, n, out, false);
+}
+long long gsc_debug_pairing_few(const uint8_t* g1, const uint8_t* g2, size_t n, uint8_t* out) {
+    if (hooks_refused("gsc_debug_pairing_few") || (n && (!g1 || !g2 || !out))) return -1;
+    return gsc_verify_debug_pairing_impl(g1, g2, n, out, true);
+}
+int gsc_debug_verify_path(int mode) {
+    if (hooks_refused("gsc_debug_verify_path")) return -1;
+    return gsc_verify_debug_path_impl(mode);
 }
 int gsc_debug_verify_randomizers(const uint8_t* seed32, int all_ones) {
     if (hooks_refused("gsc_debug_verify_randomizers")) return -1;

@@ -4,8 +4,10 @@
 //   sum    one block: the chunk's totals and the G1 points of the fixed pairs (-(sum rho) alpha, ...)
 //   miller one thread per proof: f_i = e(rho A, B) unreduced; one extra block: the fixed pairs against the key's lines
 //   tree   products of 4 in place, until one Fp12 is left
-//   final  the final exponentiation of that product: one flag per chunk
+//   final  the final exponentiation of that product: one flag per chunk, by one group of lanes (k_verify_few.hip)
+// A chunk on the few-proof path takes k_verify_few.hip's lines + Miller kernels in place of `miller`.
 #include "verify_batch_kernels.hpp"
+#include "verify_few_kernels.hpp"
 #include "verify_batch_dev.hpp"
 
 namespace gsc {
@@ -112,30 +114,29 @@ __global__ __launch_bounds__(64) void k_verify_batch_tree(F12* f, size_t n, size
     f[i] = acc;
 }
 
-__global__ __launch_bounds__(64) void k_verify_batch_final(const F12* f, uint8_t* flag) {
-    if (threadIdx.x == 0) flag[0] = batch_accept(f[0]) ? 1 : 0;
-}
-
 unsigned blocks(size_t n) { return (unsigned)((n + 63) / 64); }
 
 }  // namespace
 
 size_t batch_blocks(size_t n) { return (n + kScaleThreads - 1) / kScaleThreads; }
 
-void launch_verify_batch(const KeyDev& k, const ProofDev* pd, const uint32_t* rnd, size_t n, const BatchBufs& b, hipStream_t s) {
+void launch_verify_batch(const KeyDev& k, const ProofDev* pd, const uint32_t* rnd, size_t n, const BatchBufs& b, Line* few_lines, hipStream_t s) {
     if (!n) return;
     const size_t nblk = batch_blocks(n);
     hipLaunchKernelGGL(k_verify_batch_scale, dim3((unsigned)nblk), dim3(kScaleThreads), 0, s, pd, rnd, n, k.has_commitment ? kBatchSums : 2,
                        b.ra, b.ok, b.part, b.rpart);
     hipLaunchKernelGGL(k_verify_batch_sum, dim3(1), dim3(kSumThreads), 0, s, k, b.part, b.rpart, nblk, b.fixed);
-    hipLaunchKernelGGL(k_verify_batch_miller, dim3(blocks(n) + 1), dim3(64), 0, s, k, pd, b.ra, b.fixed, n, b.f);
+    if (few_lines) {
+        launch_verify_few_lines(pd, n, few_lines, s);
+        launch_verify_few_batch_miller(k, pd, b.ra, b.fixed, few_lines, n, b.f, s);
+    } else hipLaunchKernelGGL(k_verify_batch_miller, dim3(blocks(n) + 1), dim3(64), 0, s, k, pd, b.ra, b.fixed, n, b.f);
     // every product pass folds 4 values into one: f[i] *= f[i + h] f[i + 2h] f[i + 3h], h = ceil(m / 4)
     for (size_t m = n + kBatchFixed; m > 1;) {
         const size_t h = (m + 3) / 4;
         hipLaunchKernelGGL(k_verify_batch_tree, dim3(blocks(h)), dim3(64), 0, s, b.f, m, h);
         m = h;
     }
-    hipLaunchKernelGGL(k_verify_batch_final, dim3(1), dim3(64), 0, s, b.f, b.flag);
+    launch_verify_few_final(b.f, b.flag, s);
 }
 
 }  // namespace gsc

@@ -15,6 +15,7 @@ struct BatchBufs {
     uint8_t* flag;         // 1: the chunk's batch check holds
 };
 size_t batch_blocks(size_t n);
-// rnd: n x kRandWords words (rho_i, t_i).  Writes b.ok and b.flag; proofs without ok contribute nothing.
-void launch_verify_batch(const vfy::KeyDev& k, const vfy::ProofDev* pd, const uint32_t* rnd, size_t n, const BatchBufs& b, hipStream_t s);
+// rnd: n x kRandWords words (rho_i, t_i).  Writes b.ok and b.flag; proofs without ok contribute nothing.  few_lines != nullptr (room for
+// n x kLineSteps lines): the Miller pass runs on the few-proof kernels (k_verify_few.hip); the final exponentiation always does.
+void launch_verify_batch(const vfy::KeyDev& k, const vfy::ProofDev* pd, const uint32_t* rnd, size_t n, const BatchBufs& b, vfy::Line* few_lines, hipStream_t s);
 }  // namespace gsc

@@ -1,14 +1,18 @@
-// GPU verifier in libprove.so: gsc_verify_init, gsc_verify_raw, VerifyBatch, gsc_debug_pairing, and the batched check
+// GPU verifier in libprove.so: gsc_verify_init, gsc_verify_raw, VerifyBatch, gsc_verify_json, gsc_debug_pairing, and the batched check
 // gsc_verify_raw_batched, gsc_verify_all, VerifyAll (include/libprove.h).
 // Verdicts are those of libverify.so's Verify (verifier.cpp); the host only checks sizes and packs bytes (verify_common),
 // decoding and every curve operation run in k_verify.hip (k_verify_batch.hip for the batched check).  Each key owns a non-blocking stream and chunk buffers on one device
 // (GSC_DEVICE, or the first of GSC_DEVICES); calls on the same key are serialised, and nothing here synchronises the device.
+// Routing: a call of at most GSC_VERIFY_FEW_MAX items takes the few-proof kernels (k_verify_few.hip: 8 lanes per proof), larger
+// calls the per-thread ones; gsc_verify_last_path reports which.
 #include "../../include/libprove.h"
 #include "json.hpp"
 #include "verify_common.hpp"
 #include "host_ciphers.hpp"
 #include "verify_batch_kernels.hpp"
 #include "verify_kernels.hpp"
+#include "verify_few_kernels.hpp"
+#include <atomic>
 #include <cerrno>
 #include <cstdio>
 #include <cstdlib>
@@ -30,6 +34,24 @@ namespace V = gsc::verify;
 
 constexpr size_t kChunk = 65536;      // proofs per device pass: buffers are allocated once per key, so memory does not grow with n
 
+// Largest call (items of one algorithm) that takes the few-proof kernels unless GSC_VERIFY_FEW_MAX says otherwise: the largest
+// measured size at which they beat the per-thread kernels by at least 10 %.
+constexpr size_t kFewMaxDefault = 8192;
+enum { kPathThread = 1, kPathFew = 2 };
+std::atomic<int> g_path_mode{0};      // gsc_debug_verify_path: 0 automatic, else the forced path
+
+// GSC_VERIFY_FEW_MAX: decimal digits only; anything else (a sign, letters, nothing, a value past 64 bits) is refused with a line on
+// stderr and the default stands
+size_t few_max_setting() {
+    const char* v = getenv("GSC_VERIFY_FEW_MAX");
+    if (!v) return kFewMaxDefault;
+    const size_t len = strlen(v);
+    bool digits = len > 0 && len <= 19;
+    for (size_t i = 0; digits && i < len; i++) digits = v[i] >= '0' && v[i] <= '9';
+    if (!digits) { fprintf(stderr, "GSC_VERIFY_FEW_MAX=%s is not a number of proofs: using %zu\n", v, kFewMaxDefault); return kFewMaxDefault; }
+    return (size_t)strtoull(v, nullptr, 10);
+}
+
 struct HipError : std::runtime_error { using std::runtime_error::runtime_error; };
 void ck(hipError_t e, const char* what) { if (e != hipSuccess) throw HipError(std::string(what) + ": " + hipGetErrorString(e)); }
 
@@ -49,6 +71,10 @@ struct GpuKey {
     int device = 0, algo = 0;
     hipStream_t stream = nullptr;
     bool has_commitment = false, fits = false;
+    size_t few_max = 0;                  // GSC_VERIFY_FEW_MAX as it stood when the key loaded
+    std::atomic<int> last_path{0};
+    DevBuf<Line> few_lines;              // kFewChunk x kLineSteps lines of the proofs' own B (180 MB): allocated with the key unless
+                                         // GSC_VERIFY_FEW_MAX=0, else by the first call forced onto the path (route_few)
     DevBuf<VP1> K, table, ctable;
     DevBuf<Line> lines;
     KeyDev kd{};
@@ -76,6 +102,7 @@ std::shared_ptr<GpuKey> build_key(int algo, const uint8_t* b, size_t n) {
     if (!V::parse_vk_layout(b, n, lay, &err)) { printf("%s\n", err.c_str()); return nullptr; }
     auto k = std::make_shared<GpuKey>();
     k->device = verify_device();
+    k->few_max = few_max_setting();
     k->algo = algo;
     ck(hipSetDevice(k->device), "hipSetDevice");
     ck(hipStreamCreateWithFlags(&k->stream, hipStreamNonBlocking), "hipStreamCreate");
@@ -129,6 +156,7 @@ std::shared_ptr<GpuKey> build_key(int algo, const uint8_t* b, size_t n) {
     const size_t nblk = batch_blocks(kChunk);
     k->rnd.alloc(kChunk * kRandWords); k->ra.alloc(kChunk); k->fixed.alloc(kBatchFixed); k->bok.alloc(kChunk); k->bflag.alloc(1);
     k->part.alloc(nblk * kBatchSums); k->rpart.alloc(nblk * 4); k->f.alloc(kChunk + kBatchFixed);
+    if (k->few_max) k->few_lines.alloc(kFewChunk * kLineSteps);
     return k;
 }
 
@@ -164,19 +192,37 @@ size_t prep_chunk(GpuKey& k, const uint8_t* proofs, const uint32_t* lens, const 
     return passed;
 }
 
+// the path of a call of n items, recorded for gsc_verify_last_path (k.mu held)
+bool route_few(GpuKey& k, size_t n) {
+    const int mode = g_path_mode.load();
+    const bool few = mode ? mode == kPathFew : n <= k.few_max;
+    k.last_path = few ? kPathFew : kPathThread;
+    if (few && !k.few_lines.p) k.few_lines.alloc(kFewChunk * kLineSteps);
+    return few;
+}
+// verdicts of the m proofs in k.pd into k.verdict, one pairing check per proof on the call's path
+void launch_pairings(GpuKey& k, bool few, size_t m) {
+    if (few) {
+        launch_verify_few_lines(k.pd.p, m, k.few_lines.p, k.stream);
+        launch_verify_few_pairing(k.kd, k.pd.p, k.few_lines.p, k.verdict.p, nullptr, m, k.stream);
+    } else launch_verify_pairing(k.kd, k.pd.p, k.verdict.p, nullptr, m, k.stream);
+    ck(hipGetLastError(), "k_verify_pairing");
+}
+
 // verdicts for n items; proofs in 196-byte slots.  Returns the number accepted; throws HipError on a device error.
 long long run_verify(GpuKey& k, const uint8_t* proofs, const uint32_t* lens, const uint8_t* signals, size_t n, uint8_t* verdicts) {
     std::lock_guard<std::mutex> l(k.mu);
     ck(hipSetDevice(k.device), "hipSetDevice");
     long long accepted = 0;
-    std::vector<uint8_t> win(kChunk * V::kWindows), pre(kChunk);
-    for (size_t off = 0; off < n; off += kChunk) {
-        const size_t m = std::min(kChunk, n - off);
+    const bool few = route_few(k, n);
+    const size_t chunk = std::min(n, few ? kFewChunk : kChunk);
+    std::vector<uint8_t> win(chunk * V::kWindows), pre(chunk);
+    for (size_t off = 0; off < n; off += chunk) {
+        const size_t m = std::min(chunk, n - off);
         if (!k.fits) { memset(verdicts + off, 0, m); continue; }
         prep_chunk(k, proofs, lens, signals, off, m, win, pre);
         hipStream_t s = k.stream;
-        launch_verify_pairing(k.kd, k.pd.p, k.verdict.p, nullptr, m, s);
-        ck(hipGetLastError(), "k_verify_pairing");
+        launch_pairings(k, few, m);
         ck(hipMemcpyAsync(verdicts + off, k.verdict.p, m, hipMemcpyDeviceToHost, s), "copy");
         ck(hipStreamSynchronize(s), "verify");
         for (size_t i = 0; i < m; i++) accepted += verdicts[off + i];
@@ -235,17 +281,19 @@ long long run_verify_batched(GpuKey& k, const uint8_t* proofs, const uint32_t* l
     std::lock_guard<std::mutex> l(k.mu);
     ck(hipSetDevice(k.device), "hipSetDevice");
     long long accepted = 0;
-    std::vector<uint8_t> win(kChunk * V::kWindows), pre(kChunk), okh(all ? kChunk : 0);
-    std::vector<uint32_t> rnd(kChunk * kRandWords);
-    for (size_t off = 0; off < n; off += kChunk) {
-        const size_t m = std::min(kChunk, n - off);
+    const bool few = route_few(k, n);
+    const size_t chunk = std::max<size_t>(1, std::min(n, few ? kFewChunk : kChunk));
+    std::vector<uint8_t> win(chunk * V::kWindows), pre(chunk), okh(all ? chunk : 0);
+    std::vector<uint32_t> rnd(chunk * kRandWords);
+    for (size_t off = 0; off < n; off += chunk) {
+        const size_t m = std::min(chunk, n - off);
         if (!k.fits) { if (all) return 0; memset(verdicts + off, 0, m); continue; }
         const size_t passed = prep_chunk(k, proofs, lens, signals, off, m, win, pre);
         if (all && passed < m) { ck(hipStreamSynchronize(k.stream), "verify"); return 0; }
-        draw_randomizers(rnd.data(), m, k.has_commitment, off / kChunk);      // on the host while k_verify_prep runs
+        draw_randomizers(rnd.data(), m, k.has_commitment, off / chunk);      // on the host while k_verify_prep runs
         hipStream_t s = k.stream;
         ck(hipMemcpyAsync(k.rnd.p, rnd.data(), m * kRandWords * sizeof(uint32_t), hipMemcpyHostToDevice, s), "copy");
-        launch_verify_batch(k.kd, k.pd.p, k.rnd.p, m, k.bufs(), s);
+        launch_verify_batch(k.kd, k.pd.p, k.rnd.p, m, k.bufs(), few ? k.few_lines.p : nullptr, s);
         ck(hipGetLastError(), "k_verify_batch");
         uint8_t* okv = all ? okh.data() : verdicts + off;
         uint8_t flag = 0;
@@ -256,8 +304,7 @@ long long run_verify_batched(GpuKey& k, const uint8_t* proofs, const uint32_t* l
         for (size_t i = 0; i < m; i++) nok += okv[i];
         if (all) { if (!flag || nok < m) return 0; continue; }
         if (!flag) {      // some proof with ok fails: the per-proof pairings of the same ProofDev decide, as in run_verify
-            launch_verify_pairing(k.kd, k.pd.p, k.verdict.p, nullptr, m, s);
-            ck(hipGetLastError(), "k_verify_pairing");
+            launch_pairings(k, few, m);
             ck(hipMemcpyAsync(verdicts + off, k.verdict.p, m, hipMemcpyDeviceToHost, s), "copy");
             ck(hipStreamSynchronize(s), "verify");
             nok = 0;
@@ -346,6 +393,26 @@ struct Prove_return VerifyBatch(GoSlice params) {
     return to_c(out);
 }
 
+GoUint8 gsc_verify_json(GoSlice params) {
+    try {
+        JsonValue arr;
+        arr.kind = JsonValue::Array;
+        arr.items.push_back(json_parse((const char*)params.data, params.len > 0 ? (size_t)params.len : 0));
+        Grouped g = group_requests(arr);      // VerifyBatch's parser on an array of this one item
+        for (int a = 0; a < 3; a++) if (g.where[a].size()) {
+            uint8_t v = 0;
+            return gsc_verify_raw((GoUint8)a, g.slots[a].data(), g.lens[a].data(), g.sigs[a].data(), 1, &v) == 1 && v;
+        }
+        return 0;
+    } catch (const std::exception&) { return 0; }
+}
+
+int gsc_verify_last_path(GoUint8 algorithmID) {
+    if (algorithmID > 2) return -1;
+    auto k = key_for(algorithmID);
+    return k ? k->last_path.load() : -1;
+}
+
 long long gsc_verify_raw_batched(GoUint8 algorithmID, const uint8_t* proofs, const uint32_t* proof_lens, const uint8_t* signals, size_t n,
                                  uint8_t* verdicts) {
     if (n) memset(verdicts, 0, n);
@@ -390,8 +457,15 @@ int gsc_verify_debug_randomizers_impl(const uint8_t* seed32, int all_ones) {
     return 0;
 }
 
-// gsc_debug_pairing's body: capi.cpp exports the hook behind its GSC_ENABLE_TEST_HOOKS gate and calls this
-long long gsc_verify_debug_pairing_impl(const uint8_t* g1, const uint8_t* g2, size_t n, uint8_t* out) {
+// gsc_debug_verify_path's body
+int gsc_verify_debug_path_impl(int mode) {
+    if (mode < 0 || mode > 2) return -1;
+    g_path_mode = mode;
+    return 0;
+}
+
+// gsc_debug_pairing's and gsc_debug_pairing_few's body: capi.cpp exports the hooks behind its GSC_ENABLE_TEST_HOOKS gate and calls this
+long long gsc_verify_debug_pairing_impl(const uint8_t* g1, const uint8_t* g2, size_t n, uint8_t* out, bool few) {
     if (!n) return 0;
     try {
         ck(hipSetDevice(verify_device()), "hipSetDevice");
@@ -406,7 +480,12 @@ long long gsc_verify_debug_pairing_impl(const uint8_t* g1, const uint8_t* g2, si
         for (int i = 0; i < 5; i++) kd.qinf[i] = 1;
         kd.alpha.inf = 1;
         launch_verify_debug_points(d1.p, d2.p, pd.p, n, s);
-        launch_verify_pairing(kd, pd.p, verdict.p, f.p, n, s);
+        DevBuf<Line> lines;
+        if (few) {
+            lines.alloc(n * kLineSteps);
+            launch_verify_few_lines(pd.p, n, lines.p, s);
+            launch_verify_few_pairing(kd, pd.p, lines.p, verdict.p, f.p, n, s);
+        } else launch_verify_pairing(kd, pd.p, verdict.p, f.p, n, s);
         launch_verify_f12_bytes(f.p, dout.p, n, s);
         ck(hipMemcpyAsync(out, dout.p, 384 * n, hipMemcpyDeviceToHost, s), "copy");
         ck(hipStreamSynchronize(s), "debug pairing");

@@ -180,6 +180,22 @@ extern GoUint8 VerifyAll(GoSlice params);
  * every rho_i = t_i = 1 (the naive sum, which swapped public inputs of two proofs pass; it takes precedence over a seed); NULL
  * seed and all_ones == 0: the OS CSPRNG again (the default).  Returns 0, -1 when hooks are off. */
 extern int gsc_debug_verify_randomizers(const uint8_t *seed32, int all_ones);
+/* Few-proof path (k_verify_few.hip): a call of at most GSC_VERIFY_FEW_MAX items of one algorithm (read once, when the key loads; 0
+ * switches the path off) is verified by groups of 8 lanes sharing one proof's pairing instead of one thread per proof.  Every entry
+ * point above routes by itself (such a call is processed in chunks of 8192, the batched check included); verdicts do not depend on
+ * the path.  The batched check's final exponentiation always runs there.  Default: 8192, the measured crossover. */
+/* One Verify input ({"cipher","proof","publicSignals"}) answered on the GPU: 1 iff Verify would accept it; anything malformed, an
+ * unknown cipher or a cipher without a key: 0.  Shares VerifyBatch's parser. */
+extern GoUint8 gsc_verify_json(GoSlice params);
+/* Which kernels the last verifier call on this key took: 1 one thread per proof, 2 the few-proof groups, 0 no call yet, -1 no key
+ * loaded (or algorithmID > 2). */
+extern int gsc_verify_last_path(GoUint8 algorithmID);
+/* TEST HOOK: the routing of every later verifier call.  0 automatic (by GSC_VERIFY_FEW_MAX), 1 always one thread per proof, 2 always
+ * the few-proof groups (any n, in chunks of 8192).  Returns 0, -1 when hooks are off or mode is none of these. */
+extern int gsc_debug_verify_path(int mode);
+/* TEST HOOK: gsc_debug_pairing's arguments and output, computed by the few-proof kernels (the lines of Q_i, the Miller loop over
+ * them and the lane-sliced final exponentiation). */
+extern long long gsc_debug_pairing_few(const uint8_t *g1_uncompressed, const uint8_t *g2_uncompressed, size_t n, uint8_t *out);
 
 #ifdef __cplusplus
 }

@@ -9,6 +9,15 @@ the CPU rate is measured on a sample of the same proofs with the same check.
 --batched times gsc_verify_raw_batched (one final exponentiation per chunk) against gsc_verify_raw on the same all-valid proofs
 instead, each the median of --repeat calls, and checks that the verdicts are equal.  One more ChaCha20 line at the largest size has a
 single bad proof (signals of another statement): the price of the proof-by-proof pass that follows a failing chunk.
+
+--latency times single calls from one proof upwards: for ChaCha20 and AES-128 and every size of --sizes (honoured down to 1, e.g.
+1,8,64,512,4096,8192,32768,65536), the median of --repeat (at least 5) calls of gsc_verify_raw, and of gsc_verify_raw_batched and
+gsc_verify_all too with --batched, in milliseconds and proofs/s, with libverify.so's single-thread milliseconds per proof beside n = 1.  --path thread / few forces the
+per-thread or the few-proof kernels through gsc_debug_verify_path (auto: the library routes by GSC_VERIFY_FEW_MAX; a comma-separated
+list measures one after the other on the same proofs); --label names
+the build in every line, and --lib-root measures the library of another checkout (the parent commit) with this tool.
+
+    python tools/bench_verify.py --latency --sizes 1,8,64,512,4096,8192 --path few [--batched] [--label change] [--out FILE]
 """
 import argparse
 import json
@@ -21,7 +30,6 @@ from concurrent.futures import ThreadPoolExecutor
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-import gsc_loader  # noqa: E402
 from conftest import golden_bytes  # noqa: E402
 
 NAMES = {0: "chacha20", 1: "aes-128-ctr"}
@@ -99,6 +107,70 @@ def run_batched(g, algo, n, seed, repeat, bad=None):
             "verdicts_ok": ok, "device": os.environ.get("GSC_DEVICE", "0")}
 
 
+def run_latency(g, algo, items, n, repeat, entry, path, label):
+    proofs, lens, sig = items[0][:196 * n], items[1][:n], items[2][:144 * n]
+    batched = entry == "gsc_verify_all"
+    fn = {"gsc_verify_raw": g.verify_raw, "gsc_verify_raw_batched": g.verify_raw_batched, "gsc_verify_all": g.verify_all}[entry]
+    call = lambda: fn(algo, proofs, lens, sig)
+    call(); call()                                    # warm-up: kernel load, clocks
+    med, out = _median_call(call, repeat)
+    line = {"tool": "bench_verify", "mode": "latency", "build": label, "entry": entry,
+            "cipher": NAMES[algo], "n": n, "path": path, "ms": round(1e3 * med, 3), "proofs_per_s": round(n / med, 1), "repeat": repeat,
+            "verdicts_ok": out == (1 if batched else [1] * n), "device": os.environ.get("GSC_DEVICE", "0")}
+    if hasattr(g, "verify_last_path"):
+        line["last_path"] = g.verify_last_path(algo)
+    if n == 1:
+        enc = json.dumps({"cipher": NAMES[algo], "proof": list(proofs[:lens[0]]), "publicSignals": list(sig)}).encode()
+        cpu, ok = _median_call(lambda: g.verify(enc), repeat)
+        line["cpu_1thread_ms"] = round(1e3 * cpu, 3)
+        line["verdicts_ok"] = line["verdicts_ok"] and bool(ok)
+    return line
+
+
+def aes128_keys():
+    cache = os.path.join(ROOT, "build", "keys")
+    pkp, vkp = os.path.join(cache, "pk.aes128"), os.path.join(cache, "vk.aes128")
+    r1cs = golden_bytes("r1cs.aes128")
+    if not (os.path.exists(pkp) and os.path.exists(vkp)):       # the test suite's AES-128 test keys (same seed, same cache)
+        from oracle import oracle as O
+        os.makedirs(cache, exist_ok=True)
+        pk, vkb = O.setup(O.R1CS(r1cs), bytes([1] * 32))
+        open(pkp, "wb").write(pk); open(vkp, "wb").write(vkb)
+    return open(pkp, "rb").read(), r1cs, open(vkp, "rb").read()
+
+
+def main_latency(g, a):
+    sizes = sorted(int(x) for x in a.sizes.split(",") if x)
+    modes = {"auto": 0, "thread": 1, "few": 2}
+    paths = [p for p in a.path.split(",") if p]
+    for p in paths:
+        if p not in modes or (modes[p] and (not hasattr(g, "debug_verify_path") or g.debug_verify_path(0) != 0)):
+            raise SystemExit("--path %s needs gsc_debug_verify_path (test hooks on, a build that has it)" % p)
+    lines = []
+    for algo in (0, 1):
+        if algo == 0:
+            pk, r1cs, vk = golden_bytes("pk.chacha20"), golden_bytes("r1cs.chacha20"), golden_bytes("vk.chacha20")
+        elif a.aes:
+            pk, r1cs, vk = aes128_keys()
+        else:
+            continue
+        assert g.init_algorithm(algo, pk, r1cs) and g.verify_init(algo, vk) and g.init_verifier(algo, vk)
+        items = make_items(g, algo, max(sizes), 11 + algo)      # one set of proofs; size n takes the first n
+        for p in paths:
+            if modes[p] or len(paths) > 1:
+                g.debug_verify_path(modes[p])
+            for entry in (["gsc_verify_raw", "gsc_verify_raw_batched", "gsc_verify_all"] if a.batched else ["gsc_verify_raw"]):
+                for n in sizes:
+                    lines.append(run_latency(g, algo, items, n, max(5, a.repeat), entry, p, a.label)); print(json.dumps(lines[-1]), flush=True)
+        if hasattr(g, "debug_verify_path"):
+            g.debug_verify_path(0)
+    if a.out:
+        with open(a.out, "a") as f:
+            for l in lines:
+                f.write(json.dumps(l) + "\n")
+    return 0 if all(l["verdicts_ok"] for l in lines) else 1
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="1024,8192,65536")
@@ -107,8 +179,16 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--batched", action="store_true", help="gsc_verify_raw_batched against gsc_verify_raw")
     ap.add_argument("--repeat", type=int, default=3, help="--batched: calls per timing (median)")
+    ap.add_argument("--latency", action="store_true", help="per-call milliseconds from n = 1 upwards (with --batched: gsc_verify_raw_batched and gsc_verify_all too)")
+    ap.add_argument("--path", default="auto", help="--latency: auto, thread, few or several, e.g. auto,thread,few: force the verifier's kernels (test hook)")
+    ap.add_argument("--label", default="change", help="--latency: name of the measured build in every line")
+    ap.add_argument("--lib-root", default=ROOT, help="checkout whose library is measured (default: this one)")
     a = ap.parse_args()
+    sys.path.insert(0, os.path.abspath(a.lib_root))
+    import gsc_loader
     g = gsc_loader.load()
+    if a.latency:
+        return main_latency(g, a)
     lines = []
     assert g.init_algorithm(0, golden_bytes("pk.chacha20"), golden_bytes("r1cs.chacha20"))
     vk = golden_bytes("vk.chacha20")
