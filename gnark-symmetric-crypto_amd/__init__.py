@@ -23,7 +23,8 @@ EXPORTS = ["enforce_binding", "InitAlgorithm", "Free", "Prove", "ProveBatch", "g
            "gsc_set_deterministic_randomness", "gsc_debug_prove", "gsc_debug_vector", "gsc_describe", "gsc_last_stage_ms", "gsc_last_dominant_kernel", "gsc_last_kernel_clock", "gsc_debug_field_ops", "gsc_debug_limb_ops", "gsc_debug_curve_ops", "gsc_debug_compute_h", "gsc_debug_compute_d", "gsc_debug_secret_residue", "gsc_debug_clock_trace", "gsc_debug_glv_split",
            "gsc_verify_init", "gsc_verify_raw", "VerifyBatch", "gsc_debug_pairing",
            "gsc_verify_raw_batched", "gsc_verify_all", "VerifyAll", "gsc_debug_verify_randomizers",
-           "gsc_verify_json", "gsc_verify_last_path", "gsc_debug_verify_path", "gsc_debug_pairing_few"]
+           "gsc_verify_json", "gsc_verify_last_path", "gsc_debug_verify_path", "gsc_debug_pairing_few",
+           "gsc_verify_claims", "VerifyClaims"]
 
 
 class GoSlice(C.Structure):
@@ -103,6 +104,10 @@ def lib():
         L.gsc_debug_verify_path.argtypes = [C.c_int]
         L.gsc_debug_pairing_few.restype = C.c_longlong
         L.gsc_debug_pairing_few.argtypes = [C.c_char_p, C.c_char_p, C.c_size_t, C.c_void_p]
+        L.gsc_verify_claims.restype = C.c_longlong
+        L.gsc_verify_claims.argtypes = [C.c_ubyte, C.c_char_p, C.c_void_p, C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.VerifyClaims.restype = ProveReturn
+        L.VerifyClaims.argtypes = [GoSlice]
         L.enforce_binding()
         _lib = L
     return _lib
@@ -416,6 +421,33 @@ def verify_all_json(items) -> bool:
                             for it in items]).encode()
     s, keep = _slice(bytes(items))
     return bool(lib().VerifyAll(s))
+
+
+def verify_claims(algorithm_id: int, proofs: bytes, lens, signals: bytes, ends):
+    """gsc_verify_claims: verify_raw's items cut into claims, claim j = items [ends[j-1], ends[j]) -> list of 0/1 verdicts, one per claim,
+    each from a batched check of its own.  Raises RuntimeError when no key is loaded (-1), on a device error (-2) or when ends is not
+    non-decreasing up to the number of items (-3)."""
+    n, m = len(lens), len(ends)
+    assert len(proofs) >= 196 * n and len(signals) >= 144 * n
+    lens_arr = (C.c_uint32 * max(n, 1))(*lens)
+    ends_arr = (C.c_uint64 * max(m, 1))(*ends)
+    out = C.create_string_buffer(max(m, 1))
+    rc = lib().gsc_verify_claims(algorithm_id, bytes(proofs), lens_arr, bytes(signals), n, ends_arr, m, out)
+    if rc < 0:
+        raise RuntimeError("gsc_verify_claims failed (%d): %s" % (rc, {-1: "no key loaded", -2: "device error"}.get(rc, "bad claim ends")))
+    return list(out.raw[:m])
+
+
+def verify_claims_json(claims):
+    """VerifyClaims: a list of claims, each a list of Verify inputs (dicts; bytes values become arrays), or already encoded JSON
+    bytes / str -> the decoded result: a list of bools, one per claim (top-level errors: VerifyBatch's shapes)."""
+    if isinstance(claims, str):
+        claims = claims.encode()
+    if not isinstance(claims, (bytes, bytearray)):
+        enc = lambda it: {k: (list(v) if isinstance(v, (bytes, bytearray)) else v) for k, v in it.items()} if isinstance(it, dict) else it
+        claims = json.dumps([[enc(it) for it in cl] if isinstance(cl, list) else cl for cl in claims]).encode()
+    s, keep = _slice(bytes(claims))
+    return json.loads(_take(lib().VerifyClaims(s)))
 
 
 def debug_verify_randomizers(seed: bytes = None, all_ones: bool = False) -> int:

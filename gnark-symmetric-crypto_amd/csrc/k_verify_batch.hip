@@ -120,6 +120,11 @@ unsigned blocks(size_t n) { return (unsigned)((n + 63) / 64); }
 
 size_t batch_blocks(size_t n) { return (n + kScaleThreads - 1) / kScaleThreads; }
 
+void launch_verify_batch_proof_miller(const KeyDev& k, const ProofDev* pd, const VP1* ra, size_t n, F12* f, hipStream_t s) {
+    // without the extra block every block takes k_verify_batch_miller's proof branch
+    if (n) hipLaunchKernelGGL(k_verify_batch_miller, dim3(blocks(n)), dim3(64), 0, s, k, pd, ra, (const VP1*)nullptr, n, f);
+}
+
 void launch_verify_batch(const KeyDev& k, const ProofDev* pd, const uint32_t* rnd, size_t n, const BatchBufs& b, Line* few_lines, hipStream_t s) {
     if (!n) return;
     const size_t nblk = batch_blocks(n);

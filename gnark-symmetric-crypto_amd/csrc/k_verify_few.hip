@@ -16,12 +16,8 @@ using namespace vfy;
 namespace {
 
 constexpr int kFewThreads = 64;
-constexpr int kFewLds = few::kGroupsPerWave * few::kSlots * few::kGroup;      // Fp2 slices per block
-
-__device__ __forceinline__ few::WaveGroup wave_group(e2* lds) {
-    const int t = threadIdx.x;
-    return few::WaveGroup{lds + (t / few::kGroup) * (few::kSlots * few::kGroup), t % few::kGroup};
-}
+constexpr int kFewLds = few::kWaveLds;      // Fp2 slices per block
+using few::wave_group;
 
 __global__ __launch_bounds__(64) void k_verify_few_lines(const ProofDev* pd, size_t n, Line* out) {
     const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
@@ -36,16 +32,16 @@ __global__ __launch_bounds__(kFewThreads) void k_verify_few_pairing(KeyDev k, co
     if (i < n && g.k == 0) verdict[i] = ok ? 1 : 0;
 }
 // batched check, one pair per group with f unreduced: groups [0, n) e(rho A_i, B_i) over the proof's lines (1 for a proof without ok or
-// with a point at infinity), groups [n, n + kBatchFixed) the fixed pair t against the key's lines, written behind the n proofs
-__global__ __launch_bounds__(kFewThreads) void k_verify_few_batch_miller(KeyDev k, const ProofDev* pd, const VP1* ra, const VP1* fixed, const Line* lines, size_t n, F12* f) {
+// with a point at infinity), groups [n, n + nfixed) the fixed pair t against the key's lines, written behind the n proofs
+__global__ __launch_bounds__(kFewThreads) void k_verify_few_batch_miller(KeyDev k, const ProofDev* pd, const VP1* ra, const VP1* fixed, const Line* lines, size_t n, size_t nfixed, F12* f) {
     __shared__ e2 lds[kFewLds];
     const few::WaveGroup g = wave_group(lds);
     const size_t i = blockIdx.x * (size_t)few::kGroupsPerWave + threadIdx.x / few::kGroup;
     few::Stream st = few::no_stream();
     if (i < n) { if (pd[i].ok) st = few::stream(ra + i, lines + kLineSteps * i, false, pd[i].B.inf != 0, true); }
-    else if (i < n + kBatchFixed) st = few::stream(fixed + (i - n), k.lines[i - n], false, k.qinf[i - n] != 0, true);
+    else if (i < n + nfixed) st = few::stream(fixed + (i - n), k.lines[i - n], false, k.qinf[i - n] != 0, true);
     const e2 v = few::miller_few(g, st, few::no_stream(), few::no_stream(), few::no_stream(), 1);
-    if (i < n + kBatchFixed) few::store12(g, v, f + i);
+    if (i < n + nfixed) few::store12(g, v, f + i);
 }
 // the chunk's verdict from the product of every Miller value (batch_accept of verify_batch_dev.hpp): group 0 works, the rest idle on 1
 __global__ __launch_bounds__(kFewThreads) void k_verify_few_final(const F12* f, uint8_t* flag) {
@@ -69,7 +65,10 @@ void launch_verify_few_pairing(const KeyDev& k, const ProofDev* pd, const Line* 
     if (n) hipLaunchKernelGGL(k_verify_few_pairing, dim3(blocks(n, few::kGroupsPerWave)), dim3(kFewThreads), 0, s, k, pd, lines, verdict, fout, n);
 }
 void launch_verify_few_batch_miller(const KeyDev& k, const ProofDev* pd, const VP1* ra, const VP1* fixed, const Line* lines, size_t n, F12* f, hipStream_t s) {
-    hipLaunchKernelGGL(k_verify_few_batch_miller, dim3(blocks(n + kBatchFixed, few::kGroupsPerWave)), dim3(kFewThreads), 0, s, k, pd, ra, fixed, lines, n, f);
+    hipLaunchKernelGGL(k_verify_few_batch_miller, dim3(blocks(n + kBatchFixed, few::kGroupsPerWave)), dim3(kFewThreads), 0, s, k, pd, ra, fixed, lines, n, (size_t)kBatchFixed, f);
+}
+void launch_verify_few_proof_miller(const KeyDev& k, const ProofDev* pd, const VP1* ra, const Line* lines, size_t n, F12* f, hipStream_t s) {
+    if (n) hipLaunchKernelGGL(k_verify_few_batch_miller, dim3(blocks(n, few::kGroupsPerWave)), dim3(kFewThreads), 0, s, k, pd, ra, (const VP1*)nullptr, lines, n, (size_t)0, f);
 }
 void launch_verify_few_final(const F12* f, uint8_t* flag, hipStream_t s) {
     hipLaunchKernelGGL(k_verify_few_final, dim3(1), dim3(kFewThreads), 0, s, f, flag);

@@ -75,6 +75,12 @@ struct WaveGroup {
     template <class Fn> DEVFN void lane0(Fn fn) const { if (k == 0) fn(); }
     DEVFN static V pick(bool c, const V& a, const V& b) { return sel2(c, a, b); }
 };
+constexpr int kWaveLds = kGroupsPerWave * kSlots * kGroup;      // Fp2 slices of exchange slots per block (one wave)
+// the calling lane's group of a one-wave block whose kWaveLds slices of LDS are lds
+__device__ __forceinline__ WaveGroup wave_group(e2* lds) {
+    const int t = threadIdx.x;
+    return WaveGroup{lds + (t / kGroup) * (kSlots * kGroup), t % kGroup};
+}
 #endif
 
 // ---- what lane k computes (operands: the six published coefficients) ----

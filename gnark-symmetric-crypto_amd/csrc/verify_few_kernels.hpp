@@ -11,6 +11,8 @@ void launch_verify_few_lines(const vfy::ProofDev* pd, size_t n, vfy::Line* out, 
 void launch_verify_few_pairing(const vfy::KeyDev& k, const vfy::ProofDev* pd, const vfy::Line* lines, uint8_t* verdict, vfy::F12* fout, size_t n, hipStream_t s);
 // the miller step of the batched check (k_verify_batch.hip): f[i] for the n proofs, f[n + t] for the fixed pairs
 void launch_verify_few_batch_miller(const vfy::KeyDev& k, const vfy::ProofDev* pd, const vfy::VP1* ra, const vfy::VP1* fixed, const vfy::Line* lines, size_t n, vfy::F12* f, hipStream_t s);
+// the same kernel over the proofs alone: f[i] for the n proofs (the claim-wise check, k_verify_claims.hip, has fixed pairs per part)
+void launch_verify_few_proof_miller(const vfy::KeyDev& k, const vfy::ProofDev* pd, const vfy::VP1* ra, const vfy::Line* lines, size_t n, vfy::F12* f, hipStream_t s);
 // flag[0] = final_exp(f[0]) == 1
 void launch_verify_few_final(const vfy::F12* f, uint8_t* flag, hipStream_t s);
 }  // namespace gsc

@@ -1,7 +1,7 @@
 // GPU verifier in libprove.so: gsc_verify_init, gsc_verify_raw, VerifyBatch, gsc_verify_json, gsc_debug_pairing, and the batched check
-// gsc_verify_raw_batched, gsc_verify_all, VerifyAll (include/libprove.h).
+// gsc_verify_raw_batched, gsc_verify_all, VerifyAll, and the claim-wise batched check gsc_verify_claims, VerifyClaims (include/libprove.h).
 // Verdicts are those of libverify.so's Verify (verifier.cpp); the host only checks sizes and packs bytes (verify_common),
-// decoding and every curve operation run in k_verify.hip (k_verify_batch.hip for the batched check).  Each key owns a non-blocking stream and chunk buffers on one device
+// decoding and every curve operation run in k_verify.hip (k_verify_batch.hip for the batched check, k_verify_claims.hip for the claim-wise one).  Each key owns a non-blocking stream and chunk buffers on one device
 // (GSC_DEVICE, or the first of GSC_DEVICES); calls on the same key are serialised, and nothing here synchronises the device.
 // Routing: a call of at most GSC_VERIFY_FEW_MAX items takes the few-proof kernels (k_verify_few.hip: 8 lanes per proof), larger
 // calls the per-thread ones; gsc_verify_last_path reports which.
@@ -10,6 +10,7 @@
 #include "verify_common.hpp"
 #include "host_ciphers.hpp"
 #include "verify_batch_kernels.hpp"
+#include "verify_claims_kernels.hpp"
 #include "verify_kernels.hpp"
 #include "verify_few_kernels.hpp"
 #include <atomic>
@@ -88,6 +89,19 @@ struct GpuKey {
     DevBuf<uint64_t> rpart;
     DevBuf<F12> f;
     BatchBufs bufs() const { return BatchBufs{ra.p, bok.p, part.p, rpart.p, fixed.p, f.p, bflag.p}; }
+    DevBuf<claims::Part> cparts;         // claim-wise check (k_verify_claims.hip): the buffers of ClaimBufs for one chunk, allocated by
+    DevBuf<G1X> cterms;                  // the key's first gsc_verify_claims call (claim_bufs)
+    DevBuf<uint32_t> crho;
+    DevBuf<VP1> cfixed;
+    DevBuf<F12> cpf;
+    DevBuf<uint8_t> cflag;
+    ClaimBufs claim_bufs() {
+        if (!cparts.p) {
+            cparts.alloc(kChunk); cterms.alloc(kChunk * kBatchSums); crho.alloc(kChunk * 5); cfixed.alloc(kChunk * kBatchFixed);
+            cpf.alloc(kChunk * kBatchFixed); cflag.alloc(kChunk);
+        }
+        return ClaimBufs{cparts.p, cterms.p, crho.p, cfixed.p, cpf.p, cflag.p};
+    }
     ~GpuKey() { if (stream) { (void)hipStreamSynchronize(stream); (void)hipStreamDestroy(stream); } }
 };
 
@@ -315,6 +329,55 @@ long long run_verify_batched(GpuKey& k, const uint8_t* proofs, const uint32_t* l
     return all ? 1 : accepted;
 }
 
+// ---- claim-wise batched check ----
+// Claim j is the items [ends[j-1], ends[j]) (the caller has checked ends).  A chunk's items are cut into parts at the claim and chunk
+// boundaries; every part is one equation on the device with its own randomizers' sums, and a claim is accepted iff every one of its
+// parts holds and every one of its items decodes.  Returns the number of claims accepted; throws HipError on a device error.
+long long run_verify_claims(GpuKey& k, const uint8_t* proofs, const uint32_t* lens, const uint8_t* signals, size_t n, const uint64_t* ends, size_t m,
+                            uint8_t* verdicts) {
+    std::lock_guard<std::mutex> l(k.mu);
+    ck(hipSetDevice(k.device), "hipSetDevice");
+    for (size_t j = 0; j < m; j++) verdicts[j] = (k.fits || ends[j] == (j ? ends[j - 1] : 0)) ? 1 : 0;      // empty claims hold
+    if (n && k.fits) {
+        const bool few = route_few(k, n);
+        const size_t chunk = std::min(n, few ? kFewChunk : kChunk);
+        const ClaimBufs cb = k.claim_bufs();
+        std::vector<uint8_t> win(chunk * V::kWindows), pre(chunk), okh(chunk), flag(chunk);
+        std::vector<uint32_t> rnd(chunk * kRandWords);
+        std::vector<claims::Part> parts;
+        std::vector<size_t> owner;      // the claim of each part
+        size_t first = 0;               // the first claim that may own items from `off` on
+        for (size_t off = 0; off < n; off += chunk) {
+            const size_t cm = std::min(chunk, n - off);
+            parts.clear(); owner.clear();
+            while (ends[first] <= off) first++;
+            for (size_t j = first; j < m; j++) {
+                const size_t lo = std::max<size_t>(j ? ends[j - 1] : 0, off), hi = std::min<size_t>(ends[j], off + cm);
+                if (lo >= off + cm) break;
+                if (lo < hi) { parts.push_back(claims::Part{(uint32_t)(lo - off), (uint32_t)(hi - off)}); owner.push_back(j); }
+            }
+            prep_chunk(k, proofs, lens, signals, off, cm, win, pre);
+            draw_randomizers(rnd.data(), cm, k.has_commitment, off / chunk);      // on the host while k_verify_prep runs
+            hipStream_t s = k.stream;
+            ck(hipMemcpyAsync(k.rnd.p, rnd.data(), cm * kRandWords * sizeof(uint32_t), hipMemcpyHostToDevice, s), "copy");
+            ck(hipMemcpyAsync(cb.parts, parts.data(), parts.size() * sizeof(claims::Part), hipMemcpyHostToDevice, s), "copy");
+            launch_verify_claims(k.kd, k.pd.p, k.rnd.p, cm, parts.size(), k.bufs(), cb, few ? k.few_lines.p : nullptr, s);
+            ck(hipGetLastError(), "k_verify_claims");
+            ck(hipMemcpyAsync(okh.data(), k.bok.p, cm, hipMemcpyDeviceToHost, s), "copy");
+            ck(hipMemcpyAsync(flag.data(), cb.flag, parts.size(), hipMemcpyDeviceToHost, s), "copy");
+            ck(hipStreamSynchronize(s), "verify claims");
+            for (size_t p = 0; p < parts.size(); p++) {
+                bool good = flag[p] == 1;
+                for (uint32_t i = parts[p].begin; good && i < parts[p].end; i++) good = okh[i] == 1;
+                if (!good) verdicts[owner[p]] = 0;
+            }
+        }
+    }
+    long long accepted = 0;
+    for (size_t j = 0; j < m; j++) accepted += verdicts[j];
+    return accepted;
+}
+
 // VerifyBatch / VerifyAll: the well-formed items of a JSON array grouped by algorithm, as gsc_verify_raw's arguments
 struct Grouped {
     std::vector<size_t> where[3];
@@ -430,6 +493,61 @@ int gsc_verify_all(GoUint8 algorithmID, const uint8_t* proofs, const uint32_t* p
     if (!k) return -1;
     try { return (int)run_verify_batched(*k, proofs, proof_lens, signals, n, nullptr, true); }
     catch (const std::exception& e) { printf("gsc_verify_all: %s\n", e.what()); return -2; }
+}
+
+long long gsc_verify_claims(GoUint8 algorithmID, const uint8_t* proofs, const uint32_t* proof_lens, const uint8_t* signals, size_t n,
+                            const uint64_t* claim_ends, size_t m, uint8_t* verdicts) {
+    if (algorithmID > 2) return -1;
+    auto k = key_for(algorithmID);
+    if (!k) return -1;
+    for (size_t j = 0; j < m; j++) if (claim_ends[j] < (j ? claim_ends[j - 1] : 0)) return -3;
+    if ((m ? claim_ends[m - 1] : 0) != n) return -3;
+    if (!m) return 0;
+    try { return run_verify_claims(*k, proofs, proof_lens, signals, n, claim_ends, m, verdicts); }
+    catch (const std::exception& e) { printf("gsc_verify_claims: %s\n", e.what()); memset(verdicts, 0, m); return -2; }
+}
+
+struct Prove_return VerifyClaims(GoSlice params) {
+    std::string out;
+    try {
+        JsonValue root;
+        try { root = json_parse((const char*)params.data, params.len > 0 ? (size_t)params.len : 0); }
+        catch (const JsonSyntaxError& e) { return to_c("{\"Offset\":" + std::to_string(e.offset) + "}"); }
+        if (root.kind != JsonValue::Array) return to_c(json_quote("VerifyClaims expects a JSON array"));
+        const size_t nc = root.items.size();
+        std::vector<uint8_t> verdict(nc, 0);
+        // every well-formed claim split by cipher: per cipher the items of all claims in one gsc_verify_claims call, a claim's share
+        // of them as one claim of that call
+        std::vector<uint8_t> slots[3], sigs[3];
+        std::vector<uint32_t> lens[3];
+        std::vector<uint64_t> ends[3];
+        std::vector<size_t> claim_of[3];
+        for (size_t c = 0; c < nc; c++) {
+            const JsonValue& claim = root.items[c];
+            if (claim.kind != JsonValue::Array || claim.items.empty()) continue;
+            Grouped g = group_requests(claim);
+            if (g.bad) continue;
+            verdict[c] = 1;
+            for (int a = 0; a < 3; a++) if (!g.where[a].empty()) {
+                slots[a].insert(slots[a].end(), g.slots[a].begin(), g.slots[a].end());
+                sigs[a].insert(sigs[a].end(), g.sigs[a].begin(), g.sigs[a].end());
+                lens[a].insert(lens[a].end(), g.lens[a].begin(), g.lens[a].end());
+                ends[a].push_back(lens[a].size());
+                claim_of[a].push_back(c);
+            }
+        }
+        for (int a = 0; a < 3; a++) {
+            const size_t mc = ends[a].size();
+            if (!mc) continue;
+            std::vector<uint8_t> v(mc, 0);
+            const bool ran = gsc_verify_claims((GoUint8)a, slots[a].data(), lens[a].data(), sigs[a].data(), lens[a].size(), ends[a].data(), mc, v.data()) >= 0;   // no key: false
+            for (size_t i = 0; i < mc; i++) if (!ran || !v[i]) verdict[claim_of[a][i]] = 0;
+        }
+        out = "[";
+        for (size_t c = 0; c < nc; c++) { if (c) out += ","; out += verdict[c] ? "true" : "false"; }
+        out += "]";
+    } catch (const std::exception& e) { out = json_quote(e.what()); }
+    return to_c(out);
 }
 
 GoUint8 VerifyAll(GoSlice params) {

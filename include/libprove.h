@@ -176,7 +176,24 @@ extern int gsc_verify_all(GoUint8 algorithmID, const uint8_t *proofs, const uint
 /* JSON array of Verify inputs (VerifyBatch's; ciphers may be mixed, each cipher checked with gsc_verify_all) -> 1 iff Verify would
  * accept every element.  Malformed JSON, a non-array, an empty array, an element that does not parse or a cipher without a key: 0. */
 extern GoUint8 VerifyAll(GoSlice params);
-/* TEST HOOK: the randomizers of the batched check.  seed32 (32 bytes): a fixed function of the seed from now on; all_ones != 0:
+/* Claim-wise batched check (k_verify_claims.hip): the equation above with the claim as its unit.
+ * m claims over n items of one algorithm; claim j is the contiguous run of items [claim_ends[j-1], claim_ends[j]) (claim_ends[-1] = 0).
+ * verdicts[j] = 1 iff Verify would accept every item of claim j (an empty claim: 1).  Each claim is decided by a batched check of its
+ * own (fresh random rho_i, t_i per item, as gsc_verify_raw_batched draws them): no claim's verdict depends on another claim's items, and
+ * there is no proof-by-proof pass.  A claim holding a bad proof is accepted with probability about 2^-128.
+ * Returns the number of claims accepted; -1 no key loaded; -2 device error (every verdict 0); -3 when claim_ends is not non-decreasing
+ * or claim_ends[m-1] != n (m == 0 requires n == 0) - nothing runs and verdicts is not written.
+ * proofs, proof_lens and signals as in gsc_verify_raw; routing and chunks (8192 / 65 536 items) as in every entry point above.  A claim
+ * that crosses a chunk boundary is cut there into parts, each an equation of its own: the claim holds iff all of them do. */
+extern long long gsc_verify_claims(GoUint8 algorithmID, const uint8_t *proofs, const uint32_t *proof_lens, const uint8_t *signals, size_t n,
+                                   const uint64_t *claim_ends, size_t m, uint8_t *verdicts);
+/* JSON array of claims, each a JSON array of Verify inputs (ciphers may be mixed inside a claim) -> malloc'd JSON array of true/false,
+ * one per claim.  A claim that is not an array, is empty, holds an element that does not parse or names a cipher without a key is
+ * false and leaves the others alone.  Each cipher's share of all claims goes through gsc_verify_claims once; a claim's verdict is the
+ * AND of its shares.  A top-level syntax error gives {"Offset":n}, a non-array the quoted string "VerifyClaims expects a JSON array".
+ * Release with Free. */
+extern struct Prove_return VerifyClaims(GoSlice params);
+/* TEST HOOK: the randomizers of the batched checks (gsc_verify_claims included).  seed32 (32 bytes): a fixed function of the seed from now on; all_ones != 0:
  * every rho_i = t_i = 1 (the naive sum, which swapped public inputs of two proofs pass; it takes precedence over a seed); NULL
  * seed and all_ones == 0: the OS CSPRNG again (the default).  Returns 0, -1 when hooks are off. */
 extern int gsc_debug_verify_randomizers(const uint8_t *seed32, int all_ones);

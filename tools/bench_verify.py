@@ -18,6 +18,16 @@ list measures one after the other on the same proofs); --label names
 the build in every line, and --lib-root measures the library of another checkout (the parent commit) with this tool.
 
     python tools/bench_verify.py --latency --sizes 1,8,64,512,4096,8192 --path few [--batched] [--label change] [--out FILE]
+
+--claims S[,S...] times gsc_verify_claims (one equation and one final exponentiation per claim) against gsc_verify_raw and
+gsc_verify_raw_batched on the same items: for ChaCha20 at every size of --sizes (default 8192,65536) and AES-128 at --aes, the items cut
+into claims of S proofs, once all valid and once with one bad proof (signals of another statement) in 1 % of the claims; ms per call,
+the median of --repeat (at least 5) calls after 2.  Measured on one MI355X (profiles/r09_bench_verify_claims.jsonl, DESIGN.md
+§10): at 65 536 ChaCha20 proofs per call gsc_verify_claims beats gsc_verify_raw from claims of 8 proofs (1.17x; 64: 1.26x; sizes
+between 1 and 8 were not measured) and is slower for claims of one proof (0.66x); at 8192 per call it is slower for ChaCha20 at every
+measured size and level with gsc_verify_raw for AES-128 from 8.
+
+    python tools/bench_verify.py --claims 1,8,64 [--sizes 8192,65536] [--aes 8192] [--out FILE]
 """
 import argparse
 import json
@@ -34,6 +44,7 @@ from conftest import golden_bytes  # noqa: E402
 
 NAMES = {0: "chacha20", 1: "aes-128-ctr"}
 THREADS = 16
+SIZES_DEFAULT = "1024,8192,65536"
 
 
 def make_items(g, algo, n, seed):
@@ -127,6 +138,65 @@ def run_latency(g, algo, items, n, repeat, entry, path, label):
     return line
 
 
+def run_claims(g, algo, items, n, size, bad, repeat, label):
+    proofs, lens, sig = items[0][:196 * n], items[1][:n], items[2][:144 * n]
+    ends = list(range(size, n, size)) + [n]
+    m = len(ends)
+    want = [1] * n
+    if bad:                                           # in 1 % of the claims one item gets the signals of the next statement
+        rnd = random.Random(size)
+        sigb = bytearray(sig)
+        for c in rnd.sample(range(m), max(1, m // 100)):
+            lo = ends[c - 1] if c else 0
+            i = rnd.randrange(lo, ends[c])
+            j = (i + 1) % n
+            sigb[144 * i:144 * i + 144] = sig[144 * j:144 * j + 144]
+            want[i] = 0
+        sig = bytes(sigb)
+    want_claims = [int(all(want[a:b])) for a, b in zip([0] + ends[:-1], ends)]
+    line = {"tool": "bench_verify", "mode": "claims", "build": label, "cipher": NAMES[algo], "n": n, "claim_size": size, "claims": m,
+            "bad_claims": m - sum(want_claims), "repeat": repeat, "device": os.environ.get("GSC_DEVICE", "0")}
+    ok = True
+    for entry, fn, expect in (("claims", lambda: g.verify_claims(algo, proofs, lens, sig, ends), want_claims),
+                              ("raw", lambda: g.verify_raw(algo, proofs, lens, sig), want),
+                              ("batched", lambda: g.verify_raw_batched(algo, proofs, lens, sig), want)):
+        fn(); fn()                                    # warm-up: kernel load, buffers, clocks
+        med, out = _median_call(fn, repeat)
+        line[entry + "_ms"] = round(1e3 * med, 3)
+        ok = ok and out == expect
+    line["claims_vs_raw"] = round(line["raw_ms"] / line["claims_ms"], 2)
+    line["claims_vs_batched"] = round(line["batched_ms"] / line["claims_ms"], 2)
+    line["last_path"] = g.verify_last_path(algo)
+    line["verdicts_ok"] = ok
+    return line
+
+
+def main_claims(g, a):
+    claim_sizes = [int(x) for x in a.claims.split(",") if x]
+    sizes = sorted(int(x) for x in (a.sizes if a.sizes != SIZES_DEFAULT else "8192,65536").split(",") if x)
+    lines = []
+    for algo in (0, 1):
+        if algo == 0:
+            pk, r1cs, vk = golden_bytes("pk.chacha20"), golden_bytes("r1cs.chacha20"), golden_bytes("vk.chacha20")
+            ns = sizes
+        elif a.aes:
+            pk, r1cs, vk = aes128_keys()
+            ns = [a.aes]
+        else:
+            continue
+        assert g.init_algorithm(algo, pk, r1cs) and g.verify_init(algo, vk)
+        items = make_items(g, algo, max(ns), 11 + algo)         # one set of proofs; size n takes the first n
+        for n in ns:
+            for size in claim_sizes:
+                for bad in (False, True):
+                    lines.append(run_claims(g, algo, items, n, size, bad, max(5, a.repeat), a.label)); print(json.dumps(lines[-1]), flush=True)
+    if a.out:
+        with open(a.out, "a") as f:
+            for l in lines:
+                f.write(json.dumps(l) + "\n")
+    return 0 if all(l["verdicts_ok"] for l in lines) else 1
+
+
 def aes128_keys():
     cache = os.path.join(ROOT, "build", "keys")
     pkp, vkp = os.path.join(cache, "pk.aes128"), os.path.join(cache, "vk.aes128")
@@ -173,7 +243,7 @@ def main_latency(g, a):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--sizes", default="1024,8192,65536")
+    ap.add_argument("--sizes", default=SIZES_DEFAULT)
     ap.add_argument("--aes", type=int, default=8192, help="AES-128 batch (0: skip)")
     ap.add_argument("--cpu-sample", type=int, default=2048)
     ap.add_argument("--out", default=None)
@@ -181,6 +251,7 @@ def main():
     ap.add_argument("--repeat", type=int, default=3, help="--batched: calls per timing (median)")
     ap.add_argument("--latency", action="store_true", help="per-call milliseconds from n = 1 upwards (with --batched: gsc_verify_raw_batched and gsc_verify_all too)")
     ap.add_argument("--path", default="auto", help="--latency: auto, thread, few or several, e.g. auto,thread,few: force the verifier's kernels (test hook)")
+    ap.add_argument("--claims", default=None, help="claim sizes, e.g. 1,8,64: gsc_verify_claims against gsc_verify_raw and gsc_verify_raw_batched")
     ap.add_argument("--label", default="change", help="--latency: name of the measured build in every line")
     ap.add_argument("--lib-root", default=ROOT, help="checkout whose library is measured (default: this one)")
     a = ap.parse_args()
@@ -189,6 +260,8 @@ def main():
     g = gsc_loader.load()
     if a.latency:
         return main_latency(g, a)
+    if a.claims:
+        return main_claims(g, a)
     lines = []
     assert g.init_algorithm(0, golden_bytes("pk.chacha20"), golden_bytes("r1cs.chacha20"))
     vk = golden_bytes("vk.chacha20")
