@@ -181,38 +181,29 @@ std::string Algorithm::describe() const {
     return out;
 }
 size_t Algorithm::domain_size() const { return impls_[0]->domain_n; }
-void Algorithm::debug_compute_h(const uint8_t* abc_be, size_t m, uint8_t* h_out) {
-    AlgorithmImpl& a = *impls_[0];
-    if (m > a.n_constraints) throw std::runtime_error("debug_compute_h: more rows than constraints");
+// The set-up the two quotient test hooks share: `mats` matrices [m][64] of canonical big-endian values into A, B (, C) of the first lane,
+// `quot(plan, lane, columns)` on them, A back to the host.
+template <class Quot>
+static void debug_quotient(AlgorithmImpl& a, const char* who, const uint8_t* mats_be, size_t mats, size_t m, uint8_t* out, Quot quot) {
+    if (m > a.n_constraints) throw std::runtime_error(std::string(who) + ": more rows than constraints");
     HIP_CHECK(hipSetDevice(a.cfg.device));
     struct Hold { AlgorithmImpl& a; size_t i; ~Hold() { a.release_lane(i); } } hold{a, a.acquire_lane(0)};
     AlgorithmImpl::Lane& ln = *a.lanes[0];
     const size_t B = 64, cnt = m * B;
-    DevBuf<uint8_t> d_be(3 * cnt * 32 + 32);
-    d_be.upload(abc_be, 3 * cnt * 32, ln.stream);
-    launch_fr_from_be(d_be.p, ln.d_A.p, cnt, ln.stream);
-    launch_fr_from_be(d_be.p + cnt * 32, ln.d_B.p, cnt, ln.stream);
-    launch_fr_from_be(d_be.p + 2 * cnt * 32, ln.d_C.p, cnt, ln.stream);
+    DevBuf<uint8_t> d_be(mats * cnt * 32 + 32);
+    d_be.upload(mats_be, mats * cnt * 32, ln.stream);
+    fe* const dst[3] = {ln.d_A.p, ln.d_B.p, ln.d_C.p};
+    for (size_t k = 0; k < mats; k++) launch_fr_from_be(d_be.p + k * cnt * 32, dst[k], cnt, ln.stream);
     NttPlan plan{a.L, a.tw_fwd.p, a.tw_inv.p, a.scale_mid.p, a.scale_out.p, a.dom.p + 5, a.qr.p};
-    HIP_CHECK(launch_compute_h(plan, ln.d_A.p, ln.d_B.p, ln.d_C.p, m, B, ln.stream));
-    HIP_CHECK(hipMemcpyAsync(h_out, ln.d_A.p, a.domain_n * B * 32, hipMemcpyDeviceToHost, ln.stream));
+    HIP_CHECK(quot(plan, ln, B));
+    HIP_CHECK(hipMemcpyAsync(out, ln.d_A.p, a.domain_n * B * 32, hipMemcpyDeviceToHost, ln.stream));
     HIP_CHECK(hipStreamSynchronize(ln.stream));
 }
+void Algorithm::debug_compute_h(const uint8_t* abc_be, size_t m, uint8_t* h_out) {
+    debug_quotient(*impls_[0], "debug_compute_h", abc_be, 3, m, h_out, [m](const NttPlan& plan, AlgorithmImpl::Lane& ln, size_t B) { return launch_compute_h(plan, ln.d_A.p, ln.d_B.p, ln.d_C.p, m, B, ln.stream); });
+}
 void Algorithm::debug_compute_d(const uint8_t* ab_be, size_t m, uint8_t* d_out) {
-    AlgorithmImpl& a = *impls_[0];
-    if (m > a.n_constraints) throw std::runtime_error("debug_compute_d: more rows than constraints");
-    HIP_CHECK(hipSetDevice(a.cfg.device));
-    struct Hold { AlgorithmImpl& a; size_t i; ~Hold() { a.release_lane(i); } } hold{a, a.acquire_lane(0)};
-    AlgorithmImpl::Lane& ln = *a.lanes[0];
-    const size_t B = 64, cnt = m * B;
-    DevBuf<uint8_t> d_be(2 * cnt * 32 + 32);
-    d_be.upload(ab_be, 2 * cnt * 32, ln.stream);
-    launch_fr_from_be(d_be.p, ln.d_A.p, cnt, ln.stream);
-    launch_fr_from_be(d_be.p + cnt * 32, ln.d_B.p, cnt, ln.stream);
-    NttPlan plan{a.L, a.tw_fwd.p, a.tw_inv.p, a.scale_mid.p, a.scale_out.p, a.dom.p + 5, a.qr.p};
-    HIP_CHECK(launch_compute_d(plan, ln.d_A.p, ln.d_B.p, m, B, ln.stream));
-    HIP_CHECK(hipMemcpyAsync(d_out, ln.d_A.p, a.domain_n * B * 32, hipMemcpyDeviceToHost, ln.stream));
-    HIP_CHECK(hipStreamSynchronize(ln.stream));
+    debug_quotient(*impls_[0], "debug_compute_d", ab_be, 2, m, d_out, [m](const NttPlan& plan, AlgorithmImpl::Lane& ln, size_t B) { return launch_compute_d(plan, ln.d_A.p, ln.d_B.p, m, B, ln.stream); });
 }
 // one replica: cut the request list into chunks (multiples of 64 proofs, at most one lane's capacity) and let worker threads pull
 // chunks, each on whichever lane is free.  A call that fits one lane stays whole: cutting a lone 1024-statement AES-128 call over

@@ -1,13 +1,15 @@
-// The engine behind one algorithm on one device: key tables (engine_tables.hip), the per-batch device pipeline (engine_prove.hip)
-// and the lanes that carry batches.  Internal to the library: engine.hpp is the interface capi.cpp sees; engine.hip holds the replica
+// The engine behind one algorithm on one device: key tables (engine_tables.hip), the per-batch device pipeline (engine_prove.hip;
+// its routing policy: chunk_route.hpp) and the lanes that carry batches.  Internal to the library: engine.hpp is the interface capi.cpp sees; engine.hip holds the replica
 // dispatch (Algorithm).  Reference counterpart: the per-cipher prover objects of libraries/prover/impl/provers.go:61-77
 // (baseProver{r1cs, pk}: SetParams -> tables, Prove -> pipeline).
 #pragma once
 #include "engine.hpp"
+#include "chunk_route.hpp"
 #include "formats.hpp"
 #include "kernels.hpp"
 #include "wit_small.hpp"
 #include <atomic>
+#include <chrono>
 #include <cstring>
 #include <condition_variable>
 #include <memory>
@@ -107,7 +109,6 @@ class AlgorithmImpl {
     DevBuf<uint32_t> ws_tiny, ws_parts, ws_bits, ws_twire, ws_levels, ws_rtiny, ws_rgen, ws_rtwire; DevBuf<long long> ws_tcoef, ws_rtcoef;
     DevBuf<uint8_t> ws_cls_a, ws_cls_b, ws_cls_c;      // per constraint row: 0 = byte plane, 1 = 32-byte element
     void init_small(const SolverProgram& sp);
-    static constexpr size_t OVERLAP_QUOTIENT_BELOW = 4096;      // batch calls smaller than this run the quotient beside the wire-set MSMs (prove_chunk)
     std::atomic<uint64_t> small_fallbacks{0};      // chunks that had to be solved again generically (gsc_describe)
     // NTT
     DevBuf<int32_t> tw_fwd, tw_inv, tw_inv_plain, qr; DevBuf<fe> scale_mid, scale_mid_plain, scale_out, dom;   // dom: omega, omega_inv, g, g_inv, n_inv, 16/n
@@ -134,6 +135,10 @@ class AlgorithmImpl {
         float stage_ms[4] = {0, 0, 0, 0}; float msm_z_kernel_ms = 0; size_t last_batch = 0;
         // pinned staging: inputs / randomness / masks up, proof coordinates / flags / status / commitment points and the small result words down
         PinnedBuf<uint8_t> h_in, h_rs, h_mask, h_out, h_flags, h_cpts; PinnedBuf<uint32_t> h_status; PinnedBuf<GlvSplit> h_glv; PinnedBuf<unsigned long long> h_words;
+        // the small result words: [0] the resident solver's two sync words, [1] the small-integer path's flag, [2 .. 46) clock stamps
+        uint32_t* h_fsync() const { return reinterpret_cast<uint32_t*>(h_words.p); }
+        uint32_t& h_wsflag() const { return *reinterpret_cast<uint32_t*>(h_words.p + 1); }
+        unsigned long long* h_clk() const { return h_words.p + 2; }
         KernelStat stat;                // of the chunk this lane proved last
         DevBuf<unsigned long long> d_clk;      // clock stamps: [0, 32) eight waves of the Z kernel (MsmWinArgs::clk); [32, 44) the three transform kernels (GSC_TRACE_HOST)
         size_t n_real = 0;              // statements of the chunk being proved (the batch is padded to a multiple of 64)
@@ -214,8 +219,13 @@ class AlgorithmImpl {
         n = (nbases + per - 1) / per;
         return n ? n : 1;
     }
+    RouteFacts route_facts() const { return RouteFacts{small.ok, has_commitment, quotient_eval, fuse_z_digits, mZfew.nflat != 0, mA.latency_flat(), mB1.latency_flat(), mB2.latency_flat()}; }
+    // one chunk of statements on its way through the stages of prove_chunk: what it is, the route it takes (decided once, read by every stage)
+    struct Chunk {
+        const ProofRequest* reqs; size_t n, B; DebugVectors* dbg; ChunkRoute rt;
+        std::chrono::steady_clock::time_point t_start, t_enqueued, t_done;      // host clock: entry, everything enqueued, results back (GSC_TRACE_HOST)
+    };
     size_t WIN_SLICE = 256;      // bases per slice of the windowed kernel at full batches (measured 64 .. 512: kernel time within 1 %)
-    bool few_solver_wanted(size_t n, size_t B) const { return n <= (size_t)cfg.few_max && B == 64 && cfg.few_solver; }
     struct MsmCtx { hipStream_t stream; uint4* digits; uint8_t* gok; const int8_t* plane = nullptr; size_t plane_rows = 0, plane_stride = 0; };      // plane: the scalars' byte plane (small-integer witness path)
     // the byte plane that stands for the scalar matrix `scalars` in the chunk this lane is proving (none: the matrix holds every row)
     MsmCtx with_plane(MsmCtx c, const Lane& ln, const fe* scalars) const {
@@ -232,14 +242,15 @@ class AlgorithmImpl {
     // scalars: the wire matrix W (Montgomery; wire sets) or h (canonical; Z)
     // The Horner pass of the windowed part is NOT launched here: it is queued in `pending` and flushed together with those of other
     // sets (flush_horner), because each is a serial chain of 254 doublings whose duration does not depend on the batch.
+    // latency: the chunk takes the latency kernels (ChunkRoute::latency), which work on its n_real statements' columns only
     template <class AffT, class XyzzT>
-    void run_msm(Lane& ln, const MsmCtx& ctx, const MsmSet<AffT>& set, const fe* scalars, bool wires, size_t B, size_t n_real, XyzzT* pa, XyzzT* pb, XyzzT* sj, XyzzT* flat, XyzzT* sum, bool timed, bool digits_ready,
+    void run_msm(Lane& ln, const MsmCtx& ctx, const MsmSet<AffT>& set, const fe* scalars, bool wires, size_t B, size_t n_real, bool latency, XyzzT* pa, XyzzT* pb, XyzzT* sj, XyzzT* flat, XyzzT* sum, bool timed, bool digits_ready,
                  MsmHornerJobs& pending);
     int set_index(const MsmSet<G1Aff>& set) const { const MsmSet<G1Aff>* all[Lane::NSETS] = {&mA, &mB1, &mK, &mZ, &mPed, &mPedSigma, &mZfew, &mC}; for (int k = 0; k < Lane::NSETS; k++) if (all[k] == &set) return k; return 0; }
     // side = true: on the lane's side stream with scratch buffers of its own (flat sets of calls with a handful of statements only)
     // digits_ready: the windowed part's digits are already in the lane's digit buffer (fuse_z_digits): no recoding pass
-    void run_msm_g1(Lane& ln, const MsmSet<G1Aff>& set, const fe* scalars, int mont, size_t B, G1Xyzz* sum, bool timed = false, bool side = false, bool digits_ready = false);
-    void run_msm_g2(Lane& ln, const MsmSet<G2Aff>& set, const fe* scalars, int mont, size_t B, G2Xyzz* sum, bool side = false);
+    void run_msm_g1(Lane& ln, const Chunk& ck, const MsmSet<G1Aff>& set, const fe* scalars, int mont, G1Xyzz* sum, bool timed = false, bool side = false, bool digits_ready = false);
+    void run_msm_g2(Lane& ln, const Chunk& ck, const MsmSet<G2Aff>& set, const fe* scalars, int mont, G2Xyzz* sum, bool side = false);
     template <class AffT> void flush_horner(MsmHornerJobs& pending, size_t B, hipStream_t s) { launch_msm_horner<AffT>(pending, B, s); pending.n = 0; }
 
     void fetch_column(Lane& ln, const fe* mat, size_t rows, size_t B, size_t col, std::vector<uint8_t>& out);
@@ -250,7 +261,20 @@ class AlgorithmImpl {
     // TEST HOOK: non-zero bytes left in those areas over all lanes (after draining their streams)
     size_t secret_residue();
 
+    // allow_few_solver / allow_small = false: the retries after the resident solver gave up / a small-integer prediction failed
     void prove_chunk(Lane& ln, const ProofRequest* reqs, size_t n, ProofResult* results, DebugVectors* dbg, bool allow_few_solver = true, bool allow_small = true);
+    // its stages, in this order; each enqueues on the lane's streams up to the stage event named (Lane::ev)
+    void stage_upload(Lane& ln, const Chunk& ck);           // staging, the scalar split of a latency call: ev[0]
+    void stage_witness(Lane& ln, const Chunk& ck);          // W, a, b, c (and the commitment in between): ev[1]
+    void stage_early_sums(Lane& ln, const Chunk& ck);       // latency call: A, B1, B2 and the scalar multiplications on the side streams
+    void stage_quotient(Lane& ln, const Chunk& ck);         // h or d over a: ev[2]
+    void stage_msms(Lane& ln, const Chunk& ck);             // ev[3]
+    void stage_assembly(Lane& ln, Chunk& ck);               // ev[4], results to the host, the secrets wiped; waits for the lane
+    void stage_stat(Lane& ln, const Chunk& ck);             // stage times and the dominant kernel: ln.stat, last_stat
+    void run_levels(Lane& ln, const Chunk& ck, SolverArgs& sa, uint32_t from, uint32_t to);      // witness levels [from, to) with the generic solver kernels
+    void solve_small(Lane& ln, const Chunk& ck);            // the whole witness with the small-integer kernels
+    void dump_solver_trace(Lane& ln, const unsigned long long* d_trace);      // GSC_SOLVER_TRACE
+    void trace_chunk(Lane& ln, const Chunk& ck);            // GSC_TRACE_HOST
 
     // gnark proof.WriteTo: Ar | Bs | Krs compressed, u32be nbCommitments, commitments, CommitmentPok
     void serialize(const uint8_t* o, uint8_t flags, uint32_t status, const uint8_t* commitment_xy, const uint8_t* pok_xy, ProofResult& res) const;
