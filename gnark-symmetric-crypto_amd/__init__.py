@@ -20,7 +20,7 @@ CHACHA20, AES_128, AES_256 = 0, 1, 2                       # prove_impl.go:15-19
 ALGORITHM_NAMES = {0: "chacha20", 1: "aes-128-ctr", 2: "aes-256-ctr"}   # prove_impl.go:21-25
 
 EXPORTS = ["enforce_binding", "InitAlgorithm", "Free", "Prove", "ProveBatch", "gsc_prove_raw", "gsc_setup",
-           "gsc_set_deterministic_randomness", "gsc_debug_prove", "gsc_debug_vector", "gsc_describe", "gsc_last_stage_ms", "gsc_last_dominant_kernel", "gsc_last_kernel_clock", "gsc_debug_field_ops", "gsc_debug_limb_ops", "gsc_debug_curve_ops", "gsc_debug_compute_h", "gsc_debug_compute_d", "gsc_debug_secret_residue", "gsc_debug_clock_trace", "gsc_debug_glv_split",
+           "gsc_set_deterministic_randomness", "gsc_debug_prove", "gsc_debug_vector", "gsc_describe", "gsc_last_stage_ms", "gsc_last_dominant_kernel", "gsc_last_kernel_clock", "gsc_debug_field_ops", "gsc_debug_limb_ops", "gsc_debug_curve_ops", "gsc_debug_tower_ops", "gsc_debug_compute_h", "gsc_debug_compute_d", "gsc_debug_secret_residue", "gsc_debug_clock_trace", "gsc_debug_glv_split",
            "gsc_verify_init", "gsc_verify_raw", "VerifyBatch", "gsc_debug_pairing",
            "gsc_verify_raw_batched", "gsc_verify_all", "VerifyAll", "gsc_debug_verify_randomizers",
            "gsc_verify_json", "gsc_verify_last_path", "gsc_debug_verify_path", "gsc_debug_pairing_few",
@@ -78,6 +78,8 @@ def lib():
         L.gsc_debug_field_ops.argtypes = [C.c_int, C.c_int, C.c_char_p, C.c_char_p, C.c_void_p, C.c_size_t, C.c_int]
         L.gsc_debug_limb_ops.restype = C.c_int
         L.gsc_debug_limb_ops.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+        L.gsc_debug_tower_ops.restype = C.c_int
+        L.gsc_debug_tower_ops.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         L.gsc_debug_curve_ops.restype = C.c_int
         L.gsc_debug_curve_ops.argtypes = [C.c_int, C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]
         L.gsc_verify_init.restype = C.c_int
@@ -312,6 +314,30 @@ def debug_curve_ops(group: int, op: int, pts: bytes, inf: bytes, lam: bytes, n: 
     if lib().gsc_debug_curve_ops(group, op, pts, inf, lam, n, k, out, flags):
         raise RuntimeError("gsc_debug_curve_ops failed")
     return out.raw, flags.raw
+
+
+def tower_words(path: int, op: int):
+    """(int32 words one element of gsc_debug_tower_ops reads, words it writes); the table of include/libprove.h"""
+    if not (0 <= op < 30 if path == 0 else path == 1 and 16 <= op <= 25):
+        raise RuntimeError("gsc_debug_tower_ops: path %d has no op %d" % (path, op))
+    win = {0: 9, 11: 9, 13: 9, 1: 20, 2: 36, 3: 36, 6: 36, 28: 36, 29: 36, 8: 27, 10: 19, 16: 216, 18: 162, 26: 54, 27: 90}.get(op, 108 if op >= 16 else 18)
+    wout = {0: 9, 1: 9, 11: 9, 13: 9, 15: 0, 25: 0, 26: 108, 27: 108, 28: 72, 29: 5508}.get(op, (144 if path == 1 else 108) if op >= 16 else 18)
+    return win, wout
+
+
+def debug_tower_ops(path: int, op: int, rows):
+    """TEST HOOK: rows: one flat tuple of raw int32 words per element (layout: include/libprove.h gsc_debug_tower_ops) -> (list of flat
+    tuples of the words the device wrote, list of flags).  path 0: verify_dev.hpp per thread; path 1: verify_few_dev.hpp per 8-lane group."""
+    win, wout = tower_words(path, op)
+    n = len(rows)
+    assert all(len(r) == win for r in rows)
+    src = (C.c_int32 * max(1, win * n))(*[w for r in rows for w in r])
+    out = (C.c_int32 * max(1, wout * n))()
+    flags = C.create_string_buffer(max(1, n))
+    if lib().gsc_debug_tower_ops(path, op, src, n, out, flags):
+        raise RuntimeError("gsc_debug_tower_ops failed")
+    flat = list(out)
+    return [tuple(flat[wout * i:wout * (i + 1)]) for i in range(n)], list(flags.raw[:n])
 
 
 def debug_glv_split(k: int):

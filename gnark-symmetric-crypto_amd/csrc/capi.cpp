@@ -462,6 +462,15 @@ int gsc_debug_curve_ops(int group, int op, const uint8_t* pts, const uint8_t* in
     catch (const std::exception& e) { printf("%s\n", e.what()); return -1; }
 }
 
+int gsc_debug_tower_ops(int path, int op, const int32_t* in, size_t n, int32_t* out, uint8_t* flags) {
+    if (hooks_refused("gsc_debug_tower_ops") || (n && (!in || !out || !flags))) return -1;
+    try {
+        if (debug_tower_ops(config_from_env().device, path, op, in, n, out, flags)) return 0;
+        printf("gsc_debug_tower_ops: path %d has no op %d\n", path, op);
+        return -1;
+    } catch (const std::exception& e) { printf("%s\n", e.what()); return -1; }
+}
+
 int gsc_debug_clock_trace(uint32_t n, uint32_t interval_us, unsigned long long* out) {
     if (hooks_refused("gsc_debug_clock_trace") || !out || !n) return -1;
     try { debug_clock_trace(config_from_env().device, n, interval_us, out); return 0; }

@@ -120,6 +120,27 @@ void debug_curve_ops(int device, int group, int op, const uint8_t* pts, const ui
     HIP_CHECK(hipMemcpy(flags, dflags.p, n, hipMemcpyDeviceToHost));
 }
 
+bool debug_tower_ops(int device, int path, int op, const int32_t* in, size_t n, int32_t* out, uint8_t* flags) {
+    int iw, ow;
+    if (!tower_ops_words(path, op, &iw, &ow)) return false;
+    if (n > (1u << 16)) throw std::runtime_error("gsc_debug_tower_ops: too many elements");
+    if (!n) return true;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) throw std::runtime_error("no HIP device available");
+    HIP_CHECK(hipSetDevice(device));
+    DevBuf<int32_t> din((size_t)iw * n), dout((size_t)(ow ? ow : 1) * n);
+    DevBuf<uint8_t> dflags(n);
+    HIP_CHECK(hipMemcpy(din.p, in, 4 * (size_t)iw * n, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemset(dout.p, 0, 4 * (size_t)(ow ? ow : 1) * n));
+    HIP_CHECK(hipMemset(dflags.p, 0, n));
+    if (!launch_tower_ops(path, op, din.p, dout.p, dflags.p, n, nullptr)) return false;
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipDeviceSynchronize());
+    if (ow) HIP_CHECK(hipMemcpy(out, dout.p, 4 * (size_t)ow * n, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(flags, dflags.p, n, hipMemcpyDeviceToHost));
+    return true;
+}
+
 void debug_clock_trace(int device, uint32_t n, uint32_t interval_us, unsigned long long* out) {
     HIP_CHECK(hipSetDevice(device));
     hipStream_t st; HIP_CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));

@@ -39,6 +39,10 @@ void launch_ntt_constants(const fe* omega, const fe* omega_inv, const fe* n_inv,
 bool launch_field_ops(int field, int op, const fe* a, const fe* b, fe* out, size_t n, int chain, hipStream_t s);
 bool launch_limb_ops(int field, int op, const int32_t* a, const int32_t* b, const int32_t* c, const int32_t* d, int32_t* out, size_t n, hipStream_t s);
 bool launch_curve_ops(int group, int op, size_t k, const fe* pts, const uint8_t* inf, const fe* lam, fe* out, uint8_t* flags, size_t n, hipStream_t s);
+// TEST HOOK (k_debug_tower.hip): one operation of the verifier's tower per element on raw limbs.  tower_ops_words: the int32 words an element of
+// (path, op) reads and writes, false when there is no such path / op; launch_tower_ops: false likewise (nothing is launched then).
+bool tower_ops_words(int path, int op, int* in_words, int* out_words);
+bool launch_tower_ops(int path, int op, const int32_t* in, int32_t* out, uint8_t* flags, size_t n, hipStream_t s);
 void launch_wave_inverse(const fe* a, fe* out, size_t n, hipStream_t s);      // TEST HOOK (field 1, op 8 of launch_field_ops): k_solver's division, 64 values per inversion
 
 // TEST HOOK / diagnostics: one resident wave records n samples {100 MHz clock, shader clock} `interval` 100 MHz ticks apart into out[2 n]

@@ -9,6 +9,8 @@
 //
 // Value discipline: every Fp / Fp2 value handed to a product is tight (limbs 0..7 in [0, 2^29)) with |value| < 5p; products and
 // red() return |value| < 2.01p, so sums of two such values may be multiplied directly and longer sums go through red() first.
+// Two operations hand parts of their operand on untouched, which keep the operand's bound: the even coefficients of conj12 and
+// coefficient 0 of frob12_2 (whose other coefficients are scale2's unreduced products, in (-p, 2p)).
 #pragma once
 #include "bn254_fp29.hpp"
 #include "sha256_dev.hpp"
@@ -94,7 +96,8 @@ DEVFN e2 neg2(const e2& a) { return red2(F2::neg(a)); }
 DEVFN e2 mul2(const e2& a, const e2& b) { return red2(F2::mul(a, b)); }
 DEVFN e2 sqr2(const e2& a) { return red2(F2::sqr(a)); }
 DEVFN e2 scale2(const e2& a, const e1& k) { return e2{F::mul(a.a0, k), F::mul(a.a1, k)}; }
-DEVFN e2 conj2(const e2& a) { return e2{a.a0, neg1(a.a1)}; }
+DEVFN e2 conj2(const e2& a) { return e2{red(a.a0), neg1(a.a1)}; }      // both halves reduced: an operand that was a lazy sum does not stay one
+DEVFN e2 conj2p(const e2& a) { return e2{a.a0, neg1(a.a1)}; }           // for the operand of a product: the real half goes in as it came
 DEVFN e2 mulxi(const e2& a) { return e2{lin(a.a0, 9, a.a1, -1), lin(a.a0, 1, a.a1, 9)}; }     // (9 + u) a
 DEVFN e2 small2(const e2& a, int k) { return e2{lin(a.a0, k, a.a1, 0), lin(a.a1, k, a.a0, 0)}; }
 DEVFN bool zero2(const e2& a) { return zero1(a.a0) && zero1(a.a1); }
@@ -307,7 +310,7 @@ DEVFN F12 conj12(const F12& a) { F12 r = a; r.c[1] = neg2(a.c[1]); r.c[3] = neg2
 DEVNOINL F12 frob12(const F12& a) {      // x^p
     F12 r; r.c[0] = conj2(a.c[0]);
 #pragma unroll
-    for (int i = 1; i < 6; i++) r.c[i] = mul2(conj2(a.c[i]), frob1(i));
+    for (int i = 1; i < 6; i++) r.c[i] = mul2(conj2p(a.c[i]), frob1(i));
     return r;
 }
 DEVFN F12 frob12_2(const F12& a) {    // x^(p^2)
@@ -414,8 +417,8 @@ DEVNOINL Line add_step(G2J& T, const e2& qx, const e2& qy) {
 }
 // pi(Q) and -pi^2(Q) on the twist (libverify's q1 / q2)
 DEVFN void frob_points(const VP2& q, e2& q1x, e2& q1y, e2& q2x, e2& q2y) {
-    q1x = mul2(conj2(q.x), frob_g2()); q1y = mul2(conj2(q.y), frob_g3());
-    q2x = mul2(conj2(q1x), frob_g2()); q2y = neg2(mul2(conj2(q1y), frob_g3()));
+    q1x = mul2(conj2p(q.x), frob_g2()); q1y = mul2(conj2p(q.y), frob_g3());
+    q2x = mul2(conj2p(q1x), frob_g2()); q2y = neg2(mul2(conj2p(q1y), frob_g3()));
 }
 // the kLineSteps lines of the Miller loop for one G2 point (the fixed points of a key; also how the loop itself walks)
 DEVFN void lines_of(const VP2& q, Line* out) {

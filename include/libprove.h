@@ -103,6 +103,26 @@ extern int gsc_debug_limb_ops(int field, int op, const int32_t *a, const int32_t
  * first addition, bit 2 (op 2) ZZ was 0 mod p after the last one: then there is no result.  0 on success, -1 on error. */
 extern int gsc_debug_curve_ops(int group, int op, const uint8_t *pts, const uint8_t *inf, const uint8_t *lam, size_t n, size_t k, uint8_t *out, uint8_t *flags);
 
+/* TEST HOOK: one operation of the GPU verifier's arithmetic per element on RAW limbs: the Fp / Fp2 helpers, the Fp12 tower, the Miller steps
+ * and the final exponentiation of csrc/verify_dev.hpp (path 0: one element per thread) and the Fp12 operations of its lane-sliced twin
+ * csrc/verify_few_dev.hpp (path 1: one element per group of 8 lanes; a group without an element computes on the identity, as in
+ * production).  An Fp value is 9 int32 limbs in the 2^261 Montgomery domain, used exactly as given; Fp2 = (real, imaginary) = 18 words;
+ * Fp12 = the coefficients of w^0..w^5 = 108 words; a line = (a, b, c) = 54 words; k, ka, kb are one int32 each.  The caller keeps the
+ * operands inside the discipline verify_dev.hpp documents (tight limbs, |value| < 5p).  in / out: n elements, the words of one element:
+ *   op  0 red(a)  1 lin(a, b, ka, kb) = ka a + kb b               in 9 / 20, out 9
+ *       2 add2(a, b)  3 sub2(a, b)  6 mul2(a, b)                  in 36, out 18
+ *       4 neg2  5 conj2  7 sqr2  9 mulxi  12 inv2                 in 18, out 18
+ *       8 scale2(a, k in Fp)  10 small2(a, k)                     in 27 / 19, out 18
+ *       11 inv1  13 sqrt1 (flag: a root exists; out: a root, else zeros)       in 9, out 9
+ *       14 sqrt2 (flag and out likewise)  15 lex_large2 (flag)    in 18, out 18 / 0
+ *       16 mul12(a, b)  17 sqr12  18 mul_line(f, c0, c1, c3)      in 216 / 108 / 162, out 108
+ *       19 conj12  20 frob12  21 frob12_2  22 inv12  23 pow_x  24 final_exp  25 is_one12 (flag, out 0)       in 108, out 108
+ *       26 dbl_step(X, Y, Z)  27 add_step(X, Y, Z, xQ, yQ): T' (X, Y, Z) and the line      in 54 / 90, out 108
+ *       28 frob_points(xQ, yQ): pi(Q), -pi^2(Q)  29 lines_of(xQ, yQ): the 102 lines of the Miller loop      in 36, out 72 / 5508
+ * Path 1 has ops 16..25 only and returns 144 words per Fp12 value: the slice of each of the 8 lanes (lanes 6 and 7 hold zero).
+ * flags: n bytes, 0 for an op without a flag.  0 on success; -1 for a path / op that does not exist (nothing is launched then) and on error. */
+extern int gsc_debug_tower_ops(int path, int op, const int32_t *in, size_t n, int32_t *out, uint8_t *flags);
+
 /* TEST HOOK: the quotient-polynomial kernels (computeH) alone, on caller-supplied vectors, 64 independent columns at once.
  * abc_be: a, b, c one after the other, each [m][64] canonical big-endian 32-byte values (m <= constraints of the algorithm).
  * h_out (cap bytes, at least domain*64*32): [domain][64] canonical little-endian values, row k = coefficient bitrev(k).

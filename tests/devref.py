@@ -1,5 +1,6 @@
-"""References and case tables for the per-operation tests of the device's field and curve code (gsc_debug_limb_ops,
-gsc_debug_curve_ops; include/libprove.h).  Everything here is Python integers; nothing calls the oracle or the library.
+"""References and case tables for the per-operation tests of the device's field and curve code and of the verifier's tower
+(gsc_debug_limb_ops, gsc_debug_curve_ops, gsc_debug_tower_ops; include/libprove.h).  Everything here is Python integers; nothing calls
+the oracle or the library.
 
 Radix-2^29 products are predicted LIMB FOR LIMB: for the integers A, B (C, D) the raw limbs denote, N = A*B, A^2 or A*B - C*D,
 m = -N / p mod 2^261 and V = (N + m p) / 2^261 exactly; the result's limbs 0..7 are V's 29-bit digits and limb 8 is the signed rest
@@ -13,7 +14,13 @@ mul: T1/T1s x T1/T1s and T2 x T1/T1s; sqr: T1s; fmms: four T1s; norm: |limb| <= 
 freeze_near: value in (-2p, 6p), |limb| < 2^30.
 
 The curve reference is affine chord-and-tangent arithmetic: G1 y^2 = x^3 + 3 over Fp, G2 y^2 = x^3 + 3/(9+u) over Fp[u]/(u^2+1).
+
+The tower section (further down) takes raw limbs as the integers they denote and compares VALUES: Fp2 by the obvious arithmetic, Fp12
+by schoolbook products in Fp2[w]/(w^6 - (9+u)) with Frobenius and the exponentiations as plain powers, the Miller steps by affine
+arithmetic on the twist, the whole pairing by generic lines on E(Fp12); on the limbs themselves it asserts the bounds verify_dev.hpp
+documents.
 """
+import functools
 import os
 import random
 import struct
@@ -409,6 +416,581 @@ def curve_cases(group):
     return cases
 
 
+# ---------------------------------------------------------------- the verifier's tower ----------------------------------------------------------------
+# gsc_debug_tower_ops (include/libprove.h): raw limbs in the 2^261 Montgomery domain.  A raw integer X stands for the field element
+# X / 2^261 mod p; the references below work on field elements (Fp: int, Fp2: (real, imaginary), Fp12: six Fp2, the coefficients of
+# w^0..w^5 in Fp2[w] / (w^6 - (9 + u))) and know nothing of the device's formulas.
+(T_RED, T_LIN, T_ADD2, T_SUB2, T_NEG2, T_CONJ2, T_MUL2, T_SQR2, T_SCALE2, T_MULXI, T_SMALL2, T_INV1, T_INV2, T_SQRT1, T_SQRT2, T_LEX_LARGE2,
+ T_MUL12, T_SQR12, T_MUL_LINE, T_CONJ12, T_FROB12, T_FROB12_2, T_INV12, T_POW_X, T_FINAL_EXP, T_IS_ONE12,
+ T_DBL_STEP, T_ADD_STEP, T_FROB_POINTS, T_LINES_OF) = range(30)
+TOWER_NAMES = ["red", "lin", "add2", "sub2", "neg2", "conj2", "mul2", "sqr2", "scale2", "mulxi", "small2", "inv1", "inv2", "sqrt1", "sqrt2", "lex_large2",
+               "mul12", "sqr12", "mul_line", "conj12", "frob12", "frob12_2", "inv12", "pow_x", "final_exp", "is_one12",
+               "dbl_step", "add_step", "frob_points", "lines_of"]
+TOWER_PATH1_OPS = list(range(T_MUL12, T_IS_ONE12 + 1))
+TOWER_HEAVY = (T_POW_X, T_FINAL_EXP, T_LINES_OF)      # at most 16 elements per path
+GROUP_COUNTS = (1, 7, 8, 9, 65)                        # path 1: one group, a wave less one, a full wave, a ragged second wave, nine waves
+LINE_STEPS = 102
+BN_X = 4965661367192848881
+ATE_LOOP = 6 * BN_X + 2
+FINAL_EXPONENT = (P ** 12 - 1) // R
+MONT = 1 << 261
+RINV = pow(MONT, -1, P)
+XI = (9, 1)
+
+
+def tower_words(path, op):
+    """(words in, words out) of one element; the table of include/libprove.h"""
+    win = {T_RED: 9, T_INV1: 9, T_SQRT1: 9, T_LIN: 20, T_ADD2: 36, T_SUB2: 36, T_MUL2: 36, T_FROB_POINTS: 36, T_LINES_OF: 36, T_SCALE2: 27, T_SMALL2: 19,
+           T_MUL12: 216, T_MUL_LINE: 162, T_DBL_STEP: 54, T_ADD_STEP: 90}.get(op, 108 if op >= T_MUL12 else 18)
+    wout = {T_RED: 9, T_LIN: 9, T_INV1: 9, T_SQRT1: 9, T_LEX_LARGE2: 0, T_IS_ONE12: 0, T_DBL_STEP: 108, T_ADD_STEP: 108, T_FROB_POINTS: 72,
+            T_LINES_OF: 54 * LINE_STEPS}.get(op, (144 if path == 1 else 108) if op >= T_MUL12 else 18)
+    return win, wout
+
+
+# ---- Fp2 / Fp12 references ----
+def f2_pow(a, e):
+    r = (1, 0)
+    for bit in bin(e)[2:]:
+        r = f_mul(r, r)
+        if bit == "1":
+            r = f_mul(r, a)
+    return r
+
+
+F12_ZERO, F12_ONE = ((0, 0),) * 6, ((1, 0),) + ((0, 0),) * 5
+
+
+def f12_mul(a, b):
+    """schoolbook in Fp2[w] / (w^6 - xi); the sums stay unreduced integers until the end"""
+    t0, t1 = [0] * 11, [0] * 11
+    for i, (x0, x1) in enumerate(a):
+        if x0 or x1:
+            for j, (y0, y1) in enumerate(b):
+                t0[i + j] += x0 * y0 - x1 * y1; t1[i + j] += x0 * y1 + x1 * y0
+    out = []
+    for k in range(6):
+        h0, h1 = (t0[k + 6], t1[k + 6]) if k < 5 else (0, 0)
+        out.append(((t0[k] + 9 * h0 - h1) % P, (t1[k] + h0 + 9 * h1) % P))
+    return tuple(out)
+
+
+def f12_add(a, b): return tuple(f_add(x, y) for x, y in zip(a, b))
+def f12_sub(a, b): return tuple(f_sub(x, y) for x, y in zip(a, b))
+def f12_conj(a): return tuple(f_neg(c) if i & 1 else c for i, c in enumerate(a))      # w -> -w
+
+
+@functools.lru_cache(maxsize=None)      # the GPU tests put the same elements through both paths and several group counts
+def f12_pow(a, e):
+    r = F12_ONE
+    for bit in bin(e)[2:]:
+        r = f12_mul(r, r)
+        if bit == "1":
+            r = f12_mul(r, a)
+    return r
+
+
+def f12_inv(a):
+    """through the norms of the tower: N = a conj(a) lies in Fp6 = Fp2[v] / (v^3 - xi) (v = w^2), N's norm to Fp2 is N N' N'' with the two
+    other roots of unity of v's minimal polynomial folded in by the adjugate below; 0 -> 0 as the device's Fermat inversions do"""
+    if a == F12_ZERO:
+        return F12_ZERO
+    n = f12_mul(a, f12_conj(a))
+    assert n[1] == n[3] == n[5] == (0, 0)
+    x, y, z = n[0], n[2], n[4]      # x + y v + z v^2
+    # adjugate of multiplication by N in the basis 1, v, v^2
+    t0 = f_sub(f_mul(x, x), f_mul(XI, f_mul(y, z)))
+    t1 = f_sub(f_mul(XI, f_mul(z, z)), f_mul(x, y))
+    t2 = f_sub(f_mul(y, y), f_mul(x, z))
+    d = f_inv(f_add(f_mul(x, t0), f_mul(XI, f_add(f_mul(z, t1), f_mul(y, t2)))))
+    ninv = (f_mul(t0, d), (0, 0), f_mul(t1, d), (0, 0), f_mul(t2, d), (0, 0))
+    r = f12_mul(f12_conj(a), ninv)
+    assert f12_mul(r, a) == F12_ONE
+    return r
+
+
+def f12_embed(c, k):
+    """c w^k for c in Fp2"""
+    return tuple(c if i == k else (0, 0) for i in range(6))
+
+
+# ---- the generic reduced pairing: E(Fp12): y^2 = x^3 + 3, Q untwisted, affine chord-and-tangent lines evaluated at P ----
+def _e12_line_and_sum(t, q, p):
+    """the line through t and q (the tangent when they are equal) at p, and t + q; points are pairs of Fp12 elements"""
+    (x1, y1), (x2, y2) = t, q
+    if x1 == x2:
+        assert y1 == y2
+        lam = f12_mul(f12_mul(f12_embed((3, 0), 0), f12_mul(x1, x1)), f12_inv(f12_add(y1, y1)))
+    else:
+        lam = f12_mul(f12_sub(y2, y1), f12_inv(f12_sub(x2, x1)))
+    x3 = f12_sub(f12_sub(f12_mul(lam, lam), x1), x2)
+    y3 = f12_sub(f12_mul(lam, f12_sub(x1, x3)), y1)
+    line = f12_sub(f12_sub(p[1], y1), f12_mul(lam, f12_sub(p[0], x1)))
+    return line, (x3, y3)
+
+
+def pairing_reference(p1, q2):
+    """e(P, Q)^((p^12 - 1) / r) for affine P in G1 and Q in G2 (on the twist) -> twelve integers as gsc.debug_pairing returns them"""
+    pp = (f12_embed((p1[0][0], 0), 0), f12_embed((p1[1][0], 0), 0))
+    q = (f12_embed(q2[0], 2), f12_embed(q2[1], 3))      # (x' w^2, y' w^3) lies on y^2 = x^3 + 3
+    assert f12_mul(q[1], q[1]) == f12_add(f12_mul(f12_mul(q[0], q[0]), q[0]), f12_embed((3, 0), 0))
+    f, t = F12_ONE, q
+    for bit in bin(ATE_LOOP)[3:]:
+        line, t = _e12_line_and_sum(t, t, pp)
+        f = f12_mul(f12_mul(f, f), line)
+        if bit == "1":
+            line, t = _e12_line_and_sum(t, q, pp)
+            f = f12_mul(f, line)
+    q1 = (f12_pow(q[0], P), f12_pow(q[1], P))
+    q2n = (f12_pow(q1[0], P), f12_sub(F12_ZERO, f12_pow(q1[1], P)))
+    line, t = _e12_line_and_sum(t, q1, pp)
+    f = f12_mul(f, line)
+    line, t = _e12_line_and_sum(t, q2n, pp)
+    f = f12_mul(f, line)
+    r = f12_pow(f, FINAL_EXPONENT)
+    return tuple(v for c in r for v in c)
+
+
+_pairing_cache = {}
+
+
+def pairing_cases():
+    """[(P, Q, reduced pairing)] for P = [a]G1, Q = [b]G2: a, b from 1, 2, r - 1, a 40-bit and a 250-bit value; one pair with P = -G1"""
+    if not _pairing_cache:
+        rnd = random.Random(700)
+        s40, s250 = rnd.getrandbits(40) | 1 << 39, rnd.getrandbits(250) | 1 << 249
+        pairs = [(1, 1), (2, 1), (1, 2), (R - 1, 2), (2, R - 1), (s40, s250), (s250, s40), (s40, 1), (R - 1, s250)]
+        assert pairs[3][0] == R - 1      # P = -G1
+        out = []
+        for a, b in pairs:
+            pt, qt = ec_mul(a, G1_GEN), ec_mul(b, G2_GEN)
+            out.append((pt, qt, pairing_reference(pt, qt)))
+        assert out[3][0] == ec_neg(G1_GEN)
+        _pairing_cache["cases"] = out
+    return _pairing_cache["cases"]
+
+
+# ---- raw operands ----
+def to_mont(v): return v * MONT % P
+def raw_value(x): return x * RINV % P
+def raw2(x): return (raw_value(x[0]), raw_value(x[1]))
+
+
+def is_reduced(l):
+    """what products and red() return: limbs 0..7 in [0, 2^29), |value| < 2.01 p"""
+    return all(0 <= v <= M29 for v in l[:8]) and 100 * abs(value(l)) < 201 * P
+
+
+def is_product(l):
+    """what bn254_fp29.hpp documents for Field29::mul: tight, in (-p, 2p)"""
+    return all(0 <= v <= M29 for v in l[:8]) and -P < value(l) < 2 * P
+
+
+def field_values(rnd, n):
+    """the canonical values of tests/test_gpu_field.py::_values"""
+    edge = [0, 1, 2, P - 1, P - 2, (P - 1) // 2, (P + 1) // 2, 2 ** 29 - 1, 2 ** 29, 2 ** 232, 2 ** 232 - 1, 2 ** 253, P - 2 ** 29, ALL_LIMBS]
+    return [e % P for e in edge] + [rnd.randrange(P) for _ in range(max(0, n - len(edge)))]
+
+
+def _admitted(x):
+    """verify_dev.hpp: every value handed to a product is tight with |value| < 5p"""
+    l = tight(x)
+    assert in_class(l, "T1") and abs(x) < 5 * P and value(l) == x
+    return x
+
+
+def raw_operands(rnd, n):
+    """n raw integers: canonical Montgomery images of field_values; values just inside +-5p; sums and differences of two values just inside
+    +-2.01p (the lazy sums a product may be handed); both signs, so that the top limb is negative in half of the edge cases"""
+    canon = [to_mont(v) for v in field_values(rnd, 14 + n // 3)]
+    top5, top2 = 5 * P - 1, (201 * P - 1) // 100
+    edge5 = [top5, -top5, top5 - 1, -top5 + 1, top5 - M29, -(top5 - M29), 4 * P, -4 * P, 4 * P + 1, -4 * P - 1]
+    edge5 += [s * (top5 - rnd.getrandbits(k)) for k in (8, 29, 64, 200, 232, 250) for s in (1, -1)]
+    near2 = [top2, top2 - 1, top2 - rnd.getrandbits(29), top2 - rnd.getrandbits(230), top2 - rnd.getrandbits(250)]
+    assert all(100 * v < 201 * P for v in near2)
+    sums = [s * (a + t * b) for a in near2 for b in near2[:3] for s in (1, -1) for t in (1, -1)]
+    out = canon + edge5 + sums
+    while len(out) < n:
+        out.append(rnd.choice((1, -1)) * (rnd.choice((4, 3, 0)) * P + rnd.randrange(P)))
+    for x in out:
+        _admitted(x)
+    assert any(tight(x)[8] < 0 for x in out)
+    rnd.shuffle(out)
+    return out[:n]
+
+
+def shifted(rnd, v):
+    """another admitted raw integer of the field element v: its Montgomery image moved by a multiple of p towards +-5p"""
+    m, k = to_mont(v), rnd.choice((4, -5, 3, -4, 0, -1))
+    return _admitted(m + (-4 if k == -5 and not m else k) * P)
+
+
+def _w1(x): return tight(x)
+def _w2(x): return tight(x[0]) + tight(x[1])
+def _w12(x): return tuple(w for c in x for w in _w2(c))
+def _r1(w): return tuple(w[:9])
+def _r2(w): return (tuple(w[:9]), tuple(w[9:18]))
+def _v1(w): return raw_value(value(w[:9]))
+def _v2(w): return (raw_value(value(w[:9])), raw_value(value(w[9:18])))
+def _v12(w): return tuple(_v2(w[18 * i:18 * i + 18]) for i in range(6))
+
+
+def _raw2s(rnd, n):
+    a, b = raw_operands(rnd, n), raw_operands(rnd, n)
+    return list(zip(a, b))
+
+
+def f12_shapes(rnd):
+    """field elements: 0, 1, w^k alone, every coefficient p - 1, a single non-zero coefficient in each of the 12 slots, elements of the
+    cyclotomic subgroup (outputs of the easy part of the final exponentiation), a value and its conjugate, random ones"""
+    rand2 = lambda: (rnd.randrange(P), rnd.randrange(P))
+    rand12 = lambda: tuple(rand2() for _ in range(6))
+    out = [F12_ZERO, F12_ONE] + [f12_embed((1, 0), k) for k in range(1, 6)] + [((P - 1, P - 1),) * 6]
+    for k in range(6):
+        out += [f12_embed((rnd.randrange(1, P), 0), k), f12_embed((0, rnd.randrange(1, P)), k)]
+    for _ in range(2):
+        f = rand12()
+        e = f12_mul(f12_conj(f), f12_inv(f))                  # f^(p^6 - 1)
+        g = f12_mul(f12_pow(e, P * P), e)                      # ^(p^2 + 1)
+        assert f12_mul(g, f12_conj(g)) == F12_ONE and g != F12_ONE
+        out.append(g)
+    v = rand12()
+    out += [v, f12_conj(v)]
+    return out + [rand12() for _ in range(4)]
+
+
+def f12_operands(rnd, n):
+    """n Fp12 operands as 12 raw integers each: the shapes in canonical form and moved towards +-5p, then raw edge operands in every slot"""
+    shapes = f12_shapes(rnd)
+    out = [tuple((to_mont(c[0]), to_mont(c[1])) for c in s) for s in shapes]
+    out += [tuple((shifted(rnd, c[0]), shifted(rnd, c[1])) for c in s) for s in shapes]
+    k = max(n // 3, n - len(out))      # at least a third of any table, small ones included, are raw edge operands
+    rnd.shuffle(out)
+    out = out[:n - k]
+    for _ in range(k):
+        r = raw_operands(rnd, 48)
+        out.append(tuple((r[2 * i], r[2 * i + 1]) for i in range(6)))
+    rnd.shuffle(out)
+    assert len(out) == n
+    return out
+
+
+# ---- the twist y^2 = x^3 + 3 / xi in Jacobian coordinates ----
+def _jac_dbl(X, Y, Z):
+    """(X', Y', Z' = 2YZ) of 2T and the line a yP + b xP w + c w^3 of verify_dev.hpp: a = 2YZ^3, b = -3X^2Z^2, c = 3X^3 - 2Y^2"""
+    k = lambda n: (n % P, 0)
+    XX, YY, ZZ = f_mul(X, X), f_mul(Y, Y), f_mul(Z, Z)
+    line = (f_mul(k(2), f_mul(Y, f_mul(Z, ZZ))), f_neg(f_mul(k(3), f_mul(XX, ZZ))), f_sub(f_mul(k(3), f_mul(XX, X)), f_mul(k(2), YY)))
+    m, s = f_mul(k(3), XX), f_mul(k(4), f_mul(X, YY))
+    X3 = f_sub(f_mul(m, m), f_mul(k(2), s))
+    Y3 = f_sub(f_mul(m, f_sub(s, X3)), f_mul(k(8), f_mul(YY, YY)))
+    return (X3, Y3, f_mul(k(2), f_mul(Y, Z))), line
+
+
+def _jac_add(X, Y, Z, xq, yq):
+    """(X', Y', Z' = ZH) of T + Q and the line a = ZH, b = -R, c = R xQ - yQ ZH (H = xQ Z^2 - X, R = yQ Z^3 - Y)"""
+    ZZ = f_mul(Z, Z)
+    H, Rr = f_sub(f_mul(xq, ZZ), X), f_sub(f_mul(yq, f_mul(Z, ZZ)), Y)
+    ZH = f_mul(Z, H)
+    line = (ZH, f_neg(Rr), f_sub(f_mul(Rr, xq), f_mul(yq, ZH)))
+    HH = f_mul(H, H); HHH = f_mul(H, HH); V = f_mul(X, HH)
+    X3 = f_sub(f_sub(f_mul(Rr, Rr), HHH), f_add(V, V))
+    Y3 = f_sub(f_mul(Rr, f_sub(V, X3)), f_mul(Y, HHH))
+    return (X3, Y3, ZH), line
+
+
+def jac_affine(X, Y, Z):
+    if Z == (0, 0):
+        return None
+    zi = f_inv(Z); zi2 = f_mul(zi, zi)
+    return (f_mul(X, zi2), f_mul(Y, f_mul(zi2, zi)))
+
+
+_gamma_cache = {}
+
+
+def twist_frobenius(q):
+    """pi(Q) and -pi^2(Q) on the twist: the p-power Frobenius of the untwisted point, twisted back.  (x' w^2)^p = conj(x') xi^((p-1)/3) w^2 and
+    (y' w^3)^p = conj(y') xi^((p-1)/2) w^3; the two powers of xi come from plain exponentiation, and the first call checks them against
+    x^p computed in Fp12"""
+    if not _gamma_cache:
+        _gamma_cache[2], _gamma_cache[3] = f2_pow(XI, (P - 1) // 3), f2_pow(XI, (P - 1) // 2)
+        x, y = G2_GEN
+        assert f12_pow(f12_embed(x, 2), P) == f12_embed(f_mul((x[0], -x[1] % P), _gamma_cache[2]), 2)
+        assert f12_pow(f12_embed(y, 3), P) == f12_embed(f_mul((y[0], -y[1] % P), _gamma_cache[3]), 3)
+    cj = lambda a: (a[0], -a[1] % P)
+    pi = lambda pt: (f_mul(cj(pt[0]), _gamma_cache[2]), f_mul(cj(pt[1]), _gamma_cache[3]))
+    q1 = pi(q); q2 = pi(q1)
+    return q1, (q2[0], f_neg(q2[1]))
+
+
+def lines_reference(q):
+    """the 102 lines of the Miller loop for Q, chained in Jacobian coordinates from T = (xQ, yQ, 1)"""
+    T, out = (q[0], q[1], (1, 0)), []
+    for bit in bin(ATE_LOOP)[3:]:
+        T, l = _jac_dbl(*T); out.append(l)
+        if bit == "1":
+            T, l = _jac_add(*T, q[0], q[1]); out.append(l)
+    q1, q2 = twist_frobenius(q)
+    T, l = _jac_add(*T, q1[0], q1[1]); out.append(l)
+    T, l = _jac_add(*T, q2[0], q2[1]); out.append(l)
+    assert len(out) == LINE_STEPS
+    return out
+
+
+# ---- case tables: TowerCase.rows are the elements (flat tuples of int32 words); check(row, out, flag) -> None or what is wrong ----
+class TowerCase:
+    def __init__(self, op, rows, check):
+        self.op, self.rows, self.check = op, rows, check
+        assert len(rows) % 64 and all(len(r) == tower_words(0, op)[0] for r in rows)
+
+    def mismatches(self, path, outs, flags, n=None):
+        rows = self.rows if n is None else self.rows[:n]
+        wout = tower_words(path, self.op)[1]
+        assert len(outs) == len(flags) == len(rows) and all(len(o) == wout for o in outs)
+        bad = []
+        for i, (r, o, fl) in enumerate(zip(rows, outs, flags)):
+            if path == 1 and wout:
+                if any(o[108:]):
+                    bad.append((i, "pad lanes are not zero"))
+                o = o[:108]
+            why = self.check(r, o, fl)
+            if why:
+                bad.append((i, why))
+        return bad[:4]
+
+
+def _fp2_out(out, want, bound=is_reduced):
+    if not (bound(out[:9]) and bound(out[9:18])):
+        return "bound: %r" % (out,)
+    if _v2(out) != want:
+        return "value: got %r, want %r" % (_v2(out), want)
+
+
+def _fp12_out(out, want, bound=is_reduced):
+    for i in range(6):
+        why = _fp2_out(out[18 * i:18 * i + 18], want[i], bound)
+        if why:
+            return "w^%d %s" % (i, why)
+
+
+def _is_square1(v): return v == 0 or pow(v, (P - 1) // 2, P) == 1
+def _is_square2(v): return _is_square1((v[0] * v[0] + v[1] * v[1]) % P)      # the norm test
+
+
+def _lex_large(v):
+    c = v[1] if v[1] else v[0]
+    return c > (P - 1) // 2
+
+
+_tower_cache = {}
+
+
+def tower_case(op):
+    if op not in _tower_cache:
+        _tower_cache[op] = _tower_case(op)
+    return _tower_cache[op]
+
+
+def _tower_case(op):
+    rnd = random.Random(600 + op)
+    flagless = lambda fl: "flag set" if fl else None
+    if op == T_RED:
+        rows = [_w1(x) for x in raw_operands(rnd, 261)]
+        def check(r, o, fl):
+            return flagless(fl) or (None if is_reduced(o) and _v1(o) == _v1(r) else "got %r" % (o,))
+        return TowerCase(op, rows, check)
+    if op == T_LIN:
+        ks = [(9, -1), (1, 9), (2, 0), (3, 0), (8, 0), (1, 1), (1, -1), (-1, 0), (0, 1), (9, 9), (-9, -9), (0, 0)]
+        rows = [_w1(a) + _w1(b) + ks[i % len(ks)] for i, (a, b) in enumerate(_raw2s(rnd, 261))]
+        def check(r, o, fl):
+            want = (r[18] * _v1(r) + r[19] * _v1(r[9:])) % P
+            return flagless(fl) or (None if is_reduced(o) and _v1(o) == want else "got %r" % (o,))
+        return TowerCase(op, rows, check)
+    if op in (T_ADD2, T_SUB2, T_MUL2):
+        rows = [_w2(a) + _w2(b) for a, b in zip(_raw2s(rnd, 261), _raw2s(rnd, 261))]
+        f = {T_ADD2: f_add, T_SUB2: f_sub, T_MUL2: f_mul}[op]
+        return TowerCase(op, rows, lambda r, o, fl: flagless(fl) or _fp2_out(o, f(_v2(r), _v2(r[18:]))))
+    if op in (T_NEG2, T_CONJ2, T_SQR2, T_MULXI):
+        rows = [_w2(a) for a in _raw2s(rnd, 261)]
+        f = {T_NEG2: f_neg, T_CONJ2: lambda a: (a[0], -a[1] % P), T_SQR2: lambda a: f_mul(a, a), T_MULXI: lambda a: f_mul(a, XI)}[op]
+        return TowerCase(op, rows, lambda r, o, fl: flagless(fl) or _fp2_out(o, f(_v2(r))))
+    if op == T_SCALE2:
+        rows = [_w2(a) + _w1(k) for a, k in zip(_raw2s(rnd, 261), raw_operands(rnd, 261))]
+        def check(r, o, fl):
+            k = _v1(r[18:])
+            return flagless(fl) or _fp2_out(o, tuple(c * k % P for c in _v2(r)), is_product)
+        return TowerCase(op, rows, check)
+    if op == T_SMALL2:
+        rows = [_w2(a) + ((2, 3, 8)[i % 3],) for i, a in enumerate(_raw2s(rnd, 261))]
+        return TowerCase(op, rows, lambda r, o, fl: flagless(fl) or _fp2_out(o, tuple(c * r[18] % P for c in _v2(r))))
+    if op == T_INV1:
+        rows = [_w1(x) for x in raw_operands(rnd, 133)]
+        def check(r, o, fl):
+            v = _v1(r)
+            return flagless(fl) or (None if is_reduced(o) and _v1(o) == (pow(v, -1, P) if v else 0) else "got %r" % (o,))
+        return TowerCase(op, rows, check)
+    if op == T_INV2:
+        rows = [_w2(a) for a in _raw2s(rnd, 133)]
+        return TowerCase(op, rows, lambda r, o, fl: flagless(fl) or _fp2_out(o, f_inv(_v2(r)) if any(_v2(r)) else (0, 0)))
+    if op == T_SQRT1:
+        vals = [0, 1] + [v * v % P for v in field_values(rnd, 40)] + [-v * v % P for v in field_values(rnd, 40)] + field_values(rnd, 30)
+        assert sum(_is_square1(v) for v in vals) > 40 and sum(not _is_square1(v) for v in vals) > 40
+        rows = [_w1(to_mont(v)) for v in vals] + [_w1(shifted(rnd, v)) for v in vals] + [_w1(x) for x in raw_operands(rnd, 33)]
+        def check(r, o, fl):
+            v = _v1(r)
+            if fl != _is_square1(v):
+                return "flag %d for %d" % (fl, v)
+            if not fl:
+                return None if not any(o) else "a root without the flag"
+            return None if is_reduced(o) and _v1(o) ** 2 % P == v else "root %r" % (o,)
+        return TowerCase(op, rows, check)
+    if op == T_SQRT2:
+        res = [v * v % P for v in field_values(rnd, 20) if v]
+        nonres = [-v % P for v in res]      # p = 3 mod 4: -1 is no square
+        rand2 = [(rnd.randrange(P), rnd.randrange(1, P)) for _ in range(20)]
+        vals = [(0, 0), (1, 0)] + [(v, 0) for v in res] + [(v, 0) for v in nonres] + [f_mul(a, a) for a in rand2] + [f_mul(f_mul(a, a), XI) for a in rand2]
+        vals += [(0, v) for v in res[:6]] + rand2
+        assert all(_is_square1(v) for v in res) and not any(_is_square1(v) for v in nonres) and not _is_square2(XI)
+        assert sum(_is_square2(v) for v in vals) > 40 and sum(not _is_square2(v) for v in vals) > 25
+        rows = [_w2((to_mont(v[0]), to_mont(v[1]))) for v in vals] + [_w2((shifted(rnd, v[0]), shifted(rnd, v[1]))) for v in vals] + [_w2(a) for a in _raw2s(rnd, 21)]
+        def check(r, o, fl):
+            v = _v2(r)
+            if fl != _is_square2(v):
+                return "flag %d for %r" % (fl, v)
+            if not fl:
+                return None if not any(o) else "a root without the flag"
+            return None if is_reduced(o[:9]) and is_reduced(o[9:]) and f_mul(_v2(o), _v2(o)) == v else "root %r" % (o,)
+        return TowerCase(op, rows, check)
+    if op == T_LEX_LARGE2:
+        # lex_large compares the CANONICAL integer (out of the Montgomery domain) with (p - 1) / 2
+        h = (P - 1) // 2
+        vals = [(a, b) for a in (0, 1, h, h + 1, P - 1) for b in (0, 1, h, h + 1, P - 1)] + [(rnd.randrange(P), rnd.randrange(P)) for _ in range(40)] + [(rnd.randrange(P), 0) for _ in range(20)]
+        rows = [_w2((to_mont(v[0]), to_mont(v[1]))) for v in vals] + [_w2((shifted(rnd, v[0]), shifted(rnd, v[1]))) for v in vals] + [_w2(a) for a in _raw2s(rnd, 31)]
+        return TowerCase(op, rows, lambda r, o, fl: None if fl == _lex_large(_v2(r)) else "flag %d for %r" % (fl, _v2(r)))
+    if op in (T_MUL12, T_SQR12, T_MUL_LINE, T_CONJ12, T_FROB12, T_FROB12_2, T_INV12, T_POW_X, T_FINAL_EXP):
+        n = {T_MUL12: 101, T_SQR12: 101, T_MUL_LINE: 101, T_CONJ12: 101, T_FROB12: 67, T_FROB12_2: 67, T_INV12: 67, T_POW_X: 13, T_FINAL_EXP: 13}[op]
+        a = f12_operands(rnd, n)
+        if op == T_MUL12:
+            b = f12_operands(rnd, n)
+            rows = [_w12(x) + _w12(y) for x, y in zip(a, b)]
+            return TowerCase(op, rows, lambda r, o, fl: flagless(fl) or _fp12_out(o, f12_mul(_v12(r), _v12(r[108:]))))
+        if op == T_MUL_LINE:
+            cs = [_raw2s(rnd, n) for _ in range(3)]
+            rows = [_w12(x) + _w2(cs[0][i]) + _w2(cs[1][i]) + _w2(cs[2][i]) for i, x in enumerate(a)]
+            def check(r, o, fl):
+                c0, c1, c3 = _v2(r[108:]), _v2(r[126:]), _v2(r[144:])
+                return flagless(fl) or _fp12_out(o, f12_mul(_v12(r), (c0, c1, (0, 0), c3, (0, 0), (0, 0))))
+            return TowerCase(op, rows, check)
+        rows = [_w12(x) for x in a]
+        if op == T_CONJ12:
+            def check(r, o, fl):      # the even coefficients pass through as they are
+                if any(o[36 * i:36 * i + 18] != r[36 * i:36 * i + 18] for i in range(3)):
+                    return "an even coefficient changed"
+                return flagless(fl) or _fp12_out(o, f12_conj(_v12(r)), lambda l: in_class(l, "T1"))
+            return TowerCase(op, rows, check)
+        if op == T_FROB12_2:      # coefficient 0 passes through; the others are products that scale2 returns unreduced
+            return TowerCase(op, rows, lambda r, o, fl: flagless(fl) or ("coefficient 0 changed" if o[:18] != r[:18] else
+                                                                         "bound" if not all(is_product(o[9 * i:9 * i + 9]) for i in range(2, 12)) else
+                                                                         None if _v12(o) == f12_pow(_v12(r), P * P) else "value"))
+        f = {T_SQR12: lambda x: f12_mul(x, x), T_FROB12: lambda x: f12_pow(x, P), T_INV12: f12_inv, T_POW_X: lambda x: f12_pow(x, BN_X),
+             T_FINAL_EXP: lambda x: f12_pow(x, FINAL_EXPONENT)}[op]
+        def check(r, o, fl):
+            if op == T_INV12 and _v12(r) != F12_ZERO and f12_mul(_v12(o), _v12(r)) != F12_ONE:
+                return "a * inv(a) != 1"
+            return flagless(fl) or _fp12_out(o, f(_v12(r)))
+        return TowerCase(op, rows, check)
+    if op == T_IS_ONE12:
+        one, zero = to_mont(1), 0
+        base = [(one, zero)] + [(zero, zero)] * 5
+        elems = []      # (12 raw integers as six pairs, is it one)
+        for wave in range(8):      # path 1: wave j of eight groups holds its one element that is not 1 at group position j
+            for pos in range(8):
+                e = [tuple(shifted(rnd, raw_value(x)) if wave % 2 else x for x in c) for c in base]
+                if pos == wave:
+                    s = rnd.randrange(12)
+                    c = list(e[s // 2]); c[s % 2] += 1; e[s // 2] = tuple(c)
+                elems.append((tuple(e), pos != wave))
+        for s in range(12):        # a stray 1 in each of the 12 Fp slots: the raw integer 1, and the field element 1
+            for stray in (1, one):
+                e = [list(c) for c in base]
+                e[s // 2][s % 2] += stray
+                elems.append((tuple(tuple(c) for c in e), False))
+        elems += [(tuple((shifted(rnd, 1), shifted(rnd, 0)) if i == 0 else (shifted(rnd, 0), shifted(rnd, 0)) for i in range(6)), True) for _ in range(7)]
+        assert len(elems) == 64 + 24 + 7 and sum(1 for _, w in elems if not w) == 8 + 24
+        want = {_w12(e): w for e, w in elems}
+        for e, w in elems:
+            assert (tuple(raw2(c) for c in e) == F12_ONE) == w
+        return TowerCase(op, [_w12(e) for e, _ in elems], lambda r, o, fl: None if bool(fl) == want[tuple(r)] else "flag %d" % fl)
+    # ---- Miller steps ----
+    pool = point_pool(1)
+    lam = [l for l in scales(1) if l != (0, 0)]
+    def jac(i):      # point i of the pool under a scale: (x l^2, y l^3, l)
+        (x, y), l = pool[i % len(pool)], lam[(5 * i + 1) % len(lam)] if i % 4 else (1, 0)
+        l2 = f_mul(l, l)
+        return (f_mul(x, l2), f_mul(y, f_mul(l2, l)), l)
+    rep = lambda i, v: (to_mont(v[0]), to_mont(v[1])) if i % 3 == 0 else (shifted(rnd, v[0]), shifted(rnd, v[1]))
+    def step_check(r, o, want_t, want_line):
+        if not all(is_reduced(o[9 * i:9 * i + 9]) for i in range(12)):
+            return "bound"
+        got_t = jac_affine(_v2(o), _v2(o[18:]), _v2(o[36:]))
+        if got_t != want_t:
+            return "T': got %r, want %r" % (got_t, want_t)
+        got_line = (_v2(o[54:]), _v2(o[72:]), _v2(o[90:]))
+        return None if got_line == want_line else "line: got %r, want %r" % (got_line, want_line)
+    if op == T_DBL_STEP:
+        rows = [_w2(rep(i, T[0])) + _w2(rep(i + 1, T[1])) + _w2(rep(i + 2, T[2])) for i, T in ((i, jac(i)) for i in range(101))]
+        def check(r, o, fl):
+            T = (_v2(r), _v2(r[18:]), _v2(r[36:]))
+            a = jac_affine(*T)
+            return flagless(fl) or step_check(r, o, ec_add(a, a), _jac_dbl(*T)[1])
+        return TowerCase(op, rows, check)
+    if op == T_ADD_STEP:
+        rows = []
+        for i in range(101):
+            T, q = jac(i), pool[(3 * i + 7) % len(pool)]
+            if pool[i % len(pool)][0] == q[0]:
+                q = pool[(3 * i + 8) % len(pool)]
+            assert pool[i % len(pool)][0] != q[0]      # the Miller loop never adds T = +-Q
+            rows.append(_w2(rep(i, T[0])) + _w2(rep(i + 1, T[1])) + _w2(rep(i + 2, T[2])) + _w2(rep(i + 1, q[0])) + _w2(rep(i, q[1])))
+        def check(r, o, fl):
+            T, q = (_v2(r), _v2(r[18:]), _v2(r[36:])), (_v2(r[54:]), _v2(r[72:]))
+            return flagless(fl) or step_check(r, o, ec_add(jac_affine(*T), q), _jac_add(*T, *q)[1])
+        return TowerCase(op, rows, check)
+    qs = [ec_mul(k, G2_GEN) for k in (1, 2, R - 1, rnd.getrandbits(40), rnd.getrandbits(250))]
+    if op == T_FROB_POINTS:
+        qs = qs + pool[:28]
+        rows = [_w2(rep(i, q[0])) + _w2(rep(i + 1, q[1])) for i, q in enumerate(qs)]
+        def check(r, o, fl):
+            q1, q2 = twist_frobenius((_v2(r), _v2(r[18:])))
+            return flagless(fl) or _fp2_out(o, q1[0]) or _fp2_out(o[18:], q1[1]) or _fp2_out(o[36:], q2[0]) or _fp2_out(o[54:], q2[1])
+        return TowerCase(op, rows, check)
+    assert op == T_LINES_OF
+    qs = qs + qs[:4] + pool[12:16]
+    rows = [_w2(rep(i // 5, q[0])) + _w2(rep(i // 5 + 1, q[1])) for i, q in enumerate(qs)]
+    def check(r, o, fl):
+        want = lines_reference((_v2(r), _v2(r[18:])))
+        for s in range(LINE_STEPS):
+            w = o[54 * s:54 * s + 54]
+            if not all(is_reduced(w[9 * i:9 * i + 9]) for i in range(6)):
+                return "step %d: bound" % s
+            if (_v2(w), _v2(w[18:]), _v2(w[36:])) != want[s]:
+                return "step %d: line" % s
+        return flagless(fl)
+    return TowerCase(op, rows, check)
+
+
+def _self_check_jacobian():
+    """the chained Jacobian model above against affine arithmetic, once"""
+    T = (G2_GEN[0], G2_GEN[1], (1, 0))
+    T2, _ = _jac_dbl(*T)
+    assert jac_affine(*T2) == ec_add(G2_GEN, G2_GEN)
+    T3, _ = _jac_add(*T2, *G2_GEN)
+    assert jac_affine(*T3) == ec_mul(3, G2_GEN)
+
+
+_self_check_jacobian()
+
+
 # ---------------------------------------------------------------- host builds ----------------------------------------------------------------
 def native_exe(name):
     """tests/native/<name>.cpp, built by g++ with the HIP headers: the device headers with their plain-C products"""
@@ -426,6 +1008,17 @@ def native_limb_ops(exe, field, op, operands):
     out = subprocess.run([exe], input=payload, capture_output=True, timeout=300, check=True).stdout
     flat = struct.unpack("<%di" % (9 * n), out)
     return [flat[9 * i:9 * i + 9] for i in range(n)]
+
+
+def native_tower_ops(exe, path, op, rows, wout=None):
+    """tests/native/tower_check.cpp: paths 0 and 1 as the hook, 2 and 3 the whole pairing (serial / lane-sliced) -> (outs, flags)"""
+    n = len(rows)
+    wout = tower_words(path, op)[1] if wout is None else wout
+    payload = struct.pack("<3i", path, op, n) + struct.pack("<%di" % (len(rows[0]) * n), *[w for r in rows for w in r])
+    out = subprocess.run([exe], input=payload, capture_output=True, timeout=300, check=True).stdout
+    assert len(out) == 4 * wout * n + n
+    flat = struct.unpack("<%di" % (wout * n), out[:4 * wout * n])
+    return [flat[wout * i:wout * (i + 1)] for i in range(n)], list(out[4 * wout * n:])
 
 
 def native_curve_ops(exe, group, op, pts, inf, lam, n, k):
