@@ -20,7 +20,7 @@ CHACHA20, AES_128, AES_256 = 0, 1, 2                       # prove_impl.go:15-19
 ALGORITHM_NAMES = {0: "chacha20", 1: "aes-128-ctr", 2: "aes-256-ctr"}   # prove_impl.go:21-25
 
 EXPORTS = ["enforce_binding", "InitAlgorithm", "Free", "Prove", "ProveBatch", "gsc_prove_raw", "gsc_setup",
-           "gsc_set_deterministic_randomness", "gsc_debug_prove", "gsc_debug_vector", "gsc_describe", "gsc_last_stage_ms", "gsc_last_dominant_kernel", "gsc_last_kernel_clock", "gsc_debug_field_ops", "gsc_debug_limb_ops", "gsc_debug_curve_ops", "gsc_debug_tower_ops", "gsc_debug_compute_h", "gsc_debug_compute_d", "gsc_debug_secret_residue", "gsc_debug_clock_trace", "gsc_debug_glv_split",
+           "gsc_set_deterministic_randomness", "gsc_debug_prove", "gsc_debug_vector", "gsc_describe", "gsc_last_stage_ms", "gsc_last_dominant_kernel", "gsc_last_kernel_clock", "gsc_debug_field_ops", "gsc_debug_limb_ops", "gsc_debug_curve_ops", "gsc_debug_tower_ops", "gsc_debug_compute_h", "gsc_debug_compute_d", "gsc_debug_z_sum", "gsc_debug_secret_residue", "gsc_debug_clock_trace", "gsc_debug_glv_split",
            "gsc_verify_init", "gsc_verify_raw", "VerifyBatch", "gsc_debug_pairing",
            "gsc_verify_raw_batched", "gsc_verify_all", "VerifyAll", "gsc_debug_verify_randomizers",
            "gsc_verify_json", "gsc_verify_last_path", "gsc_debug_verify_path", "gsc_debug_pairing_few",
@@ -382,6 +382,19 @@ def debug_compute_d(algorithm_id: int, ab_be: bytes, m: int) -> bytes:
     if L.gsc_debug_compute_d(algorithm_id, ab_be, m, out, len(out)) != n:
         raise RuntimeError("gsc_debug_compute_d failed")
     return out.raw
+
+
+def debug_z_sum(algorithm_id: int, abc_be: bytes, m: int):
+    """TEST HOOK: the evaluation-form quotient sum of 64 columns of caller-supplied a|b|c ([m][64] big-endian each, c = a b) through the
+    batch kernels and the engine's own Z sets -> (64 x 64 B big-endian X | Y, 64 infinity flags)."""
+    L = lib()
+    L.gsc_debug_z_sum.restype = C.c_int
+    L.gsc_debug_z_sum.argtypes = [C.c_ubyte, C.c_char_p, C.c_size_t, C.c_void_p, C.c_void_p]
+    assert len(abc_be) == 3 * m * 64 * 32
+    out, flags = C.create_string_buffer(64 * 64), C.create_string_buffer(64)
+    if L.gsc_debug_z_sum(algorithm_id, abc_be, m, out, flags) != 0:
+        raise RuntimeError("gsc_debug_z_sum failed")
+    return out.raw, flags.raw
 
 
 # ---- GPU verifier in libprove.so (k_verify.hip): verdicts identical to libverify's Verify ----

@@ -523,6 +523,12 @@ long long gsc_debug_compute_d(GoUint8 algorithmID, const uint8_t* ab_be, size_t 
     try { a->debug_compute_d(ab_be, m, d_out); return (long long)a->domain_size(); }
     catch (const std::exception& e) { printf("%s\n", e.what()); return -1; }
 }
+int gsc_debug_z_sum(GoUint8 algorithmID, const uint8_t* abc_be, size_t m, uint8_t* out, uint8_t* flags) {
+    if (hooks_refused("gsc_debug_z_sum") || algorithmID > 2 || !abc_be || !out || !flags) return -1;
+    Algorithm* a = lookup(algorithmID); if (!a) return -1;
+    try { a->debug_z_sum(abc_be, m, out, flags); return 0; }
+    catch (const std::exception& e) { printf("%s\n", e.what()); return -1; }
+}
 
 size_t gsc_describe(GoUint8 algorithmID, char* out, size_t cap) {
     if (algorithmID > 2 || !cap) return 0;

@@ -49,6 +49,7 @@ EngineConfig config_from_env() {
     c.few_wide = env_int("GSC_FEW_WIDE", 1);
     c.quotient_eval = env_int("GSC_QUOTIENT_EVAL", 1);
     c.fuse_z_digits = env_int("GSC_FUSE_Z_DIGITS", 1);
+    c.quotient_fold = env_int("GSC_QUOTIENT_FOLD", 1);
     c.small_witness = env_int("GSC_SMALL_WITNESS", 1);
     c.small_witness_few = env_int("GSC_SMALL_WITNESS_FEW", 1);
     c.ntt_plain = env_int("GSC_NTT_PLAIN", 1) ? 1 : 0;
@@ -189,12 +190,13 @@ std::string Algorithm::describe() const {
     char buf[640];
     snprintf(buf, sizeof buf, "wires=%zu constraints=%zu domain=2^%d max_batch=%zu lanes=%zu small=%zux%zu devices=%zu window_z=%d window_w=%d tables=%.2f GiB bases A=%zu B=%zu K=%zu Z=%zu grouped A=%zu B=%zu K=%zu wide(windowed+expanded) A=%zu+%zu B=%zu+%zu K=%zu+%zu",
              impl_->n_wires, impl_->n_constraints, impl_->L, max_batch(), impl_->full_lanes, impl_->lanes.size() - impl_->full_lanes, impl_->lanes.size() > impl_->full_lanes ? impl_->lanes.back()->cap : (size_t)0, impls_.size(), impl_->cfg.window_z, impl_->cfg.window_w, impl_->table_bytes / 1073741824.0,
-             impl_->mA.nbases, impl_->mB1.nbases, impl_->mK.nbases, impl_->mZ.nbases, impl_->mA.nbit, impl_->mB1.nbit, impl_->mK.nbit,
+             impl_->mA.nbases, impl_->mB1.nbases, impl_->mK.nbases, impl_->mZ.digit_bases ? impl_->mZ.digit_bases : impl_->mZ.nbases, impl_->mA.nbit, impl_->mB1.nbit, impl_->mK.nbit,
              impl_->mA.nwide, impl_->mA.nexpanded, impl_->mB1.nwide, impl_->mB1.nexpanded, impl_->mK.nwide, impl_->mK.nexpanded);
     // per replica: calls and statements it has served (ReplicaPicker): shows that small calls reach every device
     std::string out = buf;
     if (impl_->quotient_eval) out += std::string(" quotient=evaluation-form") + (impl_->fuse_z_digits ? "+digits" : "") + (!impl_->fuse_z_digits || !impl_->cfg.overlap_quotient ? "" : impl_->cfg.overlap_quotient == 2 ? "+beside-wire-sets" : "+beside-wire-sets(<4096)") + "(c: " + std::to_string(impl_->mC.nbit) + " grouped + " + std::to_string(impl_->mC.nflat - impl_->mC.nbit) + " flat + " + std::to_string(impl_->mC.nwide) + " windowed)";
     else out += " quotient=coefficient-form";
+    if (impl_->quotient_eval) out += impl_->mZ.digit_bases ? " Zlive=" + std::to_string(impl_->mZ.nwide) : " Zfold=off(" + impl_->fold_why + ")";
     out += impl_->small.ok ? " witness=small-integer(" + std::to_string(impl_->small.n_levels) + " chained levels, fallbacks " + std::to_string(impl_->small_fallbacks.load()) + ")" : " witness=generic" + (impl_->small.why.empty() ? std::string() : "(" + impl_->small.why + ")");
     out += " served(calls/statements)=";
     const auto sv = picker_->served();
@@ -203,7 +205,7 @@ std::string Algorithm::describe() const {
 }
 size_t Algorithm::domain_size() const { return impls_[0]->domain_n; }
 // The set-up the two quotient test hooks share: `mats` matrices [m][64] of canonical big-endian values into A, B (, C) of the first lane,
-// `quot(plan, lane, columns)` on them, A back to the host.
+// `quot(plan, lane, columns)` on them, A back to the host (out != nullptr).
 template <class Quot>
 static void debug_quotient(AlgorithmImpl& a, const char* who, const uint8_t* mats_be, size_t mats, size_t m, uint8_t* out, Quot quot) {
     if (m > a.n_constraints) throw std::runtime_error(std::string(who) + ": more rows than constraints");
@@ -217,7 +219,7 @@ static void debug_quotient(AlgorithmImpl& a, const char* who, const uint8_t* mat
     for (size_t k = 0; k < mats; k++) launch_fr_from_be(d_be.p + k * cnt * 32, dst[k], cnt, ln.stream);
     NttPlan plan{a.L, a.tw_fwd.p, a.tw_inv.p, a.scale_mid.p, a.scale_out.p, a.dom.p + 5, a.qr.p};
     HIP_CHECK(quot(plan, ln, B));
-    HIP_CHECK(hipMemcpyAsync(out, ln.d_A.p, a.domain_n * B * 32, hipMemcpyDeviceToHost, ln.stream));
+    if (out) HIP_CHECK(hipMemcpyAsync(out, ln.d_A.p, a.domain_n * B * 32, hipMemcpyDeviceToHost, ln.stream));
     HIP_CHECK(hipStreamSynchronize(ln.stream));
 }
 void Algorithm::debug_compute_h(const uint8_t* abc_be, size_t m, uint8_t* h_out) {
@@ -225,6 +227,28 @@ void Algorithm::debug_compute_h(const uint8_t* abc_be, size_t m, uint8_t* h_out)
 }
 void Algorithm::debug_compute_d(const uint8_t* ab_be, size_t m, uint8_t* d_out) {
     debug_quotient(*impls_[0], "debug_compute_d", ab_be, 2, m, d_out, [m](const NttPlan& plan, AlgorithmImpl::Lane& ln, size_t B) { return launch_compute_d(plan, ln.d_A.p, ln.d_B.p, m, B, ln.stream); });
+}
+void Algorithm::debug_z_sum(const uint8_t* abc_be, size_t m, uint8_t* out, uint8_t* flags) {
+    AlgorithmImpl& a = *impls_[0];
+    if (!a.quotient_eval) throw std::runtime_error("debug_z_sum: the engine holds the coefficient form");
+    HIP_CHECK(hipSetDevice(a.cfg.device));
+    DevBuf<uint8_t> d_out(64 * 64), d_flags(64);
+    debug_quotient(a, "debug_z_sum", abc_be, 3, m, nullptr, [&](const NttPlan& plan, AlgorithmImpl::Lane& ln, size_t B) {
+        AlgorithmImpl::Chunk ck{nullptr, B, B, nullptr, chunk_route(B, a.cfg, a.route_facts(), RouteCall{}), {}, {}, {}};
+        ln.small_active = false;
+        // rows m .. n - 1 of a, b, c (and the padding row of c) are zero in this call
+        for (fe* mat : {ln.d_A.p, ln.d_B.p, ln.d_C.p}) HIP_CHECK(hipMemsetAsync(mat + m * B, 0, (a.domain_n - m) * B * sizeof(fe), ln.stream));
+        HIP_CHECK(hipMemsetAsync(ln.d_C.p + a.domain_n * B, 0, B * sizeof(fe), ln.stream));
+        if (ck.rt.z_digits_ready) HIP_CHECK(launch_compute_d_digits(plan, ln.d_A.p, ln.d_B.p, a.n_constraints, B, QuotDigits{ln.d_digits.p, a.mZ.c, a.mZ.nwin}, ln.stream));
+        else HIP_CHECK(launch_compute_d(plan, ln.d_A.p, ln.d_B.p, a.n_constraints, B, ln.stream));
+        a.run_msm_g1(ln, ck, a.mC, ln.d_C.p, 1, ln.d_sumC.p);
+        a.run_msm_g1(ln, ck, a.mZ, ln.d_A.p, 0, ln.d_sumZ.p, false, false, ck.rt.z_digits_ready);
+        a.flush_horner<G1Aff>(ln.pending1, B, ln.stream);
+        launch_g1_sum_be(ln.d_sumC.p, ln.d_sumZ.p, B, d_out.p, d_flags.p, ln.stream);
+        HIP_CHECK(hipMemcpyAsync(out, d_out.p, 64 * 64, hipMemcpyDeviceToHost, ln.stream));
+        HIP_CHECK(hipMemcpyAsync(flags, d_flags.p, 64, hipMemcpyDeviceToHost, ln.stream));
+        return hipGetLastError();
+    });
 }
 // one replica: cut the request list into chunks (multiples of 64 proofs, at most one lane's capacity) and let worker threads pull
 // chunks, each on whichever lane is free.  A call that fits one lane stays whole: cutting a lone 1024-statement AES-128 call over

@@ -53,6 +53,8 @@ struct EngineConfig {
     int quotient_eval = 1;       // GSC_QUOTIENT_EVAL: batch calls take the quotient in evaluation form (k_quot_bases.hip: four transforms instead of six, the Z sum over the
                                  // bases V_i plus a flat sum over the solver's c); 0 = coefficient form for every call (six transforms, the key's own Z bases)
     int fuse_z_digits = 1;       // GSC_FUSE_Z_DIGITS: in evaluation form the last quotient kernel writes the signed digits of d itself (no scalar vector, no recoding pass); 0 = it writes d
+    int quotient_fold = 1;       // GSC_QUOTIENT_FOLD: in evaluation form, the bases of the coset values that the domain's zero padding makes redundant are folded into the others at
+                                 // InitAlgorithm (k_quot_bases.hip, "the fold": n - m + 1 of the n Z bases are never walked again); 0 = the sets as the key gives them.  Same bytes
     int small_witness = 1;       // GSC_SMALL_WITNESS: circuits whose whole witness is small integers (ChaCha20-V3) are solved by the integer kernels on byte planes
                                  // (wit_small.hpp) in every call beyond the latency path; 0 = always the generic field-arithmetic solver;
                                  // 2 (test hooks only) = every constraint row predicted narrow: the kernels notice, the chunk is solved again generically
@@ -113,6 +115,9 @@ class Algorithm {
     // d_out: [domain][64] little-endian canonical values, row i = A(zeta w^i) B(zeta w^i) * 2^261 mod r (natural order).
     void debug_compute_d(const uint8_t* ab_be, size_t m, uint8_t* d_out);
     size_t domain_size() const;
+    // TEST HOOK: the evaluation-form quotient sum sum_i c_i U_i + sum_i d_i V_i of 64 columns through the batch kernels, whatever sets init_key built.
+    // abc_be: a, b, c = a b row by row, [m][64] canonical big-endian values.  out: 64 x 64 B big-endian canonical X | Y, flags[i] = 1: infinity.
+    void debug_z_sum(const uint8_t* abc_be, size_t m, uint8_t* out, uint8_t* flags);
     // TEST HOOK: bytes of secrets (key wires, r, s, input records, masks) still non-zero in device memory, all replicas and lanes; 0 after any call
     size_t debug_secret_residue();
   private:

@@ -50,6 +50,8 @@ struct MsmSet {                     // one fixed-base MSM of the proving key (ke
     size_t nbases = 0;              // bases of the key in this set
     // windowed part (uniform rows of 2^(c-1) multiples): every base of Z; the wide wires of a wire set when there are many
     DevBuf<AffT> wtable; DevBuf<uint32_t> wrows; size_t nwide = 0; int c = 0, nwin = 0;
+    // the folded Z set (init_key): the last quotient kernel lays the digits out for this many bases, of which the kernel walks the first nwide (0: nwide)
+    size_t digit_bases = 0;
     // flat part: [bit groups of eight][narrow wires, own row lengths][window octets of a few wide wires (cv-bit digits)]
     DevBuf<AffT> ftable; DevBuf<uint64_t> rowoff; DevBuf<uint32_t> rowlen; DevBuf<uint32_t> frows; DevBuf<int32_t> octwin;
     size_t nflat = 0, nbit = 0, nexpanded = 0; int cv = 0; DevBuf<AffT> sub; DevBuf<uint8_t> group_ok;
@@ -121,6 +123,13 @@ class AlgorithmImpl {
     // ... and the last quotient kernel writes the digits of d itself (launch_compute_d_digits): mZ's table positions follow quot_digit_index,
     // whole batches skip the recoding pass; the other sets recode into a (small) digit buffer of their own meanwhile (Lane::d_digits_w)
     bool fuse_z_digits = false;
+    // The fold (k_quot_bases.hip): with m constraints on a domain of n only m - 1 of the d_i are independent of c; the bases of the others went into U and V
+    // (U', V': valid only as a pair — mC and mZ are both folded or neither), mZ walks m - 1 bases.  fold_why: why not, for gsc_describe.
+    std::string fold_why = "GSC_QUOTIENT_FOLD=0";
+    static constexpr double FOLD_MAX_SCALAR_MULS = 1e9;      // init cost gate: (2m - 1)(n - m + 1) scalar multiplications (ChaCha20-V3 4.3e8; AES-V2's dense fold is 20 x that)
+    // U' and V' (table order, m and m - 1 points) from U and V; false (and fold_why) when a folded base is the point at infinity
+    bool fold_quotient_bases(const DevBuf<G1Aff>& d_U, const std::vector<uint8_t>& stU, const DevBuf<G1Aff>& d_V, const std::vector<uint8_t>& stV, const std::vector<uint32_t>& rowsZ,
+                             DevBuf<G1Aff>& d_U2, std::vector<uint8_t>& stU2, DevBuf<G1Aff>& d_V2, std::vector<uint8_t>& stV2);
     // batch buffers: one set per lane.  A lane = a HIP stream with its own witness / polynomial / partial-sum buffers; with more than
     // one full lane big batches are cut into chunks that the lanes prove concurrently.  Measured on MI355X: for FULL
     // batches two lanes do not beat one (the MSM kernels fill the chip; chaining the heavy phases so that only the witness stage

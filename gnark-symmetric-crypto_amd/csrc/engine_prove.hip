@@ -90,7 +90,8 @@ void AlgorithmImpl::run_msm(Lane& ln, const MsmCtx& ctx, const MsmSet<AffT>& set
         MsmRecodeArgs ra{scalars, set.wrows.p, wires ? 1 : 0, set.nwide, B, set.c, set.nwin, ctx.digits};
         if (!digits_ready) launch_msm_recode(ra, ctx.stream);
         MsmWinArgs a{set.wtable.p, set.c, set.nwin, set.nwide, ctx.digits, B, nslices, per, pa, timed && !latency ? ln.d_clk.p : nullptr,
-                     timed && cfg.z_exp_entry_bits > 0 && cfg.z_exp_entry_bits < 31 ? (1u << cfg.z_exp_entry_bits) - 1 : 0u};
+                     timed && cfg.z_exp_entry_bits > 0 && cfg.z_exp_entry_bits < 31 ? (1u << cfg.z_exp_entry_bits) - 1 : 0u,
+                     digits_ready ? set.digit_bases : 0};      // (digits recoded here are laid out for the bases walked)
         if (timed) HIP_CHECK(hipEventRecord(ln.ev[5], ctx.stream));
         if (latency) launch_msm_win_few<AffT>(a, n_real, ctx.stream);
         else launch_msm_win<AffT>(a, ctx.stream);
@@ -401,7 +402,7 @@ void AlgorithmImpl::stage_stat(Lane& ln, const Chunk& ck) {
     (void)hipEventElapsedTime(&ln.msm_z_kernel_ms, ln.ev[5], ln.ev[6]); ln.last_batch = ck.B;
     KernelStat& st = ln.stat;
     st.name = ck.rt.kernel_name;
-    st.ms = ln.msm_z_kernel_ms; st.statements = ck.n; st.columns = ck.B; st.nbases = mZ.nwide; st.nwin = mZ.nwin;
+    st.ms = ln.msm_z_kernel_ms; st.statements = ck.n; st.columns = ck.B; st.nbases = mZ.digit_bases ? mZ.digit_bases : mZ.nwide; st.nwin = mZ.nwin;
     for (int k = 0; k < 4; k++) st.stage_ms[k] = ln.stage_ms[k];
     // shader clock of the Z launch: (shader-clock ticks) / (100 MHz ticks) over the lives of eight waves spread over the grid, one on each XCD
     // (the XCDs are clocked separately; a pair of stamps from two different waves is useless: the shader-clock counters are not chip-wide —

@@ -187,7 +187,7 @@ template <class F, bool EXACT, bool WIDE>
 __device__ __forceinline__ Xyzz9<F> accumulate_window(const MsmWinArgs& a, size_t k0, size_t k1, uint32_t j, size_t p) {
     using C = Curve9<F>;
     constexpr size_t DW = WIDE ? 2 : 1;                     // 16-byte words per (octet, proof)
-    const size_t noct = (a.nbases + 7) / 8, D = (size_t)1 << (a.c - 1);
+    const size_t noct = ((a.digit_bases ? a.digit_bases : a.nbases) + 7) / 8, D = (size_t)1 << (a.c - 1);
     const fe* table = reinterpret_cast<const fe*>(a.table);
     const uint4* dig = a.digits + (((size_t)j * noct + k0 / 8) * a.batch + p) * DW;
     Xyzz9<F> acc = C::infinity();
@@ -249,7 +249,7 @@ __global__ __launch_bounds__(64, F::WORDS == 1 ? 3 : 1) void k_msm_win(MsmWinArg
 template <class F>
 __global__ __launch_bounds__(64) void k_msm_win_few(MsmWinArgs a) {
     using C = Curve9<F>;
-    const size_t slice = blockIdx.x / (uint32_t)a.nwin, p = blockIdx.y, noct = (a.nbases + 7) / 8, D = (size_t)1 << (a.c - 1);
+    const size_t slice = blockIdx.x / (uint32_t)a.nwin, p = blockIdx.y, noct = ((a.digit_bases ? a.digit_bases : a.nbases) + 7) / 8, D = (size_t)1 << (a.c - 1);
     const uint32_t j = blockIdx.x % (uint32_t)a.nwin, lane = threadIdx.x;
     const auto [k0, k1] = slice_bounds(slice, a.per, a.nbases);
     const fe* table = reinterpret_cast<const fe*>(a.table);

@@ -108,7 +108,113 @@ __global__ __launch_bounds__(64) void k_qb_finish(const fe* Y, uint32_t n, const
     status[i] = 0;
 }
 
+// ---- the fold: bases of the coset values that the domain's zero padding makes redundant ---------------------------------------------------
+// Rows m .. n-1 of a and b are zero, so A and B vanish on S = {w^i : m <= i < n}: P = A B = Z_S^2 Q with deg Q <= 2m - 2, and the n values
+// d_i = P(y_i), y_i = zeta w^i, are determined by the m values c_i = P(x_i), x_i = w^i, and any m - 1 of them.  The others (J, n - m + 1
+// indices; I: the rest) are Lagrange combinations over the nodes {x_i : i < m} + {y_i : i in I},
+//   d_j = sum_{i<m} alpha_ji c_i + sum_{i in I} beta_ji d_i,   alpha_ji = lambda_j mu_i / (y_j - x_i),   beta_ji = lambda_j nu_i / (y_j - y_i),
+//   lambda_j = 2n Z_S(y_j) / (y_j Z_J'(y_j)),   mu_i = x_i Z_J(x_i) / (2n Z_S(x_i)),   nu_i = y_i Z_J(y_i) / (2n Z_S(y_i))
+// (Z_S, Z_J: the vanishing polynomials of S and of {y_j : j in J}; x^n = 1 and y^n = -1 used), so their bases move into the rest, once
+// per key:  U'_i = U_i + sum_J alpha_ji V_j,  V'_i = V_i + sum_J beta_ji V_j.  The engine's d is d_i 2^261 with 2^-261 folded into V:
+// beta is homogeneous in d, alpha carries the factor 2^261.  tests/test_quot_fold_host.py checks the algebra on integers.
+//
+// Columns p of the fold: p < m the node x_p (base U_p), p >= m the node y of table position p - m (base V at that position); J = the table
+// positions m - 1 .. n - 1 (perm: position -> coset index).
+
+// pw[k] = w^k, k < n; yj[q] = the coset point of the dropped table position m - 1 + q (Montgomery)
+__global__ __launch_bounds__(64) void k_qf_powers(const fe* omega, const uint32_t* perm, uint32_t n, int L, uint32_t m, fe* pw, fe* yj) {
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    pw[k] = qb_fr_pow(*omega, k);
+    if (k >= m - 1) yj[k - (m - 1)] = Fr::mul(qb_zeta(L), qb_fr_pow(*omega, perm[k]));
+}
+
+// One thread per point: t < m the node x_t, then the n coset points in table order.  node[p], weight[p] (mu 2^261 or nu) for the columns,
+// lam[q] for the dropped position m - 1 + q.  All Montgomery.
+__global__ __launch_bounds__(64) void k_qf_weights(const fe* pw, const uint32_t* perm, uint32_t n, int L, uint32_t m, fe* node, fe* weight, const fe* yj, fe* lam) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= m + n) return;
+    const fe zeta = qb_zeta(L);
+    const bool on_coset = t >= m;
+    const uint32_t pos = on_coset ? t - m : 0u, idx = on_coset ? perm[pos] : t;
+    const bool dropped = on_coset && pos >= m - 1;
+    const fe e = on_coset ? Fr::mul(zeta, pw[idx]) : pw[idx];
+    fe zs = Fr::one(), zj = Fr::one();
+    for (uint32_t s = m; s < n; s++) zs = Fr::mul(zs, Fr::sub(e, pw[s]));
+    for (uint32_t q = m - 1; q < n; q++) if (!(dropped && q == pos)) zj = Fr::mul(zj, Fr::sub(e, yj[q - (m - 1)]));      // (dropped: Z_J'(e))
+    const fe two_n = Fr::from_u32(2 * n);
+    if (dropped) {
+        lam[pos - (m - 1)] = Fr::mul(Fr::mul(two_n, zs), Fr::inv(Fr::mul(e, zj)));
+    } else {
+        fe w = Fr::mul(Fr::mul(e, zj), Fr::inv(Fr::mul(two_n, zs)));
+        if (!on_coset) w = Fr::mul(w, qb_fr_pow(Fr::from_u32(2), 261));
+        const uint32_t p = on_coset ? m + pos : t;
+        node[p] = e; weight[p] = w;
+    }
+}
+
+// scal[q * batch + b] = lambda_q weight_p / (y_q - node_p) as a canonical integer, p = p0 + b (columns beyond ncols repeat the last one):
+// the scalar matrix of the windowed MSM over the dropped bases, [base][column].  A thread inverts its QF_ROWS differences at once.
+constexpr int QF_ROWS = 16;
+__global__ __launch_bounds__(64) void k_qf_scalars(const fe* node, const fe* weight, const fe* yj, const fe* lam, uint32_t nj, uint32_t p0, uint32_t ncols, size_t batch, fe* scal) {
+    const size_t b = (size_t)blockIdx.x * 64 + threadIdx.x;
+    const uint32_t q0 = blockIdx.y * QF_ROWS, p = p0 + b < ncols ? p0 + (uint32_t)b : ncols - 1;
+    const fe e = node[p], w = weight[p];
+    fe pre[QF_ROWS], run = Fr::one();
+#pragma unroll
+    for (int k = 0; k < QF_ROWS; k++) {
+        pre[k] = run;
+        if (q0 + k < nj) run = Fr::mul(run, Fr::sub(yj[q0 + k], e));
+    }
+    fe inv = Fr::inv(run);
+#pragma unroll
+    for (int k = QF_ROWS - 1; k >= 0; k--) {
+        if (q0 + k >= nj) continue;
+        const fe one_over = Fr::mul(inv, pre[k]);
+        inv = Fr::mul(inv, Fr::sub(yj[q0 + k], e));
+        store_fe(scal + (size_t)(q0 + k) * batch + b, Fr::from_mont(Fr::mul(Fr::mul(lam[q0 + k], w), one_over)));
+    }
+}
+
+// out[i] = base[i] + sum[i] with the exact group law, affine in the table builders' layout; status 2 = the point at infinity
+__global__ __launch_bounds__(64) void k_qf_add(const Aff<Fp>* base, const uint8_t* base_status, const fe* sum, uint32_t n, Aff<Fp>* out, uint8_t* status) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    Xyzz9<Fp29f> p = G1x::load_xyzz(sum + 4 * (size_t)i);
+    if (base_status[i] != 2) p = G1x::add(p, G1x::from_aff(Aff9<Fp29f>{qb_to_fp29(base[i].x), qb_to_fp29(base[i].y)}));
+    if (p.inf) { status[i] = 2; out[i] = Aff<Fp>{Fp::zero(), Fp::zero()}; return; }
+    const Aff9<Fp29f> a = G1x::to_aff(p);
+    out[i] = Aff<Fp>{qb_from_fp29(a.x), qb_from_fp29(a.y)};
+    status[i] = 0;
+}
+
+// TEST HOOK: out[i] = a[i] + b[i] as canonical big-endian X | Y (zeros and flag 1 for the point at infinity)
+__global__ __launch_bounds__(64) void k_qf_sum_be(const fe* a, const fe* b, uint32_t n, uint8_t* out, uint8_t* flags) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const Xyzz9<Fp29f> p = G1x::add(G1x::load_xyzz(a + 4 * (size_t)i), G1x::load_xyzz(b + 4 * (size_t)i));
+    fe xy[2] = {fe{}, fe{}};
+    if (!p.inf) { const Aff9<Fp29f> q = G1x::to_aff(p); xy[0] = Fp29::pack(Fp29::from_mont(q.x)); xy[1] = Fp29::pack(Fp29::from_mont(q.y)); }
+    flags[i] = p.inf ? 1 : 0;
+    for (int c = 0; c < 2; c++) for (int k = 0; k < 32; k++) out[64 * (size_t)i + 32 * c + k] = (uint8_t)(xy[c].l[7 - k / 4] >> (8 * (3 - k % 4)));
+}
+
 }  // namespace
+
+void launch_quot_fold_weights(const fe* omega, const uint32_t* perm, int L, uint32_t m, fe* pw, fe* node, fe* weight, fe* yj, fe* lam, hipStream_t s) {
+    const uint32_t n = 1u << L;
+    hipLaunchKernelGGL(k_qf_powers, dim3((n + 63) / 64), dim3(64), 0, s, omega, perm, n, L, m, pw, yj);
+    hipLaunchKernelGGL(k_qf_weights, dim3((m + n + 63) / 64), dim3(64), 0, s, pw, perm, n, L, m, node, weight, yj, lam);
+}
+void launch_quot_fold_scalars(const fe* node, const fe* weight, const fe* yj, const fe* lam, uint32_t nj, uint32_t p0, uint32_t ncols, size_t batch, fe* scal, hipStream_t s) {
+    hipLaunchKernelGGL(k_qf_scalars, dim3((unsigned)(batch / 64), (nj + QF_ROWS - 1) / QF_ROWS), dim3(64), 0, s, node, weight, yj, lam, nj, p0, ncols, batch, scal);
+}
+void launch_quot_fold_add(const G1Aff* base, const uint8_t* base_status, const G1Xyzz* sum, size_t n, G1Aff* out, uint8_t* status, hipStream_t s) {
+    if (n) hipLaunchKernelGGL(k_qf_add, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, reinterpret_cast<const Aff<Fp>*>(base), base_status, reinterpret_cast<const fe*>(sum), (uint32_t)n, reinterpret_cast<Aff<Fp>*>(out), status);
+}
+void launch_g1_sum_be(const G1Xyzz* a, const G1Xyzz* b, size_t n, uint8_t* out, uint8_t* flags, hipStream_t s) {
+    if (n) hipLaunchKernelGGL(k_qf_sum_be, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, reinterpret_cast<const fe*>(a), reinterpret_cast<const fe*>(b), (uint32_t)n, out, flags);
+}
 
 void launch_quot_bases(const G1Aff* zfile, const uint8_t* zstatus, int L, int mode, const fe* omega_inv, const fe* n_inv,
                        fe* tw, G1Xyzz* scratch, const uint32_t* perm, G1Aff* out, uint8_t* status, hipStream_t s) {

@@ -164,6 +164,17 @@ inline uint32_t quot_digit_index(int L, uint32_t t) {
 // perm (device, n entries, or nullptr): out[i] = the point of index perm[i] instead of i.
 void launch_quot_bases(const G1Aff* zfile, const uint8_t* zstatus, int L, int mode, const fe* omega_inv, const fe* n_inv,
                        fe* tw, G1Xyzz* scratch, const uint32_t* perm, G1Aff* out, uint8_t* status, hipStream_t s);
+// InitAlgorithm: the fold of the coset values that the domain's zero padding makes redundant (k_quot_bases.hip, "the fold").  With m
+// constraints the d of the table positions m - 1 .. n - 1 (perm: position -> coset index) are linear in c and in the other d; the fold's
+// 2m - 1 columns are the nodes x_p (p < m, base U_p) and the coset points of the positions p - m (base V at that position).
+// weights: pw (n elements, scratch), node and weight (2m - 1), yj and lam (n - m + 1), all Montgomery.
+void launch_quot_fold_weights(const fe* omega, const uint32_t* perm, int L, uint32_t m, fe* pw, fe* node, fe* weight, fe* yj, fe* lam, hipStream_t s);
+// scal[q * batch + b] = the canonical scalar of dropped base q in column p0 + b (columns beyond ncols repeat the last): launch_msm_recode's layout, mont = 0
+void launch_quot_fold_scalars(const fe* node, const fe* weight, const fe* yj, const fe* lam, uint32_t nj, uint32_t p0, uint32_t ncols, size_t batch, fe* scal, hipStream_t s);
+// out[i] = base[i] + sum[i] (exact group law; base_status[i] = 2: base i is the point at infinity), affine, status[i] = 2 for the point at infinity
+void launch_quot_fold_add(const G1Aff* base, const uint8_t* base_status, const G1Xyzz* sum, size_t n, G1Aff* out, uint8_t* status, hipStream_t s);
+// TEST HOOK: out[i] = a[i] + b[i] as 64 B big-endian canonical X | Y, flags[i] = 1 for the point at infinity
+void launch_g1_sum_be(const G1Xyzz* a, const G1Xyzz* b, size_t n, uint8_t* out, uint8_t* flags, hipStream_t s);
 
 // ---- multi-scalar multiplication (k_msm_win.hip, k_msm.hip) ----
 // Launchers are typed by group: overloads where the point pointers say which one is meant, templates on the affine point type (G1Aff, G2Aff;
@@ -218,6 +229,9 @@ struct MsmWinArgs {
     // TEST HOOK (timing experiment, WRONG sums): every gather's entry index is masked to this many bits, i.e. the kernel does the same arithmetic over rows of
     // 2^bits entries — the L2 hit rate it would have with that many lanes per entry in flight.  0 = off.
     uint32_t exp_entry_mask = 0;
+    // the bases the digit buffer was laid out for when that is more than the nbases this launch walks (0: nbases) — the folded Z set, whose digits
+    // the last quotient kernel writes for all n positions
+    size_t digit_bases = 0;
 };
 template <class AffT> void launch_msm_win(const MsmWinArgs& a, hipStream_t s);
 // The same partial sums for the first `nproofs` proofs only (columns nproofs .. batch-1 of `partial` are not written): lanes are bases

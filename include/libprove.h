@@ -139,6 +139,9 @@ extern int gsc_debug_clock_trace(uint32_t n, uint32_t interval_us, unsigned long
  * non-zero in the algorithm's device buffers — the engine clears them behind the last kernel of every call, so 0; -1 on error / hooks disabled. */
 extern long long gsc_debug_secret_residue(GoUint8 algorithmID);
 extern long long gsc_debug_compute_d(GoUint8 algorithmID, const uint8_t *ab_be, size_t m, uint8_t *d_out, size_t cap);
+// TEST HOOK: the evaluation-form quotient sum (sum c_i U_i + sum d_i V_i) of 64 columns through the batch kernels and whatever sets InitAlgorithm built.
+// abc_be: a, b, c = a b row by row, [m][64] canonical big-endian values; out: 64 x 64 B big-endian X | Y; flags[i] = 1: the point at infinity.  0 on success.
+extern int gsc_debug_z_sum(GoUint8 algorithmID, const uint8_t *abc_be, size_t m, uint8_t *out, uint8_t *flags);
 /* TEST HOOK (host arithmetic only, no GPU): the GLV split the latency path feeds to its scalar multiplications
  * (csrc/glv.hpp).  k: canonical scalar < r, 32 bytes little-endian.  out: 20 bytes |k1|, 20 bytes |k2| (little-endian), 4 bytes
  * flags (bit 0: k1 < 0, bit 1: k2 < 0) with k = k1 + k2 * lambda (mod r).  Returns 0, -1 on error. */
