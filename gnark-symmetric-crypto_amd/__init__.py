@@ -20,7 +20,7 @@ CHACHA20, AES_128, AES_256 = 0, 1, 2                       # prove_impl.go:15-19
 ALGORITHM_NAMES = {0: "chacha20", 1: "aes-128-ctr", 2: "aes-256-ctr"}   # prove_impl.go:21-25
 
 EXPORTS = ["enforce_binding", "InitAlgorithm", "Free", "Prove", "ProveBatch", "gsc_prove_raw", "gsc_setup",
-           "gsc_set_deterministic_randomness", "gsc_debug_prove", "gsc_debug_vector", "gsc_describe", "gsc_last_stage_ms", "gsc_last_dominant_kernel", "gsc_last_kernel_clock", "gsc_debug_field_ops", "gsc_debug_limb_ops", "gsc_debug_curve_ops", "gsc_debug_tower_ops", "gsc_debug_compute_h", "gsc_debug_compute_d", "gsc_debug_z_sum", "gsc_debug_secret_residue", "gsc_debug_clock_trace", "gsc_debug_glv_split",
+           "gsc_set_deterministic_randomness", "gsc_debug_prove", "gsc_debug_vector", "gsc_describe", "gsc_last_stage_ms", "gsc_last_dominant_kernel", "gsc_last_kernel_clock", "gsc_debug_field_ops", "gsc_debug_limb_ops", "gsc_debug_curve_ops", "gsc_debug_tower_ops", "gsc_debug_compute_h", "gsc_debug_compute_d", "gsc_debug_z_sum", "gsc_debug_quot_fold_dft", "gsc_debug_secret_residue", "gsc_debug_clock_trace", "gsc_debug_glv_split",
            "gsc_verify_init", "gsc_verify_raw", "VerifyBatch", "gsc_debug_pairing",
            "gsc_verify_raw_batched", "gsc_verify_all", "VerifyAll", "gsc_debug_verify_randomizers",
            "gsc_verify_json", "gsc_verify_last_path", "gsc_debug_verify_path", "gsc_debug_pairing_few",
@@ -395,6 +395,22 @@ def debug_z_sum(algorithm_id: int, abc_be: bytes, m: int):
     if L.gsc_debug_z_sum(algorithm_id, abc_be, m, out, flags) != 0:
         raise RuntimeError("gsc_debug_z_sum failed")
     return out.raw, flags.raw
+
+
+def debug_quot_fold_dft(L: int, m: int, perm, u_be: bytes, u_inf: bytes, v_be: bytes, v_inf: bytes):
+    """TEST HOOK: the fold of the redundant quotient bases by three group transforms on caller-supplied bases (no InitAlgorithm).  n = 2^L;
+    perm: n table positions -> coset indices, or None for the identity; u_be (m) and v_be (n, table order): 64 B big-endian X | Y per point with
+    infinity flags -> (U' bytes, U' flags, V' bytes, V' flags) for m and m - 1 points.  Raises RuntimeError when the library returns -1."""
+    lb = lib()
+    n = 1 << L
+    lb.gsc_debug_quot_fold_dft.restype = C.c_int
+    lb.gsc_debug_quot_fold_dft.argtypes = [C.c_int, C.c_uint32, C.c_void_p] + [C.c_char_p] * 4 + [C.c_void_p] * 4
+    assert len(u_be) == 64 * m and len(u_inf) == m and len(v_be) == 64 * n and len(v_inf) == n and (perm is None or len(perm) == n)
+    pm = (C.c_uint32 * n)(*perm) if perm is not None else None
+    u2, f2, v2, g2 = C.create_string_buffer(64 * m), C.create_string_buffer(m), C.create_string_buffer(64 * max(m - 1, 1)), C.create_string_buffer(max(m - 1, 1))
+    if lb.gsc_debug_quot_fold_dft(L, m, pm, u_be, u_inf, v_be, v_inf, u2, f2, v2, g2) != 0:
+        raise RuntimeError("gsc_debug_quot_fold_dft failed")
+    return u2.raw, f2.raw, v2.raw[:64 * (m - 1)], g2.raw[:m - 1]
 
 
 # ---- GPU verifier in libprove.so (k_verify.hip): verdicts identical to libverify's Verify ----

@@ -530,6 +530,13 @@ int gsc_debug_z_sum(GoUint8 algorithmID, const uint8_t* abc_be, size_t m, uint8_
     catch (const std::exception& e) { printf("%s\n", e.what()); return -1; }
 }
 
+int gsc_debug_quot_fold_dft(int L, uint32_t m, const uint32_t* perm, const uint8_t* u_be, const uint8_t* u_inf, const uint8_t* v_be, const uint8_t* v_inf,
+                            uint8_t* u2_be, uint8_t* u2_inf, uint8_t* v2_be, uint8_t* v2_inf) {
+    if (hooks_refused("gsc_debug_quot_fold_dft") || L < 2 || L > 17 || m < 2 || m > (1u << L) || !u_be || !u_inf || !v_be || !v_inf || !u2_be || !u2_inf || !v2_be || !v2_inf) return -1;
+    try { debug_quot_fold_dft(config_from_env().device, L, m, perm, u_be, u_inf, v_be, v_inf, u2_be, u2_inf, v2_be, v2_inf); return 0; }
+    catch (const std::exception& e) { printf("%s\n", e.what()); return -1; }
+}
+
 size_t gsc_describe(GoUint8 algorithmID, char* out, size_t cap) {
     if (algorithmID > 2 || !cap) return 0;
     Algorithm* a = lookup(algorithmID);

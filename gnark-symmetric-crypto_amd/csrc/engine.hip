@@ -50,6 +50,7 @@ EngineConfig config_from_env() {
     c.quotient_eval = env_int("GSC_QUOTIENT_EVAL", 1);
     c.fuse_z_digits = env_int("GSC_FUSE_Z_DIGITS", 1);
     c.quotient_fold = env_int("GSC_QUOTIENT_FOLD", 1);
+    if (c.quotient_fold < 0 || c.quotient_fold > 2) throw std::runtime_error("GSC_QUOTIENT_FOLD must be 0, 1 or 2");
     c.small_witness = env_int("GSC_SMALL_WITNESS", 1);
     c.small_witness_few = env_int("GSC_SMALL_WITNESS_FEW", 1);
     c.ntt_plain = env_int("GSC_NTT_PLAIN", 1) ? 1 : 0;
@@ -142,6 +143,34 @@ bool debug_tower_ops(int device, int path, int op, const int32_t* in, size_t n, 
     return true;
 }
 
+void debug_quot_fold_dft(int device, int L, uint32_t m, const uint32_t* perm, const uint8_t* u_be, const uint8_t* u_inf, const uint8_t* v_be, const uint8_t* v_inf,
+                         uint8_t* u2_be, uint8_t* u2_inf, uint8_t* v2_be, uint8_t* v2_inf) {
+    const size_t n = (size_t)1 << L;
+    std::vector<uint32_t> pm(n);
+    {      // position -> coset index: a permutation, or the kernels' scatter would leave slots unwritten (or land outside the array)
+        std::vector<uint8_t> seen(n, 0);
+        for (size_t i = 0; i < n; i++) { pm[i] = perm ? perm[i] : (uint32_t)i; if (pm[i] >= n || seen[pm[i]]++) throw std::runtime_error("gsc_debug_quot_fold_dft: perm is not a permutation of 0 .. n - 1"); }
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) throw std::runtime_error("no HIP device available");
+    HIP_CHECK(hipSetDevice(device));
+    DevBuf<uint32_t> d_perm(n);
+    DevBuf<uint8_t> d_be((m + n) * 64), d_inf(m + n), d_stU(m), d_stV(n), d_stU2(m), d_stV2(m - 1), d_out((2 * (size_t)m - 1) * 64), d_flags(2 * (size_t)m - 1), scratch(quot_fold_dft_scratch_bytes(L, m));
+    DevBuf<G1Aff> d_U(m), d_V(n), d_U2(m), d_V2(m - 1);
+    HIP_CHECK(hipMemcpy(d_perm.p, pm.data(), 4 * n, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(d_be.p, u_be, 64 * (size_t)m, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(d_be.p + 64 * (size_t)m, v_be, 64 * n, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(d_inf.p, u_inf, m, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(d_inf.p + m, v_inf, n, hipMemcpyHostToDevice));
+    launch_g1_aff_from_be(d_be.p, d_inf.p, m, d_U.p, d_stU.p, nullptr);
+    launch_g1_aff_from_be(d_be.p + 64 * (size_t)m, d_inf.p + m, n, d_V.p, d_stV.p, nullptr);
+    launch_quot_fold_dft(L, m, d_perm.p, d_U.p, d_stU.p, d_V.p, d_stV.p, d_U2.p, d_stU2.p, d_V2.p, d_stV2.p, scratch.p, nullptr);
+    launch_g1_aff_to_be(d_U2.p, d_stU2.p, m, d_out.p, d_flags.p, nullptr);
+    launch_g1_aff_to_be(d_V2.p, d_stV2.p, m - 1, d_out.p + 64 * (size_t)m, d_flags.p + m, nullptr);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipMemcpy(u2_be, d_out.p, 64 * (size_t)m, hipMemcpyDeviceToHost)); HIP_CHECK(hipMemcpy(u2_inf, d_flags.p, m, hipMemcpyDeviceToHost));
+    if (m > 1) { HIP_CHECK(hipMemcpy(v2_be, d_out.p + 64 * (size_t)m, 64 * (size_t)(m - 1), hipMemcpyDeviceToHost)); HIP_CHECK(hipMemcpy(v2_inf, d_flags.p + m, m - 1, hipMemcpyDeviceToHost)); }
+}
+
 void debug_clock_trace(int device, uint32_t n, uint32_t interval_us, unsigned long long* out) {
     HIP_CHECK(hipSetDevice(device));
     hipStream_t st; HIP_CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
@@ -196,7 +225,7 @@ std::string Algorithm::describe() const {
     std::string out = buf;
     if (impl_->quotient_eval) out += std::string(" quotient=evaluation-form") + (impl_->fuse_z_digits ? "+digits" : "") + (!impl_->fuse_z_digits || !impl_->cfg.overlap_quotient ? "" : impl_->cfg.overlap_quotient == 2 ? "+beside-wire-sets" : "+beside-wire-sets(<4096)") + "(c: " + std::to_string(impl_->mC.nbit) + " grouped + " + std::to_string(impl_->mC.nflat - impl_->mC.nbit) + " flat + " + std::to_string(impl_->mC.nwide) + " windowed)";
     else out += " quotient=coefficient-form";
-    if (impl_->quotient_eval) out += impl_->mZ.digit_bases ? " Zlive=" + std::to_string(impl_->mZ.nwide) : " Zfold=off(" + impl_->fold_why + ")";
+    if (impl_->quotient_eval) out += impl_->mZ.digit_bases ? " Zlive=" + std::to_string(impl_->mZ.nwide) + " Zfold=" + impl_->fold_route : " Zfold=off(" + impl_->fold_why + ")";
     out += impl_->small.ok ? " witness=small-integer(" + std::to_string(impl_->small.n_levels) + " chained levels, fallbacks " + std::to_string(impl_->small_fallbacks.load()) + ")" : " witness=generic" + (impl_->small.why.empty() ? std::string() : "(" + impl_->small.why + ")");
     out += " served(calls/statements)=";
     const auto sv = picker_->served();

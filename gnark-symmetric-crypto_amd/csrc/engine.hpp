@@ -54,7 +54,8 @@ struct EngineConfig {
                                  // bases V_i plus a flat sum over the solver's c); 0 = coefficient form for every call (six transforms, the key's own Z bases)
     int fuse_z_digits = 1;       // GSC_FUSE_Z_DIGITS: in evaluation form the last quotient kernel writes the signed digits of d itself (no scalar vector, no recoding pass); 0 = it writes d
     int quotient_fold = 1;       // GSC_QUOTIENT_FOLD: in evaluation form, the bases of the coset values that the domain's zero padding makes redundant are folded into the others at
-                                 // InitAlgorithm (k_quot_bases.hip, "the fold": n - m + 1 of the n Z bases are never walked again); 0 = the sets as the key gives them.  Same bytes
+                                 // InitAlgorithm (k_quot_bases.hip, "the fold": n - m + 1 of the n Z bases are never walked again).  1 = by the dense sums where their init cost
+                                 // allows it (ChaCha20-V3), by three group transforms otherwise (AES-V2); 2 = by the transforms always; 0 = the sets as the key gives them.  Same bytes
     int small_witness = 1;       // GSC_SMALL_WITNESS: circuits whose whole witness is small integers (ChaCha20-V3) are solved by the integer kernels on byte planes
                                  // (wit_small.hpp) in every call beyond the latency path; 0 = always the generic field-arithmetic solver;
                                  // 2 (test hooks only) = every constraint row predicted narrow: the kernels notice, the chunk is solved again generically
@@ -126,6 +127,11 @@ class Algorithm {
     mutable std::atomic<size_t> last_replica_{0};            // the replica whose chunk finished last (last_kernel_stat)
 };
 
+// TEST HOOK: the fold of the redundant quotient bases by three group transforms (launch_quot_fold_dft) on caller-supplied bases; no key, no algorithm.
+// n = 2^L, 2 <= m <= n; perm: n entries, table position -> coset index (nullptr: the identity); u (m points) and v (n points, table order): 64 B canonical
+// big-endian X | Y each, *_inf[i] = 1: the point at infinity.  Out: U' (m) and V' (m - 1) in the same format.  Throws on HIP errors and on a perm that is none.
+void debug_quot_fold_dft(int device, int L, uint32_t m, const uint32_t* perm, const uint8_t* u_be, const uint8_t* u_inf, const uint8_t* v_be, const uint8_t* v_inf,
+                         uint8_t* u2_be, uint8_t* u2_inf, uint8_t* v2_be, uint8_t* v2_inf);
 // TEST HOOK: samples the device's shader clock for n x interval_us microseconds beside whatever else runs (a resident one-wave kernel on a
 // stream of its own); out: n pairs {100 MHz clock, shader clock}.  Blocks until the samples are in.
 void debug_clock_trace(int device, uint32_t n, uint32_t interval_us, unsigned long long* out);

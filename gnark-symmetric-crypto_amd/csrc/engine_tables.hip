@@ -389,6 +389,32 @@ bool AlgorithmImpl::fold_quotient_bases(const DevBuf<G1Aff>& d_U, const std::vec
     return true;
 }
 
+// The same U' and V' from three group transforms (launch_quot_fold_dft): no table, no scalar matrix — 3 n points and the weights as scratch.
+bool AlgorithmImpl::fold_quotient_bases_dft(const DevBuf<G1Aff>& d_U, const std::vector<uint8_t>& stU, const DevBuf<G1Aff>& d_V, const std::vector<uint8_t>& stV, const std::vector<uint32_t>& rowsZ,
+                                            DevBuf<G1Aff>& d_U2, std::vector<uint8_t>& stU2, DevBuf<G1Aff>& d_V2, std::vector<uint8_t>& stV2) {
+    const size_t m = n_constraints;
+    DevBuf<uint32_t> d_perm(domain_n); d_perm.upload(rowsZ.data(), domain_n, stream);
+    DevBuf<uint8_t> d_stU(m), d_stV(domain_n), d_stU2(m), d_stV2(m - 1), scratch(quot_fold_dft_scratch_bytes(L, (uint32_t)m));
+    d_stU.upload(stU.data(), m, stream); d_stV.upload(stV.data(), domain_n, stream);
+    d_U2.alloc(m); d_V2.alloc(m - 1); stU2.resize(m); stV2.resize(m - 1);
+    hipEvent_t ev[3]; for (auto& e : ev) HIP_CHECK(hipEventCreate(&e));
+    struct Free { hipEvent_t* e; ~Free() { for (int i = 0; i < 3; i++) (void)hipEventDestroy(e[i]); } } free_ev{ev};
+    HIP_CHECK(hipEventRecord(ev[0], stream));
+    launch_quot_fold_dft(L, (uint32_t)m, d_perm.p, d_U.p, d_stU.p, d_V.p, d_stV.p, d_U2.p, d_stU2.p, d_V2.p, d_stV2.p, scratch.p, stream, ev[1]);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipEventRecord(ev[2], stream));
+    HIP_CHECK(hipMemcpyAsync(stU2.data(), d_stU2.p, m, hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipMemcpyAsync(stV2.data(), d_stV2.p, m - 1, hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipStreamSynchronize(stream));
+    if (cfg.trace_host) {
+        float w = 0, t = 0; HIP_CHECK(hipEventElapsedTime(&w, ev[0], ev[1])); HIP_CHECK(hipEventElapsedTime(&t, ev[1], ev[2]));
+        fprintf(stderr, "  tables G1.Z fold (dft): weights %.0f ms, transforms %.0f ms\n", w, t);
+    }
+    if (std::count(stV2.begin(), stV2.end(), (uint8_t)0) != (ptrdiff_t)(m - 1)) { fold_why = "a folded V base is the point at infinity"; return false; }
+    fold_why.clear();
+    return true;
+}
+
 void AlgorithmImpl::init_key(const R1csFile& cs, const PkFile& key) {
     if (key.n_wires != n_wires) throw std::runtime_error("pk: wire count does not match the r1cs");
     domain_n = key.domain_n; L = 0; while (((size_t)1 << L) < domain_n) L++;
@@ -500,15 +526,18 @@ void AlgorithmImpl::init_key(const R1csFile& cs, const PkFile& key) {
             };
         };
         // The fold: positions m - 1 .. n - 1 of the table order leave the Z set, their bases go into U and into the live V (k_quot_bases.hip).
-        // Gated on its init cost, on a key without points at infinity among V (positions must not shift) and on there being something to drop.
+        // Gated on a key without points at infinity among V (positions must not shift) and on there being something to drop.  Route: the dense sums
+        // where their init cost passes FOLD_MAX_SCALAR_MULS (ChaCha20-V3), otherwise — or always, GSC_QUOTIENT_FOLD=2 — the three transforms.
         DevBuf<G1Aff> d_U2, d_V2; std::vector<uint8_t> stU2, stV2;
         size_t live = domain_n;
         const double fold_cost = (2.0 * (double)n_constraints - 1.0) * (double)(domain_n - n_constraints + 1);
         if (cfg.quotient_fold) {
+            const bool dense = cfg.quotient_fold == 1 && fold_cost <= FOLD_MAX_SCALAR_MULS;
             if (n_constraints < 2 || domain_n - n_constraints + 1 < domain_n / 64) fold_why = "nothing to drop";
-            else if (fold_cost > FOLD_MAX_SCALAR_MULS) { char b[96]; snprintf(b, sizeof b, "init cost %.1e scalar multiplications > %.0e", fold_cost, FOLD_MAX_SCALAR_MULS); fold_why = b; }
             else if (std::count(stV.begin(), stV.end(), (uint8_t)0) != (ptrdiff_t)domain_n) fold_why = "a V base is the point at infinity";
-            else timed("G1.Z fold", [&] { if (fold_quotient_bases(d_U, stU, d_V, stV, rowsZ, d_U2, stU2, d_V2, stV2)) live = n_constraints - 1; });
+            else timed("G1.Z fold", [&] {
+                if (dense ? fold_quotient_bases(d_U, stU, d_V, stV, rowsZ, d_U2, stU2, d_V2, stV2) : fold_quotient_bases_dft(d_U, stU, d_V, stV, rowsZ, d_U2, stU2, d_V2, stV2)) { live = n_constraints - 1; fold_route = dense ? "dense" : "dft"; }
+            });
         }
         const bool folded = live != domain_n;
         const std::vector<uint8_t> rawV(live * 32, 0), rawU(n_constraints * 32, 0);      // build_set only takes the point count from these

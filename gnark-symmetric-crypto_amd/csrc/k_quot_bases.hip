@@ -199,7 +199,120 @@ __global__ __launch_bounds__(64) void k_qf_sum_be(const fe* a, const fe* b, uint
     for (int c = 0; c < 2; c++) for (int k = 0; k < 32; k++) out[64 * (size_t)i + 32 * c + k] = (uint8_t)(xy[c].l[7 - k / 4] >> (8 * (3 - k % 4)));
 }
 
+// ---- the fold as three group transforms ----------------------------------------------------------------------------------------------------
+// The dense route above spends one scalar multiplication per (column, dropped base).  Both sums are structured in the node index:
+// with W_j = lambda_j V_j (j in J; the point at infinity elsewhere) and W^_k = sum_j w^(-jk) W_j (one transform of size n),
+//   x nodes (i < m):      y^n - x^n = -2 = (y - x) sum_k y^(n-1-k) x^k, hence
+//     sum_J W_j / (y_j - x_i) = -1/2 sum_k w^(ik) zeta^(n-1-k) W^_((k+1) mod n);
+//   coset nodes (i in I): 1 / (y_j - y_i) = g(j - i) / y_i with g(d) = 1 / (w^d - 1), g(0) = 0 — a cyclic correlation, and
+//     g^_k = sum_d g(d) w^(dk) is closed-form, g^_0 = (1 - n) / 2, g^_k = (n + 1) / 2 - k (0 < k < n), hence
+//     sum_J W_j / (y_j - y_i) = 1 / (n y_i) sum_k w^(ik) g^_k W^_k.
+// The outer sums run in the other direction: k_qb_stage's transform, read at index (-i) mod n.  U'_i = U_i - (weight_i / 2) A^[-i],
+// V'_i = V_i + (weight_i / (n y_i)) G^[-i]: the same group elements as the dense route's, hence the same affine bases.
+// tests/test_quot_fold_dft_host.py checks the identities on integers.
+
+// cst[0] = w = zeta^2, cst[1] = w^-1 = w^(n-1) (Montgomery): what k_qf_powers and k_qb_twiddles take from the key's domain record
+__global__ void k_qfd_consts(int L, fe* cst) {
+    if (blockIdx.x || threadIdx.x) return;
+    const fe w = Fr::sqr(qb_zeta(L));
+    cst[0] = w; cst[1] = qb_fr_pow(w, (1u << L) - 1u);
+}
+
+// Y[bitrev(j)] = lambda_q V(position m - 1 + q), j = perm[position]; the point at infinity for the coset indices that stay (and for a dropped V
+// that is the point at infinity)
+__global__ __launch_bounds__(64) void k_qfd_load(const Aff<Fp>* V, const uint8_t* status, const uint32_t* perm, uint32_t n, int L, uint32_t m, const fe* lam, fe* Y) {
+    const uint32_t pos = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pos >= n) return;
+    fe* dst = Y + 4 * (size_t)(__brev(perm[pos]) >> (32 - L));
+    if (pos < m - 1 || status[pos] == 2) { G1x::store_xyzz(dst, G1x::infinity()); return; }
+    const Aff9<Fp29f> P{qb_to_fp29(V[pos].x), qb_to_fp29(V[pos].y)};
+    G1x::store_xyzz(dst, qb_scalar_mul(G1x::from_aff(P), Fr::from_mont(lam[pos - (m - 1)])));
+}
+
+// The second pass's inputs from W^ (natural order), written in bit-reversed order.  mode 0: zeta^(n-1-k) W^_((k+1) mod n); mode 1: g^_k W^_k
+__global__ __launch_bounds__(64) void k_qfd_pointwise(const fe* What, uint32_t n, int L, int mode, fe* Y) {
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    fe s; uint32_t src = k;
+    if (mode == 0) { s = qb_fr_pow(qb_zeta(L), n - 1 - k); src = (k + 1) & (n - 1); }
+    else {
+        const fe half = Fr::inv(Fr::from_u32(2));
+        s = k ? Fr::sub(Fr::mul(Fr::from_u32(n + 1), half), Fr::from_u32(k)) : Fr::neg(Fr::mul(Fr::from_u32(n - 1), half));
+    }
+    const Xyzz9<Fp29f> p = G1x::load_xyzz(What + 4 * (size_t)src);
+    G1x::store_xyzz(Y + 4 * (size_t)(__brev(k) >> (32 - L)), qb_scalar_mul(p, Fr::from_mont(s)));
+}
+
+// Column p of the fold (k_qf_weights): p < m the node x_p, out U'_p = U_p - (weight_p / 2) Ax[-p]; p >= m the coset node of table position
+// p - m, index i = perm[p - m], out V'_(p-m) = V_(p-m) + (weight_p / (n node_p)) Gy[-i].  Affine bases and statuses as k_qf_add writes them.
+__global__ __launch_bounds__(64) void k_qfd_finish(const fe* Ax, const fe* Gy, const uint32_t* perm, uint32_t n, uint32_t m, const fe* node, const fe* weight,
+                                                   const Aff<Fp>* U, const uint8_t* stU, const Aff<Fp>* V, const uint8_t* stV, Aff<Fp>* U2, uint8_t* stU2, Aff<Fp>* V2, uint8_t* stV2) {
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= 2 * m - 1) return;
+    const bool on_coset = p >= m;
+    const uint32_t o = on_coset ? p - m : p, i = on_coset ? perm[o] : p, at = (n - i) & (n - 1);
+    const fe s = on_coset ? Fr::mul(weight[p], Fr::inv(Fr::mul(Fr::from_u32(n), node[p]))) : Fr::neg(Fr::mul(weight[p], Fr::inv(Fr::from_u32(2))));
+    Xyzz9<Fp29f> q = qb_scalar_mul(G1x::load_xyzz((on_coset ? Gy : Ax) + 4 * (size_t)at), Fr::from_mont(s));
+    const Aff<Fp>& b = on_coset ? V[o] : U[o];
+    if ((on_coset ? stV[o] : stU[o]) != 2) q = G1x::add(q, G1x::from_aff(Aff9<Fp29f>{qb_to_fp29(b.x), qb_to_fp29(b.y)}));
+    Aff<Fp>* out = on_coset ? V2 + o : U2 + o; uint8_t* st = on_coset ? stV2 + o : stU2 + o;
+    if (q.inf) { *st = 2; *out = Aff<Fp>{Fp::zero(), Fp::zero()}; return; }
+    const Aff9<Fp29f> a = G1x::to_aff(q);
+    *out = Aff<Fp>{qb_from_fp29(a.x), qb_from_fp29(a.y)};
+    *st = 0;
+}
+
+// TEST HOOK: affine points between 64 B canonical big-endian X | Y with a flag (1: the point at infinity) and the bases' layout with a status (2)
+__global__ __launch_bounds__(64) void k_qfd_from_be(const uint8_t* be, const uint8_t* flags, uint32_t n, Aff<Fp>* out, uint8_t* status) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    fe xy[2] = {fe{}, fe{}};
+    for (int c = 0; c < 2; c++) for (int k = 0; k < 32; k++) xy[c].l[7 - k / 4] |= (uint32_t)be[64 * (size_t)i + 32 * c + k] << (8 * (3 - k % 4));
+    const bool inf = flags[i] != 0;
+    out[i] = inf ? Aff<Fp>{Fp::zero(), Fp::zero()} : Aff<Fp>{Fp::to_mont(xy[0]), Fp::to_mont(xy[1])};
+    status[i] = inf ? 2 : 0;
+}
+__global__ __launch_bounds__(64) void k_qfd_to_be(const Aff<Fp>* in, const uint8_t* status, uint32_t n, uint8_t* be, uint8_t* flags) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const bool inf = status[i] == 2;
+    fe xy[2] = {fe{}, fe{}};
+    if (!inf) { xy[0] = Fp::from_mont(in[i].x); xy[1] = Fp::from_mont(in[i].y); }
+    flags[i] = inf ? 1 : 0;
+    for (int c = 0; c < 2; c++) for (int k = 0; k < 32; k++) be[64 * (size_t)i + 32 * c + k] = (uint8_t)(xy[c].l[7 - k / 4] >> (8 * (3 - k % 4)));
+}
+
 }  // namespace
+
+size_t quot_fold_dft_scratch_bytes(int L, uint32_t m) {
+    const size_t n = (size_t)1 << L, nj = n - m + 1;
+    return (2 + n + n / 2 + 2 * (2 * (size_t)m - 1) + 2 * nj) * sizeof(fe) + 3 * n * sizeof(G1Xyzz);
+}
+void launch_quot_fold_dft(int L, uint32_t m, const uint32_t* perm, const G1Aff* U, const uint8_t* stU, const G1Aff* V, const uint8_t* stV,
+                          G1Aff* U2, uint8_t* stU2, G1Aff* V2, uint8_t* stV2, void* scratch, hipStream_t s, hipEvent_t weights_done) {
+    const uint32_t n = 1u << L, hn = n / 2, nj = n - m + 1, ncols = 2 * m - 1, blocks = (n + 63) / 64;
+    fe* cst = static_cast<fe*>(scratch); fe* pw = cst + 2; fe* tw = pw + n; fe* node = tw + hn; fe* weight = node + ncols; fe* yj = weight + ncols; fe* lam = yj + nj;
+    fe* What = lam + nj; fe* Ax = What + 4 * (size_t)n; fe* Gy = Ax + 4 * (size_t)n;
+    hipLaunchKernelGGL(k_qfd_consts, dim3(1), dim3(64), 0, s, L, cst);
+    launch_quot_fold_weights(cst, perm, L, m, pw, node, weight, yj, lam, s);
+    if (weights_done) (void)hipEventRecord(weights_done, s);
+    hipLaunchKernelGGL(k_qb_twiddles, dim3((hn + 63) / 64), dim3(64), 0, s, cst + 1, hn, tw);
+    auto transform = [&](fe* Y) { for (int st = 0; st < L; st++) hipLaunchKernelGGL(k_qb_stage, dim3((hn + 63) / 64), dim3(64), 0, s, Y, hn, L, st, tw); };
+    hipLaunchKernelGGL(k_qfd_load, dim3(blocks), dim3(64), 0, s, reinterpret_cast<const Aff<Fp>*>(V), stV, perm, n, L, m, lam, What);
+    transform(What);
+    hipLaunchKernelGGL(k_qfd_pointwise, dim3(blocks), dim3(64), 0, s, What, n, L, 0, Ax);
+    hipLaunchKernelGGL(k_qfd_pointwise, dim3(blocks), dim3(64), 0, s, What, n, L, 1, Gy);
+    transform(Ax);
+    transform(Gy);
+    hipLaunchKernelGGL(k_qfd_finish, dim3((ncols + 63) / 64), dim3(64), 0, s, Ax, Gy, perm, n, m, node, weight, reinterpret_cast<const Aff<Fp>*>(U), stU,
+                       reinterpret_cast<const Aff<Fp>*>(V), stV, reinterpret_cast<Aff<Fp>*>(U2), stU2, reinterpret_cast<Aff<Fp>*>(V2), stV2);
+}
+void launch_g1_aff_from_be(const uint8_t* be, const uint8_t* flags, size_t n, G1Aff* out, uint8_t* status, hipStream_t s) {
+    if (n) hipLaunchKernelGGL(k_qfd_from_be, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, be, flags, (uint32_t)n, reinterpret_cast<Aff<Fp>*>(out), status);
+}
+void launch_g1_aff_to_be(const G1Aff* in, const uint8_t* status, size_t n, uint8_t* be, uint8_t* flags, hipStream_t s) {
+    if (n) hipLaunchKernelGGL(k_qfd_to_be, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, reinterpret_cast<const Aff<Fp>*>(in), status, (uint32_t)n, be, flags);
+}
 
 void launch_quot_fold_weights(const fe* omega, const uint32_t* perm, int L, uint32_t m, fe* pw, fe* node, fe* weight, fe* yj, fe* lam, hipStream_t s) {
     const uint32_t n = 1u << L;

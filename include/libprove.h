@@ -142,6 +142,11 @@ extern long long gsc_debug_compute_d(GoUint8 algorithmID, const uint8_t *ab_be, 
 // TEST HOOK: the evaluation-form quotient sum (sum c_i U_i + sum d_i V_i) of 64 columns through the batch kernels and whatever sets InitAlgorithm built.
 // abc_be: a, b, c = a b row by row, [m][64] canonical big-endian values; out: 64 x 64 B big-endian X | Y; flags[i] = 1: the point at infinity.  0 on success.
 extern int gsc_debug_z_sum(GoUint8 algorithmID, const uint8_t *abc_be, size_t m, uint8_t *out, uint8_t *flags);
+// TEST HOOK: the fold of the Z bases that the domain's zero padding makes redundant, by three group transforms, on caller-supplied bases (needs a device, no
+// InitAlgorithm).  n = 2^L, 2 <= L <= 17, 2 <= m <= n; perm: n entries, table position -> coset index (NULL: the identity); u_be (m points) and v_be (n points,
+// table order): 64 B big-endian X | Y each, *_inf[i] = 1: the point at infinity.  Out: U' (m) and V' (m - 1) in the same format.  0 on success, -1 on error.
+extern int gsc_debug_quot_fold_dft(int L, uint32_t m, const uint32_t *perm, const uint8_t *u_be, const uint8_t *u_inf, const uint8_t *v_be, const uint8_t *v_inf,
+                                   uint8_t *u2_be, uint8_t *u2_inf, uint8_t *v2_be, uint8_t *v2_inf);
 /* TEST HOOK (host arithmetic only, no GPU): the GLV split the latency path feeds to its scalar multiplications
  * (csrc/glv.hpp).  k: canonical scalar < r, 32 bytes little-endian.  out: 20 bytes |k1|, 20 bytes |k2| (little-endian), 4 bytes
  * flags (bit 0: k1 < 0, bit 1: k2 < 0) with k = k1 + k2 * lambda (mod r).  Returns 0, -1 on error. */
