@@ -51,6 +51,7 @@ EngineConfig config_from_env() {
     c.fuse_z_digits = env_int("GSC_FUSE_Z_DIGITS", 1);
     c.quotient_fold = env_int("GSC_QUOTIENT_FOLD", 1);
     if (c.quotient_fold < 0 || c.quotient_fold > 2) throw std::runtime_error("GSC_QUOTIENT_FOLD must be 0, 1 or 2");
+    c.quotient_live_tiles = env_int("GSC_QUOTIENT_LIVE_TILES", 1) ? 1 : 0;
     c.small_witness = env_int("GSC_SMALL_WITNESS", 1);
     c.small_witness_few = env_int("GSC_SMALL_WITNESS_FEW", 1);
     c.ntt_plain = env_int("GSC_NTT_PLAIN", 1) ? 1 : 0;
@@ -226,6 +227,7 @@ std::string Algorithm::describe() const {
     if (impl_->quotient_eval) out += std::string(" quotient=evaluation-form") + (impl_->fuse_z_digits ? "+digits" : "") + (!impl_->fuse_z_digits || !impl_->cfg.overlap_quotient ? "" : impl_->cfg.overlap_quotient == 2 ? "+beside-wire-sets" : "+beside-wire-sets(<4096)") + "(c: " + std::to_string(impl_->mC.nbit) + " grouped + " + std::to_string(impl_->mC.nflat - impl_->mC.nbit) + " flat + " + std::to_string(impl_->mC.nwide) + " windowed)";
     else out += " quotient=coefficient-form";
     if (impl_->quotient_eval) out += impl_->mZ.digit_bases ? " Zlive=" + std::to_string(impl_->mZ.nwide) + " Zfold=" + impl_->fold_route : " Zfold=off(" + impl_->fold_why + ")";
+    if (impl_->quotient_eval) out += " Qtiles=" + std::to_string(quot_live_tiles(impl_->L, impl_->quot_live)) + "/" + std::to_string(1u << (impl_->L - (impl_->L + 1) / 2));      // tiles the last quotient kernel runs
     out += impl_->small.ok ? " witness=small-integer(" + std::to_string(impl_->small.n_levels) + " chained levels, fallbacks " + std::to_string(impl_->small_fallbacks.load()) + ")" : " witness=generic" + (impl_->small.why.empty() ? std::string() : "(" + impl_->small.why + ")");
     out += " served(calls/statements)=";
     const auto sv = picker_->served();
@@ -268,8 +270,8 @@ void Algorithm::debug_z_sum(const uint8_t* abc_be, size_t m, uint8_t* out, uint8
         // rows m .. n - 1 of a, b, c (and the padding row of c) are zero in this call
         for (fe* mat : {ln.d_A.p, ln.d_B.p, ln.d_C.p}) HIP_CHECK(hipMemsetAsync(mat + m * B, 0, (a.domain_n - m) * B * sizeof(fe), ln.stream));
         HIP_CHECK(hipMemsetAsync(ln.d_C.p + a.domain_n * B, 0, B * sizeof(fe), ln.stream));
-        if (ck.rt.z_digits_ready) HIP_CHECK(launch_compute_d_digits(plan, ln.d_A.p, ln.d_B.p, a.n_constraints, B, QuotDigits{ln.d_digits.p, a.mZ.c, a.mZ.nwin}, ln.stream));
-        else HIP_CHECK(launch_compute_d(plan, ln.d_A.p, ln.d_B.p, a.n_constraints, B, ln.stream));
+        if (ck.rt.z_digits_ready) HIP_CHECK(launch_compute_d_digits(plan, ln.d_A.p, ln.d_B.p, a.n_constraints, B, QuotDigits{ln.d_digits.p, a.mZ.c, a.mZ.nwin}, ln.stream, nullptr, a.quot_live));
+        else HIP_CHECK(launch_compute_d(plan, ln.d_A.p, ln.d_B.p, a.n_constraints, B, ln.stream, 0, nullptr, a.quot_live));
         a.run_msm_g1(ln, ck, a.mC, ln.d_C.p, 1, ln.d_sumC.p);
         a.run_msm_g1(ln, ck, a.mZ, ln.d_A.p, 0, ln.d_sumZ.p, false, false, ck.rt.z_digits_ready);
         a.flush_horner<G1Aff>(ln.pending1, B, ln.stream);

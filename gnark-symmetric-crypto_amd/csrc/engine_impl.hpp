@@ -127,6 +127,9 @@ class AlgorithmImpl {
     // (U', V': valid only as a pair — mC and mZ are both folded or neither), mZ walks m - 1 bases.  fold_why: why not, for gsc_describe.
     std::string fold_why = "GSC_QUOTIENT_FOLD=0";
     const char* fold_route = "";      // "dense" or "dft" once the sets are folded (gsc_describe: Zfold=)
+    // ... and the evaluation-form quotient computes d for the live table positions only (launch_compute_d*'s live; cfg.quotient_live_tiles).  0: for all n —
+    // the sets are not folded, or the knob is off
+    size_t quot_live = 0;
     // The dense route's init cost gate: (2m - 1)(n - m + 1) scalar multiplications (ChaCha20-V3 4.3e8).  Beyond it (AES-V2: 8.5e9 and 6.6e9), and for
     // GSC_QUOTIENT_FOLD=2 whatever the size, the same sums come from three group transforms of size n (fold_quotient_bases_dft: AES-128 3.8e6).
     static constexpr double FOLD_MAX_SCALAR_MULS = 1e9;

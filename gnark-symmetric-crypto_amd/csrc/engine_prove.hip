@@ -326,8 +326,8 @@ void AlgorithmImpl::stage_quotient(Lane& ln, const Chunk& ck) {
             fetch_column(ln, ta.p, domain_n, B, 0, dbg->H);
         }
         if (rt.overlap_q) HIP_CHECK(hipStreamWaitEvent(qs, ln.ev[1], 0));      // the end of the witness stage
-        if (rt.z_digits_ready) HIP_CHECK(launch_compute_d_digits(plan, ln.d_A.p, ln.d_B.p, n_constraints, B, QuotDigits{ln.d_digits.p, mZ.c, mZ.nwin}, qs, narrow));
-        else HIP_CHECK(launch_compute_d(plan, ln.d_A.p, ln.d_B.p, n_constraints, B, ln.stream, few_cols, narrow));
+        if (rt.z_digits_ready) HIP_CHECK(launch_compute_d_digits(plan, ln.d_A.p, ln.d_B.p, n_constraints, B, QuotDigits{ln.d_digits.p, mZ.c, mZ.nwin}, qs, narrow, quot_live));
+        else HIP_CHECK(launch_compute_d(plan, ln.d_A.p, ln.d_B.p, n_constraints, B, ln.stream, few_cols, narrow, quot_live));      // (the recoding pass reads mZ's rows: live positions)
     } else HIP_CHECK(launch_compute_h(plan, ln.d_A.p, ln.d_B.p, ln.d_C.p, n_constraints, B, ln.stream, few_cols, narrow));
     HIP_CHECK(hipEventRecord(ln.ev[2], qs));
     if (dbg && !rt.eval) fetch_column(ln, ln.d_A.p, domain_n, B, 0, dbg->H);

@@ -544,7 +544,8 @@ void AlgorithmImpl::init_key(const R1csFile& cs, const PkFile& key) {
         const std::vector<uint32_t> rowsV(rowsZ.begin(), rowsZ.begin() + live);
         timed("G1.Z (V)", [&] { build_set<G1Aff, G1Xyzz>(mZ, rawV, 32, rowsV, cfg.window_z, "G1.Z (evaluation form)", folded ? from_dev(d_V2, stV2) : from_dev(d_V, stV), true); });
         fuse_z_digits = mZ.nwide == live && cfg.fuse_z_digits != 0;      // (a V_i at infinity would be dropped from the table: positions would shift)
-        if (folded) mZ.digit_bases = domain_n;      // the last quotient kernel writes digits for all n positions; the dropped ones are not read
+        if (folded) mZ.digit_bases = domain_n;      // the digit buffer keeps all n positions (the last quotient kernel's own indexing); the dropped ones are not read ...
+        quot_live = folded && cfg.quotient_live_tiles ? live : 0;      // ... nor, with this, written: whole tiles of that kernel hold nothing else and are not run
         timed("G1.Z (U)", [&] { build_set<G1Aff, G1Xyzz>(mC, rawU, 32, rowsC, cfg.window_w, "G1.Z (evaluation form, c)", folded ? from_dev(d_U2, stU2) : from_dev(d_U, stU), false, 0, &row_class_c, (uint32_t)domain_n, false); });
     }
     if (cfg.few_path && cfg.few_z_gb > 0) {

@@ -336,7 +336,9 @@ __global__ __launch_bounds__(512) void k_ntt_dif_strided(NttPlan pl, fe* v0, fe*
 }
 
 // K2: contiguous DIF tail, scale by zeta^j / n (and into the 2^261 domain), contiguous DIT head.  grid (2^Lhi, batch/P, 2: a, b); block (2^(Llo-2) * P)
-__global__ __launch_bounds__(256) void k_ntt_mid_contig(NttPlan pl, fe* v0, fe* v1, fe* v2, size_t batch) {
+// tiles: element e of this kernel's contiguous tile is loaded by workgroup e of K3 alone; when K3 runs its first `tiles` workgroups only (launch_quotient),
+// the elements e >= tiles are not stored.  Loads, stages and barriers are the same for every thread.
+__global__ __launch_bounds__(256) void k_ntt_mid_contig(NttPlan pl, fe* v0, fe* v1, fe* v2, size_t batch, uint32_t tiles) {
     extern __shared__ __attribute__((aligned(16))) int32_t smem[];
     const int L = pl.L, Lhi = (L + 1) / 2, Llo = L - Lhi;
     const uint32_t Cn = 1u << Llo;
@@ -372,6 +374,7 @@ __global__ __launch_bounds__(256) void k_ntt_mid_contig(NttPlan pl, fe* v0, fe* 
     __syncthreads();
     dit_run<false, true>(t, u4, q, 2, Llo, L, Llo, b, pl, Cn);
     for (uint32_t e = u4; e < Cn; e += Cn / 4) {
+        if (e >= tiles) break;      // (e grows: nothing further of this thread's is read)
         const size_t idx = ((size_t)b << Llo) + e;
         store_lazy(vec + idx * batch + q0 + q, t.get(e, q), pl.qr);
     }
@@ -387,6 +390,7 @@ __global__ __launch_bounds__(256) void k_ntt_mid_contig(NttPlan pl, fe* v0, fe* 
 // (kernels.hpp QuotDigits; the recoding of k_msm_win.hip k_recode for canonical scalars): its elements u4 + {0, 1, 2, 3} * G/4 are the
 // bases 4 m .. 4 m + 3, m = g * G/4 + u4, i.e. one half of octet m / 2 — one 16-byte word of four int32 digits per window when c > 16, half
 // a word of int16 digits otherwise.
+// EVAL != 0: the grid may stop short of 2^Llo tiles (launch_quotient: the fold's dead tiles): a tile reads, couples and writes its own positions only.
 template <int EVAL>
 __global__ __launch_bounds__(512) void k_ntt_pointwise_strided(NttPlan pl, fe* va, const fe* vb, size_t batch, QuotDigits qd) {
     extern __shared__ __attribute__((aligned(16))) int32_t smem[];
@@ -518,16 +522,16 @@ __global__ __launch_bounds__(256) void k_ntt_final_contig(NttPlan pl, fe* vh, co
 }  // namespace
 
 namespace {
-hipError_t launch_quotient(const NttPlan& p, fe* a, fe* b, fe* c, size_t m, size_t batch, hipStream_t s, size_t ncols, int eval, const QuotDigits& qd, const NttNarrow* narrow);
+hipError_t launch_quotient(const NttPlan& p, fe* a, fe* b, fe* c, size_t m, size_t batch, hipStream_t s, size_t ncols, int eval, const QuotDigits& qd, const NttNarrow* narrow, size_t live);
 }
-hipError_t launch_compute_h(const NttPlan& p, fe* a, fe* b, fe* c, size_t m, size_t batch, hipStream_t s, size_t ncols, const NttNarrow* narrow) { return launch_quotient(p, a, b, c, m, batch, s, ncols, 0, QuotDigits{nullptr, 0, 0}, narrow); }
-hipError_t launch_compute_d(const NttPlan& p, fe* a, fe* b, size_t m, size_t batch, hipStream_t s, size_t ncols, const NttNarrow* narrow) { return launch_quotient(p, a, b, nullptr, m, batch, s, ncols, 1, QuotDigits{nullptr, 0, 0}, narrow); }
-hipError_t launch_compute_d_digits(const NttPlan& p, fe* a, fe* b, size_t m, size_t batch, const QuotDigits& qd, hipStream_t s, const NttNarrow* narrow) {
+hipError_t launch_compute_h(const NttPlan& p, fe* a, fe* b, fe* c, size_t m, size_t batch, hipStream_t s, size_t ncols, const NttNarrow* narrow) { return launch_quotient(p, a, b, c, m, batch, s, ncols, 0, QuotDigits{nullptr, 0, 0}, narrow, 0); }
+hipError_t launch_compute_d(const NttPlan& p, fe* a, fe* b, size_t m, size_t batch, hipStream_t s, size_t ncols, const NttNarrow* narrow, size_t live) { return launch_quotient(p, a, b, nullptr, m, batch, s, ncols, 1, QuotDigits{nullptr, 0, 0}, narrow, live); }
+hipError_t launch_compute_d_digits(const NttPlan& p, fe* a, fe* b, size_t m, size_t batch, const QuotDigits& qd, hipStream_t s, const NttNarrow* narrow, size_t live) {
     if (!qd.digits || qd.c < 4 || qd.c > MSM_MAX_WINDOW || qd.nwin != msm_windows(qd.c)) return hipErrorInvalidValue;
-    return launch_quotient(p, a, b, nullptr, m, batch, s, 0, 2, qd, narrow);
+    return launch_quotient(p, a, b, nullptr, m, batch, s, 0, 2, qd, narrow, live);
 }
 namespace {
-hipError_t launch_quotient(const NttPlan& p, fe* a, fe* b, fe* c, size_t m, size_t batch, hipStream_t s, size_t ncols, int eval, const QuotDigits& qd, const NttNarrow* narrow) {
+hipError_t launch_quotient(const NttPlan& p, fe* a, fe* b, fe* c, size_t m, size_t batch, hipStream_t s, size_t ncols, int eval, const QuotDigits& qd, const NttNarrow* narrow, size_t live) {
     const int L = p.L, Lhi = (L + 1) / 2, Llo = L - Lhi;
     if (L < NTT_MIN_LOG2 || L > NTT_MAX_LOG2 || batch % P) return hipErrorInvalidValue;      // block sizes / launch bounds below assume this range
     const unsigned G = 1u << Lhi, Cn = 1u << Llo;
@@ -546,9 +550,12 @@ hipError_t launch_quotient(const NttPlan& p, fe* a, fe* b, fe* c, size_t m, size
     nr.plain = nr.plain && eval && nr.plane[0] && nr.plane[1] && p.tw_inv_plain && p.scale_mid_plain && Lhi >= 3 ? 1 : 0;
     NttPlan p2 = p; if (nr.plain) p2.scale_mid = p.scale_mid_plain;
     hipLaunchKernelGGL(k_ntt_dif_strided, dim3(Cn, pb, eval ? 2 : 3), dim3(G / 4 * P), lds_s, s, p, a, b, c, m, batch, nr);
-    hipLaunchKernelGGL(k_ntt_mid_contig, dim3(G, pb, 2), dim3(Cn / 4 * P), lds_c, s, p2, a, b, c, batch);
-    if (eval == 2) { hipLaunchKernelGGL(k_ntt_pointwise_strided<2>, dim3(Cn, pb, 1), dim3(G / 4 * P), lds_s, s, p, a, b, batch, qd); return hipGetLastError(); }
-    if (eval) { hipLaunchKernelGGL(k_ntt_pointwise_strided<1>, dim3(Cn, pb, 1), dim3(G / 4 * P), lds_s, s, p, a, b, batch, qd); return hipGetLastError(); }
+    // Evaluation form: the last kernel's tiles beyond the live table positions feed nothing that is read (kernels.hpp quot_live_tiles); the coefficient
+    // form runs every tile, its d goes through an inverse transform.
+    const unsigned tiles = eval ? quot_live_tiles(L, live) : Cn;
+    hipLaunchKernelGGL(k_ntt_mid_contig, dim3(G, pb, 2), dim3(Cn / 4 * P), lds_c, s, p2, a, b, c, batch, tiles);
+    if (eval == 2) { hipLaunchKernelGGL(k_ntt_pointwise_strided<2>, dim3(tiles, pb, 1), dim3(G / 4 * P), lds_s, s, p, a, b, batch, qd); return hipGetLastError(); }
+    if (eval) { hipLaunchKernelGGL(k_ntt_pointwise_strided<1>, dim3(tiles, pb, 1), dim3(G / 4 * P), lds_s, s, p, a, b, batch, qd); return hipGetLastError(); }
     hipLaunchKernelGGL(k_ntt_pointwise_strided<0>, dim3(Cn, pb, 1), dim3(G / 4 * P), lds_s, s, p, a, b, batch, qd);
     hipLaunchKernelGGL(k_ntt_final_contig, dim3(G, pb, 1), dim3(Cn / 4 * P), lds_c, s, p, a, c, batch);
     return hipGetLastError();

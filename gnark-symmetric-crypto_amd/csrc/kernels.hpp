@@ -145,17 +145,27 @@ constexpr int NTT_MIN_LOG2 = 15, NTT_MAX_LOG2 = 17;
 hipError_t launch_compute_h(const NttPlan& p, fe* a, fe* b, fe* c, size_t m, size_t batch, hipStream_t s, size_t ncols = 0, const NttNarrow* narrow = nullptr);
 // The quotient in EVALUATION form: only the four transforms of a and b; on return a[i] = A(zeta w^i) B(zeta w^i) * 2^261 mod r as a
 // canonical integer, natural order (b overwritten, c not touched): the scalars of the bases V_i of launch_quot_bases.
-hipError_t launch_compute_d(const NttPlan& p, fe* a, fe* b, size_t m, size_t batch, hipStream_t s, size_t ncols = 0, const NttNarrow* narrow = nullptr);
+// live > 0 (the fold): only the table positions 0 .. live-1 of the MSM set (quot_digit_index) are read afterwards.  The last kernel then
+// runs the quot_live_tiles(L, live) tiles that hold them and the second kernel stores only what those tiles load: a (and the digit words) of every
+// other position are NOT written and hold leftovers.  0: every position.
+hipError_t launch_compute_d(const NttPlan& p, fe* a, fe* b, size_t m, size_t batch, hipStream_t s, size_t ncols = 0, const NttNarrow* narrow = nullptr, size_t live = 0);
 // The same, but the last kernel recodes d itself: it writes the signed c-bit digits of the windowed MSM (launch_msm_win's format, see
 // launch_msm_recode) instead of d — no scalar vector in memory, no recoding pass.  A thread of that kernel holds d at four indices, which
 // become four consecutive bases: table position t of the MSM set belongs to the index quot_digit_index(L, t) (the engine lays the bases
 // V out in that order).  Whole batches only (ncols = 0).
 struct QuotDigits { uint4* digits; int c, nwin; };
-hipError_t launch_compute_d_digits(const NttPlan& p, fe* a, fe* b, size_t m, size_t batch, const QuotDigits& qd, hipStream_t s, const NttNarrow* narrow = nullptr);
+hipError_t launch_compute_d_digits(const NttPlan& p, fe* a, fe* b, size_t m, size_t batch, const QuotDigits& qd, hipStream_t s, const NttNarrow* narrow = nullptr, size_t live = 0);
 inline uint32_t quot_digit_index(int L, uint32_t t) {
     const int Lhi = (L + 1) / 2, Llo = L - Lhi; const uint32_t quarter = (1u << Lhi) / 4;
     const uint32_t kq = t & 3, m = t >> 2, u4 = m % quarter, g = m / quarter;
     return ((u4 + kq * quarter) << Llo) + g;
+}
+// The order is tile-major in the last kernel's own tiles: workgroup g of that kernel holds exactly the table positions [g G, (g + 1) G), G = 2^ceil(L/2)
+// (tests/test_quot_live_tiles_host.py).  Positions 0 .. live-1 therefore need the first ceil(live / G) of its 2^floor(L/2) tiles; live = 0 stands for all.
+inline uint32_t quot_live_tiles(int L, size_t live) {
+    const int Lhi = (L + 1) / 2, Llo = L - Lhi; const size_t G = (size_t)1 << Lhi, all = (size_t)1 << Llo;
+    const size_t tiles = live ? (live + G - 1) / G : all;
+    return (uint32_t)(tiles < 1 ? 1 : tiles > all ? all : tiles);
 }
 // InitAlgorithm: the key's quotient bases in evaluation form (k_quot_bases.hip).  zfile: the n - 1 points of pk.G1.Z as stored
 // (bit-reversed order), zstatus[i] = 2 for a point at infinity; n = 2^L.  mode 0: out[i] = U_i = (1/2n) sum_k w^(-ik) Z_k (scalars: the
