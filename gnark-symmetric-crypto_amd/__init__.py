@@ -20,7 +20,7 @@ CHACHA20, AES_128, AES_256 = 0, 1, 2                       # prove_impl.go:15-19
 ALGORITHM_NAMES = {0: "chacha20", 1: "aes-128-ctr", 2: "aes-256-ctr"}   # prove_impl.go:21-25
 
 EXPORTS = ["enforce_binding", "InitAlgorithm", "Free", "Prove", "ProveBatch", "gsc_prove_raw", "gsc_setup",
-           "gsc_set_deterministic_randomness", "gsc_debug_prove", "gsc_debug_vector", "gsc_describe", "gsc_last_stage_ms", "gsc_last_dominant_kernel", "gsc_last_kernel_clock", "gsc_debug_field_ops", "gsc_debug_limb_ops", "gsc_debug_curve_ops", "gsc_debug_tower_ops", "gsc_debug_compute_h", "gsc_debug_compute_d", "gsc_debug_z_sum", "gsc_debug_quot_fold_dft", "gsc_debug_secret_residue", "gsc_debug_clock_trace", "gsc_debug_glv_split",
+           "gsc_set_deterministic_randomness", "gsc_debug_prove", "gsc_debug_vector", "gsc_describe", "gsc_last_stage_ms", "gsc_last_dominant_kernel", "gsc_last_kernel_clock", "gsc_debug_field_ops", "gsc_debug_limb_ops", "gsc_debug_curve_ops", "gsc_debug_tower_ops", "gsc_debug_compute_h", "gsc_debug_compute_d", "gsc_debug_z_sum", "gsc_debug_quot_fold_dft", "gsc_debug_secret_residue", "gsc_debug_secret_scan", "gsc_debug_wipe", "gsc_debug_clock_trace", "gsc_debug_glv_split",
            "gsc_verify_init", "gsc_verify_raw", "VerifyBatch", "gsc_debug_pairing",
            "gsc_verify_raw_batched", "gsc_verify_all", "VerifyAll", "gsc_debug_verify_randomizers",
            "gsc_verify_json", "gsc_verify_last_path", "gsc_debug_verify_path", "gsc_debug_pairing_few",
@@ -248,6 +248,45 @@ def debug_secret_residue(algorithm_id: int) -> int:
     lib().gsc_debug_secret_residue.restype = C.c_longlong
     lib().gsc_debug_secret_residue.argtypes = [C.c_ubyte]
     return int(lib().gsc_debug_secret_residue(algorithm_id))
+
+
+def debug_secret_scan(algorithm_id: int):
+    """TEST HOOK: (bytes off the idle image over every secret region of every lane, {"lane<i>.<name>": bytes} of the regions that are not clean,
+    {"registered": bytes, "allocated": bytes, "public": [names]}); the total is -1 with the hooks disabled / on error."""
+    buf = C.create_string_buffer(16384)
+    lib().gsc_debug_secret_scan.restype = C.c_longlong
+    lib().gsc_debug_secret_scan.argtypes = [C.c_ubyte, C.c_char_p, C.c_size_t]
+    total = int(lib().gsc_debug_secret_scan(algorithm_id, buf, 16384))
+    dirty, info = {}, {}
+    for word in buf.value.decode().split():
+        k, v = word.split("=", 1)
+        if k.startswith("lane"):
+            dirty[k] = int(v)
+        else:
+            info[k] = v.split(",") if k == "public" else int(v)
+    return total, dirty, info
+
+
+def debug_wipe(nbytes: int, fill: int, descs, cls: bytes = b"", windows=(), want_buffer: bool = True):
+    """TEST HOOK: k_wipe on a device buffer of nbytes bytes filled with `fill`.  descs / windows: (offset, rows, pitch, width[, image]) tuples.
+    Returns (the buffer afterwards as bytes or None, [bytes off the idle image per window] by k_scan_idle, device ms of the wipe); raises on error."""
+    def pack(items):
+        flat = []
+        for it in items:
+            it = tuple(it)
+            flat += list(it) + [0] * (5 - len(it))
+        return (C.c_uint64 * max(1, len(flat)))(*flat)
+    descs, windows = list(descs), list(windows)
+    out = (C.c_ubyte * nbytes)() if want_buffer else None
+    counts = (C.c_uint64 * max(1, len(windows)))()
+    ms = C.c_float(0)
+    f = lib().gsc_debug_wipe
+    f.restype = C.c_int
+    f.argtypes = [C.c_uint64, C.c_int, C.c_void_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_float)]
+    rc = f(nbytes, fill, pack(descs), len(descs), cls if cls else None, len(cls), out, pack(windows), len(windows), counts, C.byref(ms))
+    if rc != 0:
+        raise RuntimeError("gsc_debug_wipe failed")
+    return (bytes(out) if want_buffer else None), [int(counts[i]) for i in range(len(windows))], float(ms.value)
 
 
 def debug_clock_trace(n: int, interval_us: int):

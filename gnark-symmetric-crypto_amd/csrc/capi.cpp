@@ -515,6 +515,21 @@ long long gsc_debug_secret_residue(GoUint8 algorithmID) {
     Algorithm* a = lookup(algorithmID); if (!a) return -1;
     try { return (long long)a->debug_secret_residue(); } catch (const std::exception& e) { fprintf(stderr, "gsc_debug_secret_residue: %s\n", e.what()); return -1; }
 }
+long long gsc_debug_secret_scan(GoUint8 algorithmID, char* out, size_t cap) {
+    if (hooks_refused("gsc_debug_secret_scan") || algorithmID > 2) return -1;
+    Algorithm* a = lookup(algorithmID); if (!a) return -1;
+    try {
+        std::string report;
+        const long long total = (long long)a->debug_secret_scan(report);
+        if (out && cap) { const size_t n = report.size() < cap - 1 ? report.size() : cap - 1; memcpy(out, report.data(), n); out[n] = 0; }
+        return total;
+    } catch (const std::exception& e) { fprintf(stderr, "gsc_debug_secret_scan: %s\n", e.what()); return -1; }
+}
+int gsc_debug_wipe(uint64_t bytes, int fill, const uint64_t* desc, size_t ndesc, const uint8_t* cls, size_t ncls, uint8_t* buf_out, const uint64_t* win, size_t nwin, uint64_t* counts, float* ms) {
+    if (hooks_refused("gsc_debug_wipe") || (ndesc && !desc) || (nwin && (!win || !counts)) || (ncls && !cls) || ndesc > 4096 || nwin > 4096) return -1;
+    try { const float t = debug_wipe(config_from_env().device, bytes, fill, desc, ndesc, cls, ncls, buf_out, win, nwin, counts); if (ms) *ms = t; return 0; }
+    catch (const std::exception& e) { fprintf(stderr, "gsc_debug_wipe: %s\n", e.what()); return -1; }
+}
 long long gsc_debug_compute_d(GoUint8 algorithmID, const uint8_t* ab_be, size_t m, uint8_t* d_out, size_t cap) {
     if (hooks_refused("gsc_debug_compute_d") || algorithmID > 2) return -1;
     Algorithm* a = lookup(algorithmID); if (!a) return -1;

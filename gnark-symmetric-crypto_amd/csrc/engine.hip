@@ -63,7 +63,7 @@ EngineConfig config_from_env() {
     if (c.small_witness < 0 || c.small_witness > 2 || (c.small_witness == 2 && !test_hooks_enabled())) throw std::runtime_error("GSC_SMALL_WITNESS must be 0 or 1");
     if (c.few_workgroups < 0 || c.few_workgroups > 256) throw std::runtime_error("GSC_FEW_WGS must be in [0, 256]");
     c.trace_host = getenv("GSC_TRACE_HOST") != nullptr;
-    if (test_hooks_enabled()) { c.solver_trace = getenv("GSC_SOLVER_TRACE") != nullptr; c.few_test_abort = getenv("GSC_FEW_TEST_ABORT") != nullptr; c.keep_secrets = getenv("GSC_KEEP_SECRETS") != nullptr; c.z_exp_entry_bits = env_int("GSC_Z_EXP_ENTRY_BITS", 0); }
+    if (test_hooks_enabled()) { c.solver_trace = getenv("GSC_SOLVER_TRACE") != nullptr; c.few_test_abort = getenv("GSC_FEW_TEST_ABORT") != nullptr; c.keep_secrets = getenv("GSC_KEEP_SECRETS") != nullptr; c.wipe_full = env_int("GSC_WIPE", 1) != 0; c.fail_after_stage = env_int("GSC_FAIL_AFTER_STAGE", 0); c.wipe_grid = env_int("GSC_WIPE_GRID", 0); if (c.wipe_grid < 0 || c.wipe_grid > 65536) throw std::runtime_error("GSC_WIPE_GRID must be in [0, 65536]"); c.z_exp_entry_bits = env_int("GSC_Z_EXP_ENTRY_BITS", 0); }
     if (c.max_batch < 64) c.max_batch = 64;
     c.max_batch = (c.max_batch + 63) / 64 * 64;
     if ((c.window_z && (c.window_z < 4 || c.window_z > MSM_MAX_WINDOW)) || (c.window_w && (c.window_w < 4 || c.window_w > 16))) throw std::runtime_error("GSC_WINDOW_Z must be in [4,17], GSC_WINDOW_W in [4,16]");
@@ -172,6 +172,45 @@ void debug_quot_fold_dft(int device, int L, uint32_t m, const uint32_t* perm, co
     if (m > 1) { HIP_CHECK(hipMemcpy(v2_be, d_out.p + 64 * (size_t)m, 64 * (size_t)(m - 1), hipMemcpyDeviceToHost)); HIP_CHECK(hipMemcpy(v2_inf, d_flags.p + m, m - 1, hipMemcpyDeviceToHost)); }
 }
 
+float debug_wipe(int device, uint64_t bytes, int fill, const uint64_t* desc, size_t ndesc, const uint8_t* cls, size_t ncls, uint8_t* out, const uint64_t* win, size_t nwin, uint64_t* counts) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) throw std::runtime_error("no HIP device available");
+    if (!bytes || bytes > ((uint64_t)1 << 36)) throw std::runtime_error("gsc_debug_wipe: buffer size out of range");
+    // every descriptor inside the buffer (no overflow: each factor is bounded first), image descriptors only with a class array
+    auto checked = [&](const uint64_t* d, uint8_t* base, const uint8_t* d_cls) {
+        const uint64_t off = d[0], rows = d[1], pitch = d[2], width = d[3];
+        if (off > bytes || rows > bytes || pitch > bytes || width > bytes) throw std::runtime_error("gsc_debug_wipe: descriptor outside the buffer");
+        if (rows && width) {
+            if (rows > 1 && pitch < width) throw std::runtime_error("gsc_debug_wipe: rows overlap");
+            const unsigned __int128 end = (unsigned __int128)off + (unsigned __int128)(rows - 1) * pitch + width;
+            if (end > bytes) throw std::runtime_error("gsc_debug_wipe: descriptor outside the buffer");
+        }
+        if (d[4] && (!d_cls || !ncls)) throw std::runtime_error("gsc_debug_wipe: plane image without row classes");
+        return WipeDesc{base + off, rows, pitch, width, d[4] ? d_cls : nullptr, d[4] ? (uint64_t)ncls : 0};
+    };
+    HIP_CHECK(hipSetDevice(device));
+    DevBuf<uint8_t> buf(bytes), d_cls(ncls ? ncls : 1); DevBuf<unsigned long long> d_cnt(nwin ? nwin : 1);
+    if (ncls) HIP_CHECK(hipMemcpy(d_cls.p, cls, ncls, hipMemcpyHostToDevice));
+    std::vector<WipeDesc> ds, ws;
+    for (size_t i = 0; i < ndesc; i++) ds.push_back(checked(desc + 5 * i, buf.p, d_cls.p));
+    for (size_t i = 0; i < nwin; i++) ws.push_back(checked(win + 5 * i, buf.p, d_cls.p));
+    HIP_CHECK(hipMemset(buf.p, fill, bytes));
+    HIP_CHECK(hipMemset(d_cnt.p, 0, d_cnt.bytes()));
+    HIP_CHECK(hipDeviceSynchronize());
+    hipEvent_t e0, e1; HIP_CHECK(hipEventCreate(&e0)); HIP_CHECK(hipEventCreate(&e1));
+    struct Ev { hipEvent_t a, b; ~Ev() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } ev{e0, e1};
+    HIP_CHECK(hipEventRecord(e0, nullptr));
+    launch_wipe(ds.data(), ds.size(), 0, nullptr);
+    HIP_CHECK(hipEventRecord(e1, nullptr));
+    for (size_t i = 0; i < nwin; i++) launch_scan_idle(ws[i], d_cnt.p + i, nullptr);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipDeviceSynchronize());
+    float ms = 0; HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+    if (out) HIP_CHECK(hipMemcpy(out, buf.p, bytes, hipMemcpyDeviceToHost));
+    if (nwin) { std::vector<unsigned long long> h(nwin); HIP_CHECK(hipMemcpy(h.data(), d_cnt.p, nwin * 8, hipMemcpyDeviceToHost)); for (size_t i = 0; i < nwin; i++) counts[i] = h[i]; }
+    return ms;
+}
+
 void debug_clock_trace(int device, uint32_t n, uint32_t interval_us, unsigned long long* out) {
     HIP_CHECK(hipSetDevice(device));
     hipStream_t st; HIP_CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
@@ -229,6 +268,7 @@ std::string Algorithm::describe() const {
     if (impl_->quotient_eval) out += impl_->mZ.digit_bases ? " Zlive=" + std::to_string(impl_->mZ.nwide) + " Zfold=" + impl_->fold_route : " Zfold=off(" + impl_->fold_why + ")";
     if (impl_->quotient_eval) out += " Qtiles=" + std::to_string(quot_live_tiles(impl_->L, impl_->quot_live)) + "/" + std::to_string(1u << (impl_->L - (impl_->L + 1) / 2));      // tiles the last quotient kernel runs
     out += impl_->small.ok ? " witness=small-integer(" + std::to_string(impl_->small.n_levels) + " chained levels, fallbacks " + std::to_string(impl_->small_fallbacks.load()) + ")" : " witness=generic" + (impl_->small.why.empty() ? std::string() : "(" + impl_->small.why + ")");
+    out += impl_->cfg.keep_secrets ? " wipe=off" : impl_->cfg.wipe_full ? " wipe=full" : " wipe=inputs";
     out += " served(calls/statements)=";
     const auto sv = picker_->served();
     for (size_t i = 0; i < sv.size(); i++) out += (i ? "," : "") + std::to_string(sv[i].calls) + "/" + std::to_string(sv[i].statements);
@@ -244,13 +284,14 @@ static void debug_quotient(AlgorithmImpl& a, const char* who, const uint8_t* mat
     struct Hold { AlgorithmImpl& a; size_t i; ~Hold() { a.release_lane(i); } } hold{a, a.acquire_lane(0)};
     AlgorithmImpl::Lane& ln = *a.lanes[0];
     const size_t B = 64, cnt = m * B;
-    DevBuf<uint8_t> d_be(mats * cnt * 32 + 32);
+    DevBuf<uint8_t> d_be(mats * cnt * 32 + 32, true);
     d_be.upload(mats_be, mats * cnt * 32, ln.stream);
     fe* const dst[3] = {ln.d_A.p, ln.d_B.p, ln.d_C.p};
     for (size_t k = 0; k < mats; k++) launch_fr_from_be(d_be.p + k * cnt * 32, dst[k], cnt, ln.stream);
     NttPlan plan{a.L, a.tw_fwd.p, a.tw_inv.p, a.scale_mid.p, a.scale_out.p, a.dom.p + 5, a.qr.p};
     HIP_CHECK(quot(plan, ln, B));
     if (out) HIP_CHECK(hipMemcpyAsync(out, ln.d_A.p, a.domain_n * B * 32, hipMemcpyDeviceToHost, ln.stream));
+    if (!a.cfg.keep_secrets && a.cfg.wipe_full) a.wipe_whole(ln, ln.stream);      // the hook's vectors are a caller's data like any other
     HIP_CHECK(hipStreamSynchronize(ln.stream));
 }
 void Algorithm::debug_compute_h(const uint8_t* abc_be, size_t m, uint8_t* h_out) {
@@ -319,6 +360,14 @@ static void prove_on_replica(AlgorithmImpl& a, const ProofRequest* reqs, size_t 
     if (err) std::rethrow_exception(err);
 }
 size_t Algorithm::debug_secret_residue() { size_t n = 0; for (auto& i : impls_) n += i->secret_residue(); return n; }
+size_t Algorithm::debug_secret_scan(std::string& report) {
+    size_t n = 0, registered = 0, allocated = 0, lane_base = 0;
+    for (auto& i : impls_) { n += i->secret_scan(lane_base, report, registered, allocated); lane_base += i->lanes.size(); }
+    report += "registered=" + std::to_string(registered) + " allocated=" + std::to_string(allocated) + " public=";
+    bool first = true;
+    for (int r = 0; r < WR_COUNT; r++) if (wipe_region_public(r)) { report += (first ? "" : ",") + std::string(wipe_region_name(r)); first = false; }
+    return n;
+}
 void Algorithm::forget_thread_stat() const { if (t_call_owner == this) t_call_owner = nullptr; }
 void Algorithm::prove_batch(const ProofRequest* reqs, size_t n, ProofResult* results, DebugVectors* debug_first, bool whole) {
     if (!n) return;

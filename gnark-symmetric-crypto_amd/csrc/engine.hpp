@@ -72,6 +72,10 @@ struct EngineConfig {
     bool solver_trace = false;   // GSC_SOLVER_TRACE: per-level clock stamps of the witness kernels
     int z_exp_entry_bits = 0;    // GSC_Z_EXP_ENTRY_BITS (test hooks; WRONG proofs, timing only): the Z kernel's gathers are confined to the first 2^bits entries of every row
     bool keep_secrets = false;   // GSC_KEEP_SECRETS: skip the end-of-call wipe of key wires / randomness in device memory (shows that the residue check sees them)
+    bool wipe_full = true;       // GSC_WIPE (test hooks only): 0 = only what the wipe of the rounds before 14 cleared (inputs, randomness, key wires), for A/B timing; otherwise every
+                                 // key-derived buffer of the lane is back to its idle image when the call leaves (wipe_plan.hpp)
+    int wipe_grid = 0;           // GSC_WIPE_GRID (test hooks only): workgroups of the wipe launched beside the Z sum (0 = WIPE_GRID_BESIDE), for the measurements of DESIGN.md §5
+    int fail_after_stage = 0;    // GSC_FAIL_AFTER_STAGE=k (test hooks only): prove_chunk throws on the host after enqueuing stage k (1 upload, 2 witness, 3 early sums, 4 quotient, 5 msms); nothing faults on the device
     bool few_test_abort = false; // GSC_FEW_TEST_ABORT: the resident witness kernel's barrier never fills (exercises the give-up path)
 };
 // Every knob is read HERE, once per InitAlgorithm / gsc_setup call — never on the proving path (getenv there would race with a
@@ -123,6 +127,9 @@ class Algorithm {
     void debug_z_sum(const uint8_t* abc_be, size_t m, uint8_t* out, uint8_t* flags);
     // TEST HOOK: bytes of secrets (key wires, r, s, input records, masks) still non-zero in device memory, all replicas and lanes; 0 after any call
     size_t debug_secret_residue();
+    // TEST HOOK: bytes off the idle image in EVERY secret region of every lane over its whole allocation, all replicas (after draining the lanes);
+    // report: "lane<i>.<name>=<bytes>" for the regions that are not clean, then "registered=<bytes> allocated=<bytes> public=<names>"
+    size_t debug_secret_scan(std::string& report);
   private:
     std::vector<std::unique_ptr<AlgorithmImpl>> impls_;      // one per device
     std::unique_ptr<class ReplicaPicker> picker_;            // dispatch.hpp: least-loaded replica for calls that are not split
@@ -134,6 +141,10 @@ class Algorithm {
 // big-endian X | Y each, *_inf[i] = 1: the point at infinity.  Out: U' (m) and V' (m - 1) in the same format.  Throws on HIP errors and on a perm that is none.
 void debug_quot_fold_dft(int device, int L, uint32_t m, const uint32_t* perm, const uint8_t* u_be, const uint8_t* u_inf, const uint8_t* v_be, const uint8_t* v_inf,
                          uint8_t* u2_be, uint8_t* u2_inf, uint8_t* v2_be, uint8_t* v2_inf);
+// TEST HOOK: k_wipe / k_scan_idle on a buffer of `bytes` bytes filled with `fill`, no key, no algorithm.  desc: ndesc x {offset, rows, pitch, width, image}
+// (image != 0: the plane image by cls[row % ncls]); they must lie inside the buffer.  out (may be null): the buffer afterwards.  win: nwin x {offset, rows, pitch,
+// width, image} scan windows, counts[i] = bytes of window i off its idle image.  Returns the milliseconds the wipe launch took on the device.
+float debug_wipe(int device, uint64_t bytes, int fill, const uint64_t* desc, size_t ndesc, const uint8_t* cls, size_t ncls, uint8_t* out, const uint64_t* win, size_t nwin, uint64_t* counts);
 // TEST HOOK: samples the device's shader clock for n x interval_us microseconds beside whatever else runs (a resident one-wave kernel on a
 // stream of its own); out: n pairs {100 MHz clock, shader clock}.  Blocks until the samples are in.
 void debug_clock_trace(int device, uint32_t n, uint32_t interval_us, unsigned long long* out);

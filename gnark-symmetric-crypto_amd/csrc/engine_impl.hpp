@@ -8,6 +8,7 @@
 #include "formats.hpp"
 #include "kernels.hpp"
 #include "wit_small.hpp"
+#include "wipe_plan.hpp"
 #include <atomic>
 #include <chrono>
 #include <cstring>
@@ -22,14 +23,20 @@ namespace gsc {
 
 #define HIP_CHECK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) throw std::runtime_error(std::string("HIP error: ") + hipGetErrorString(e_) + " at " #expr); } while (0)
 
+// alloc_lane points this at the lane's byte count for its duration: every DevBuf the thread allocates meanwhile is counted, so that the lane's
+// region table (wipe_plan.hpp) can be held against what was really allocated
+inline thread_local size_t* devbuf_tally = nullptr;
+
 template <class T>
 struct DevBuf {
     T* p = nullptr; size_t n = 0;
+    bool secret = false;      // a temporary that holds a call's data: zeroed before it is freed, also when an exception unwinds (like setup_dev.hip's Buf)
     DevBuf() = default;
-    explicit DevBuf(size_t count) { alloc(count); }
+    explicit DevBuf(size_t count, bool is_secret = false) : secret(is_secret) { alloc(count); }
     DevBuf(const DevBuf&) = delete; DevBuf& operator=(const DevBuf&) = delete;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    void alloc(size_t count) { if (p) { (void)hipFree(p); p = nullptr; } n = count; if (count) HIP_CHECK(hipMalloc((void**)&p, count * sizeof(T))); }
+    ~DevBuf() { release(); }
+    void release() { if (p) { if (secret) { (void)hipMemset(p, 0, n * sizeof(T)); (void)hipDeviceSynchronize(); } (void)hipFree(p); p = nullptr; } }
+    void alloc(size_t count) { release(); n = count; if (count) { HIP_CHECK(hipMalloc((void**)&p, count * sizeof(T))); if (devbuf_tally) *devbuf_tally += count * sizeof(T); } }
     void upload(const T* src, size_t count, hipStream_t s) { HIP_CHECK(hipMemcpyAsync(p, src, count * sizeof(T), hipMemcpyHostToDevice, s)); }
     size_t bytes() const { return n * sizeof(T); }
 };
@@ -147,6 +154,7 @@ class AlgorithmImpl {
         hipStream_t stream = nullptr, side = nullptr, side2 = nullptr;      // side: the assembly's scalar multiplications, beside the MSMs; side2: the B2 sum of a latency-path call
         hipEvent_t ev_ab = nullptr, ev_fs = nullptr, ev_b2 = nullptr, ev_s2 = nullptr;
         hipEvent_t ev_ws = nullptr;     // the wire-set MSMs of a call whose quotient runs beside them are through (stage accounting)
+        hipEvent_t ev_wa = nullptr, ev_wa_done = nullptr;      // phase A of the wipe may start (main stream) / is through (third stream)
         hipEvent_t ev_few = nullptr;    // completion of this lane's latest k_solver_few launch (FewSolverChain)
         hipEvent_t ev[7] = {};          // 0..4 stage boundaries, 5..6 bracket the dominant kernel (Z-table MSM gather-accumulate)
         float stage_ms[4] = {0, 0, 0, 0}; float msm_z_kernel_ms = 0; size_t last_batch = 0;
@@ -176,8 +184,16 @@ class AlgorithmImpl {
         DevBuf<G1Xyzz> d_sj1[NSETS], d_flat1[NSETS]; DevBuf<G2Xyzz> d_sj2, d_flat2;
         MsmHornerJobs pending1{}, pending2{};
         DevBuf<uint8_t> d_gok;                                                    // bit-group verdicts [group][wave of 64 proofs]
+        // The region table (wipe_plan.hpp): every device allocation above, by name, as alloc_lane made it; allocated = what the DevBufs really took
+        struct Region { int region; uint8_t* p; size_t bytes; };
+        std::vector<Region> regions; size_t allocated = 0;
+        template <class T> void reg(int region, DevBuf<T>& b) { if (b.p) regions.push_back(Region{region, reinterpret_cast<uint8_t*>(b.p), b.bytes()}); }
+        // what the scratch buffers need for a chunk of 64 (k + 1) columns, in bytes (alloc_lane sized them by the largest; a chunk writes no further than its own)
+        struct ScratchNeed { size_t part1a = 0, part1b = 0, part2a = 0, part2b = 0, digits = 0, digits_w = 0, gok = 0, sj1[8] = {0, 0, 0, 0, 0, 0, 0, 0}, sj2 = 0; };
+        std::vector<ScratchNeed> need_at;
+        bool wipe_a_pending = false;    // phase A of the chunk being proved is enqueued: phase B waits for it
         ~Lane() { if (ev_few) { for (int d = 0; d < 64; d++) { FewSolverChain& c = few_solver_chain(d); std::lock_guard<std::mutex> lk(c.m); if (c.last == ev_few) c.last = nullptr; } (void)hipEventDestroy(ev_few); }
-                  for (auto& e : ev) if (e) (void)hipEventDestroy(e); if (ev_ws) (void)hipEventDestroy(ev_ws); if (ev_ab) (void)hipEventDestroy(ev_ab); if (ev_fs) (void)hipEventDestroy(ev_fs); if (ev_b2) (void)hipEventDestroy(ev_b2); if (ev_s2) (void)hipEventDestroy(ev_s2); if (side2) (void)hipStreamDestroy(side2); if (side) (void)hipStreamDestroy(side); if (stream) (void)hipStreamDestroy(stream); }
+                  for (auto& e : ev) if (e) (void)hipEventDestroy(e); if (ev_ws) (void)hipEventDestroy(ev_ws); if (ev_wa) (void)hipEventDestroy(ev_wa); if (ev_wa_done) (void)hipEventDestroy(ev_wa_done); if (ev_ab) (void)hipEventDestroy(ev_ab); if (ev_fs) (void)hipEventDestroy(ev_fs); if (ev_b2) (void)hipEventDestroy(ev_b2); if (ev_s2) (void)hipEventDestroy(ev_s2); if (side2) (void)hipStreamDestroy(side2); if (side) (void)hipStreamDestroy(side); if (stream) (void)hipStreamDestroy(stream); }
     };
     std::vector<std::unique_ptr<Lane>> lanes;
     size_t cap = 0;                     // proofs per full lane = the largest chunk
@@ -274,9 +290,21 @@ class AlgorithmImpl {
     // The statement's secrets must not outlive the call in device memory (the witness of these circuits IS a cipher key): enqueued behind a
     // chunk's last kernel, clears the key wires (32-byte rows and byte plane), the rows of r, s, -rs, the raw input records, the prover
     // randomness, its endomorphism split and the commitment mask.  (The reference leaves all of this to Go's garbage collector.)
+    // That is the wipe of the rounds before 14 (the secret inputs only), kept for A/B timing (GSC_WIPE=0, test hooks only).  The full wipe (cfg.wipe_full, the default) brings EVERY secret
+    // region of the lane (wipe_plan.hpp) back to its idle image: phase A beside the Z sum on the lane's low-priority stream, phase B behind the
+    // assembly; a latency call: one launch behind the assembly.
     void wipe_secrets(Lane& ln, size_t B, bool small_call);
+    WipePlan plan_wipe(const Lane& ln, const Chunk& ck) const;
+    void run_wipe(Lane& ln, const std::vector<WipeItem>& items, hipStream_t s, unsigned max_blocks);
+    void wipe_phase_a(Lane& ln, const Chunk& ck);      // from stage_msms, at the trigger
+    void wipe_phase_b(Lane& ln, const Chunk& ck);      // from stage_assembly
+    void wipe_whole(Lane& ln, hipStream_t s);          // every secret region over its whole allocation (alloc_lane; a call that leaves by an exception)
+    // test knob GSC_FAIL_AFTER_STAGE: a host exception behind stage k's enqueue
+    void fail_after(int stage) const { if (cfg.fail_after_stage == stage) throw std::runtime_error("GSC_FAIL_AFTER_STAGE=" + std::to_string(stage) + ": test failure injected"); }
     // TEST HOOK: non-zero bytes left in those areas over all lanes (after draining their streams)
     size_t secret_residue();
+    // TEST HOOK: bytes off the idle image in every secret region of every lane, over the whole allocations (k_scan_idle); report: see gsc_debug_secret_scan
+    size_t secret_scan(size_t lane_base, std::string& report, size_t& registered, size_t& allocated);
 
     // allow_few_solver / allow_small = false: the retries after the resident solver gave up / a small-integer prediction failed
     void prove_chunk(Lane& ln, const ProofRequest* reqs, size_t n, ProofResult* results, DebugVectors* dbg, bool allow_few_solver = true, bool allow_small = true);

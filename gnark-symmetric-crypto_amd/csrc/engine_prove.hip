@@ -137,6 +137,95 @@ void AlgorithmImpl::wipe_secrets(Lane& ln, size_t B, bool small_call) {
     if (small_call) HIP_CHECK(hipMemset2DAsync(ln.d_W8.p + n_public * 64, (size_t)small.rows_per_group * 64, 0, n_secret * 64, B / 64, ln.stream));
 }
 
+WipePlan AlgorithmImpl::plan_wipe(const Lane& ln, const Chunk& ck) const {
+    WipeSizes z;
+    z.B = ck.B; z.n = ck.n; z.n_wires = n_wires; z.n_constraints = n_constraints; z.domain_n = domain_n; z.rows_per_group = small.ok ? small.rows_per_group : 0;
+    z.fe_bytes = sizeof(fe); z.xyzz1_bytes = sizeof(G1Xyzz); z.xyzz2_bytes = sizeof(G2Xyzz);
+    const Lane::ScratchNeed& nd = ln.need_at.at(ck.B / 64 - 1);
+    z.part1a = nd.part1a; z.part1b = nd.part1b; z.part2a = nd.part2a; z.part2b = nd.part2b; z.digits = nd.digits; z.digits_w = nd.digits_w; z.gok = nd.gok; z.sj2 = nd.sj2;
+    for (int k = 0; k < Lane::NSETS; k++) z.sj1[k] = nd.sj1[k];
+    std::vector<WipeRegionInfo> table;
+    for (const Lane::Region& r : ln.regions) table.push_back(WipeRegionInfo{r.region, r.bytes});
+    return wipe_plan(ck.rt, route_facts(), z, table);
+}
+
+void AlgorithmImpl::run_wipe(Lane& ln, const std::vector<WipeItem>& items, hipStream_t s, unsigned max_blocks) {
+    std::vector<WipeDesc> ds;
+    for (const WipeItem& it : items) {
+        const Lane::Region* reg = nullptr;
+        for (const Lane::Region& r : ln.regions) if (r.region == it.region) reg = &r;
+        if (!reg || wipe_region_public(it.region)) throw std::runtime_error("internal: wipe of a region the lane does not hold");
+        // inside the allocation, whatever the plan said (a kernel that writes out of bounds is worse than a region left dirty, which the scan would show)
+        if (!it.rows || !it.width) continue;
+        if (it.offset > reg->bytes || it.width > reg->bytes || it.pitch > reg->bytes || it.rows > reg->bytes || it.offset + (it.rows - 1) * it.pitch + it.width > reg->bytes || (it.rows > 1 && it.pitch < it.width))
+            throw std::runtime_error(std::string("internal: wipe descriptor outside region ") + wipe_region_name(it.region));
+        const uint8_t* cls = nullptr;
+        if (it.image) cls = it.region == WR_A8 ? ws_cls_a.p : it.region == WR_B8 ? ws_cls_b.p : it.region == WR_C8 ? ws_cls_c.p : nullptr;
+        if (it.image && !cls) throw std::runtime_error("internal: plane image of a region that is no plane");
+        ds.push_back(WipeDesc{reg->p + it.offset, it.rows, it.pitch, it.width, cls, it.image ? it.image_period : 0});
+    }
+    launch_wipe(ds.data(), ds.size(), max_blocks, s);
+    HIP_CHECK(hipGetLastError());
+}
+
+// Phase A: from here on the call only reads the Z sum's digits and the tables (and, with a commitment, the committed wires once more: the plan keeps
+// those back).  The Z kernel is VALU-bound and leaves HBM idle, so the fill goes beside it on the lane's low-priority stream with a
+// bounded grid; phase B waits for it.
+void AlgorithmImpl::wipe_phase_a(Lane& ln, const Chunk& ck) {
+    ln.wipe_a_pending = false;
+    if (cfg.keep_secrets || !cfg.wipe_full || ck.rt.latency) return;
+    const WipePlan p = plan_wipe(ln, ck);
+    if (p.a.empty()) return;
+    HIP_CHECK(hipEventRecord(ln.ev_wa, ln.stream));
+    HIP_CHECK(hipStreamWaitEvent(ln.side2, ln.ev_wa, 0));
+    run_wipe(ln, p.a, ln.side2, cfg.wipe_grid ? (unsigned)cfg.wipe_grid : WIPE_GRID_BESIDE);
+    HIP_CHECK(hipEventRecord(ln.ev_wa_done, ln.side2));
+    ln.wipe_a_pending = true;
+}
+
+void AlgorithmImpl::wipe_phase_b(Lane& ln, const Chunk& ck) {
+    if (cfg.keep_secrets) return;
+    if (!cfg.wipe_full) return wipe_secrets(ln, ck.B, ck.rt.small);
+    const WipePlan p = plan_wipe(ln, ck);
+    if (ln.wipe_a_pending) { HIP_CHECK(hipStreamWaitEvent(ln.stream, ln.ev_wa_done, 0)); ln.wipe_a_pending = false; }
+    else if (!p.a.empty()) throw std::runtime_error("internal: phase A of the wipe was not enqueued");
+    run_wipe(ln, p.b, ln.stream, 0);
+}
+
+void AlgorithmImpl::wipe_whole(Lane& ln, hipStream_t s) {
+    std::vector<WipeRegionInfo> table;
+    for (const Lane::Region& r : ln.regions) table.push_back(WipeRegionInfo{r.region, r.bytes});
+    run_wipe(ln, wipe_plan_whole(table, n_constraints), s, 0);
+}
+
+size_t AlgorithmImpl::secret_scan(size_t lane_base, std::string& report, size_t& registered, size_t& allocated) {
+    HIP_CHECK(hipSetDevice(cfg.device));
+    size_t total = 0;
+    for (size_t li = 0; li < lanes.size(); li++) {
+        Lane& ln = *lanes[li];
+        HIP_CHECK(hipStreamSynchronize(ln.side)); HIP_CHECK(hipStreamSynchronize(ln.side2)); HIP_CHECK(hipStreamSynchronize(ln.stream));
+        std::vector<WipeRegionInfo> table;
+        for (const Lane::Region& r : ln.regions) { table.push_back(WipeRegionInfo{r.region, r.bytes}); registered += r.bytes; }
+        allocated += ln.allocated;
+        const std::vector<WipeItem> items = wipe_plan_whole(table, n_constraints);
+        DevBuf<unsigned long long> d_cnt(items.size() + 1);
+        HIP_CHECK(hipMemsetAsync(d_cnt.p, 0, d_cnt.bytes(), ln.stream));
+        for (size_t k = 0; k < items.size(); k++) {
+            const WipeItem& it = items[k];
+            const Lane::Region* reg = nullptr;
+            for (const Lane::Region& r : ln.regions) if (r.region == it.region) reg = &r;
+            const uint8_t* cls = !it.image ? nullptr : it.region == WR_A8 ? ws_cls_a.p : it.region == WR_B8 ? ws_cls_b.p : ws_cls_c.p;
+            launch_scan_idle(WipeDesc{reg->p + it.offset, it.rows, it.pitch, it.width, cls, it.image ? it.image_period : 0}, d_cnt.p + k, ln.stream);
+        }
+        HIP_CHECK(hipGetLastError());
+        std::vector<unsigned long long> h(items.size() + 1);
+        HIP_CHECK(hipMemcpyAsync(h.data(), d_cnt.p, h.size() * 8, hipMemcpyDeviceToHost, ln.stream));
+        HIP_CHECK(hipStreamSynchronize(ln.stream));
+        for (size_t k = 0; k < items.size(); k++) if (h[k]) { total += h[k]; report += "lane" + std::to_string(lane_base + li) + "." + wipe_region_name(items[k].region) + "=" + std::to_string(h[k]) + " "; }
+    }
+    return total;
+}
+
 size_t AlgorithmImpl::secret_residue() {
     HIP_CHECK(hipSetDevice(cfg.device));
     size_t left = 0;
@@ -252,7 +341,7 @@ void AlgorithmImpl::stage_witness(Lane& ln, const Chunk& ck) {
     HIP_CHECK(hipMemsetAsync(ln.d_status.p, 0xFF, B * 4, ln.stream));
     SolverArgs sa{prog.p, sched.p, 0, n_levels, coeff.p, coeff_inv.p, lookup_coeff.p, ln.d_W.p, ln.d_A.p, ln.d_B.p, ln.d_C.p, B, ln.d_status.p,
                   has_commitment ? ln.d_mask.p : nullptr, has_commitment ? ln.d_commit.p : nullptr, has_div, 0u, nullptr};
-    DevBuf<unsigned long long> d_trace;
+    DevBuf<unsigned long long> d_trace; d_trace.secret = true;      // (when a level ran says something about its values)
     if (cfg.solver_trace) {
         std::vector<unsigned long long> init(16 * ((size_t)n_levels + 1), 0ull);
         if (!ck.rt.resident_wanted) for (uint32_t l = 0; l < n_levels; l++) init[16 * l] = ~0ull;
@@ -318,7 +407,7 @@ void AlgorithmImpl::stage_quotient(Lane& ln, const Chunk& ck) {
     hipStream_t qs = rt.overlap_q ? ln.side2 : ln.stream;
     if (rt.eval) {
         if (dbg) {      // the debug vector is h itself: the coefficient-form kernels on copies (they overwrite their inputs)
-            DevBuf<fe> ta(domain_n * B), tb(domain_n * B), tc(domain_n * B);
+            DevBuf<fe> ta(domain_n * B, true), tb(domain_n * B, true), tc(domain_n * B, true);
             HIP_CHECK(hipMemcpyAsync(ta.p, ln.d_A.p, n_constraints * B * sizeof(fe), hipMemcpyDeviceToDevice, ln.stream));
             HIP_CHECK(hipMemcpyAsync(tb.p, ln.d_B.p, n_constraints * B * sizeof(fe), hipMemcpyDeviceToDevice, ln.stream));
             HIP_CHECK(hipMemcpyAsync(tc.p, ln.d_C.p, n_constraints * B * sizeof(fe), hipMemcpyDeviceToDevice, ln.stream));
@@ -360,6 +449,7 @@ void AlgorithmImpl::stage_msms(Lane& ln, const Chunk& ck) {
         run_msm_g1(ln, ck, mC, ln.d_C.p, 1, ln.d_sumC.p);
     }
     if (rt.overlap_q) { HIP_CHECK(hipEventRecord(ln.ev_ws, ln.stream)); HIP_CHECK(hipStreamWaitEvent(ln.stream, ln.ev[2], 0)); }      // the wire sets are through; wait for d and its digits
+    wipe_phase_a(ln, ck);      // the witness, a, b, c and the wire sets' digits have had their last reader
     run_msm_g1(ln, ck, rt.use_zfew ? mZfew : mZ, ln.d_A.p, 0, ln.d_sumZ.p, !rt.latency, false, rt.z_digits_ready);
     if (has_commitment) run_msm_g1(ln, ck, mPedSigma, ln.d_W.p, 1, ln.d_sumPok.p);      // proof of knowledge of the commitment: same scalars over sigma * Basis
     flush_horner<G1Aff>(ln.pending1, B, ln.stream);                                           // K, Z, PedSigma: one launch
@@ -382,7 +472,7 @@ void AlgorithmImpl::stage_assembly(Lane& ln, Chunk& ck) {
     memset(ln.h_words.p, 0, ln.h_words.bytes());      // the small result words (Lane::h_fsync, h_wsflag, h_clk)
     if (rt.resident) HIP_CHECK(hipMemcpyAsync(ln.h_fsync(), ln.d_fsync.p, 8, hipMemcpyDeviceToHost, ln.stream));
     if (rt.small) HIP_CHECK(hipMemcpyAsync(&ln.h_wsflag(), ln.d_wsflag.p, 4, hipMemcpyDeviceToHost, ln.stream));
-    wipe_secrets(ln, B, rt.small);      // behind the last kernel of the chunk, inside the wait below
+    wipe_phase_b(ln, ck);      // behind the last kernel of the chunk, inside the wait below
     if (!rt.latency) { HIP_CHECK(hipMemcpyAsync(ln.h_clk(), ln.d_clk.p, (cfg.trace_host ? 44 : 32) * 8, hipMemcpyDeviceToHost, ln.stream)); HIP_CHECK(hipMemsetAsync(ln.d_clk.p, 0, 32 * 8, ln.stream)); }
     ck.t_enqueued = std::chrono::steady_clock::now();
     HIP_CHECK(hipStreamSynchronize(ln.stream));
@@ -429,7 +519,19 @@ void AlgorithmImpl::prove_chunk(Lane& ln, const ProofRequest* reqs, size_t n, Pr
     // staging is the lane's pinned memory; what it holds of the statements' secrets (keys, randomness, masks) is cleared when the call leaves, however it leaves
     struct StagingWiper { Lane& l; size_t B; ~StagingWiper() { explicit_bzero(l.h_in.p, 176 * B); explicit_bzero(l.h_rs.p, 64 * B); explicit_bzero(l.h_glv.p, l.h_glv.bytes()); if (l.h_mask.p) explicit_bzero(l.h_mask.p, 32 * B); } } wipe_staging{ln, B};
     // a call that leaves by an exception must not leave work behind on the lane's other streams (the next call would share its buffers with it)
-    struct Drain { Lane& l; int live = std::uncaught_exceptions(); ~Drain() { if (std::uncaught_exceptions() > live) { (void)hipStreamSynchronize(l.side); (void)hipStreamSynchronize(l.side2); (void)hipStreamSynchronize(l.stream); } } } drain{ln};
+    // ... nor anything key-derived in its buffers: how far the call got is not tracked, so every secret region is cleared over its whole allocation
+    struct Drain {
+        AlgorithmImpl& a; Lane& l; int live = std::uncaught_exceptions();
+        void sync() { (void)hipStreamSynchronize(l.side); (void)hipStreamSynchronize(l.side2); (void)hipStreamSynchronize(l.stream); }
+        ~Drain() {
+            if (std::uncaught_exceptions() <= live) return;
+            sync();
+            l.wipe_a_pending = false; l.pending1.n = 0; l.pending2.n = 0;
+            if (a.cfg.keep_secrets || !a.cfg.wipe_full) return;
+            try { a.wipe_whole(l, l.stream); } catch (const std::exception& e) { fprintf(stderr, "libprove: could not clear the lane after a failed call: %s\n", e.what()); }
+            sync();
+        }
+    } drain{*this, ln};
     // the route, decided here and nowhere else (chunk_route.hpp)
     RouteCall call{dbg != nullptr, allow_few_solver, allow_small, false};
     ck.rt = chunk_route(n, cfg, route_facts(), call);
@@ -439,11 +541,11 @@ void AlgorithmImpl::prove_chunk(Lane& ln, const ProofRequest* reqs, size_t n, Pr
         if (k) { call.skip_resident = true; ck.rt = chunk_route(n, cfg, route_facts(), call); }
     }
     ln.small_active = ck.rt.small;
-    stage_upload(ln, ck);
-    stage_witness(ln, ck);
-    stage_early_sums(ln, ck);
-    stage_quotient(ln, ck);
-    stage_msms(ln, ck);
+    stage_upload(ln, ck); fail_after(1);
+    stage_witness(ln, ck); fail_after(2);
+    stage_early_sums(ln, ck); fail_after(3);
+    stage_quotient(ln, ck); fail_after(4);
+    stage_msms(ln, ck); fail_after(5);
     stage_assembly(ln, ck);
     if (ln.h_fsync()[1]) {      // the resident solver gave up (its workgroups never became resident together: another process's kernel on this device)
         static std::atomic<bool> warned{false};

@@ -174,8 +174,9 @@ void AlgorithmImpl::calibrate() {
         q.r[0] = 3; q.s[0] = 5; q.mask[0] = 7;
     }
     std::vector<uint8_t> h_in(176 * B), h_rs(64 * B); pack_inputs(reqs.data(), B, B, h_in.data(), h_rs.data());
-    DevBuf<uint8_t> d_inputs(h_in.size()), d_rs(h_rs.size()), d_mask_in(32 * B); DevBuf<uint32_t> d_status(B);
-    DevBuf<fe> d_W((n_wires + 4) * B), d_A(n_constraints * B), d_B(n_constraints * B), d_C(n_constraints * B), d_mask(B), d_commit(B);
+    // (the calibration witness is a made-up key, but its buffers are cleared before they are freed like any call's)
+    DevBuf<uint8_t> d_inputs(h_in.size(), true), d_rs(h_rs.size(), true), d_mask_in(32 * B, true); DevBuf<uint32_t> d_status(B);
+    DevBuf<fe> d_W((n_wires + 4) * B, true), d_A(n_constraints * B, true), d_B(n_constraints * B, true), d_C(n_constraints * B, true), d_mask(B, true), d_commit(B, true);
     d_inputs.upload(h_in.data(), h_in.size(), stream); d_rs.upload(h_rs.data(), h_rs.size(), stream);
     if (cipher == CHACHA20) launch_assign_chacha(d_inputs.p, d_W.p, B, stream);
     else launch_assign_aes(d_inputs.p, cipher == AES_128 ? 16 : 32, d_W.p, B, stream);
@@ -567,6 +568,8 @@ void AlgorithmImpl::init_key(const R1csFile& cs, const PkFile& key) {
 
 void AlgorithmImpl::alloc_lane(Lane& ln, size_t B) {
     ln.cap = B;
+    // every device allocation from here to the end of the function is counted (DevBuf::alloc) and must be in the region table at the end
+    struct Tally { Tally(size_t* t) { devbuf_tally = t; } ~Tally() { devbuf_tally = nullptr; } } tally{&ln.allocated};
     // HIP spreads a process's streams over GPU_MAX_HW_QUEUES (4) hardware queues PER PRIORITY LEVEL, round-robin: with ten streams of one
     // priority (a full lane and two small ones, three streams each) a lane's side stream lands in the queue of another lane's main stream and
     // that lane's kernels wait behind a 3 ms chain of sixteen waves.  The three roles therefore take the three priority levels — three pools
@@ -585,23 +588,24 @@ void AlgorithmImpl::alloc_lane(Lane& ln, size_t B) {
     } else { HIP_CHECK(hipStreamCreate(&ln.stream)); HIP_CHECK(hipStreamCreate(&ln.side)); HIP_CHECK(hipStreamCreate(&ln.side2)); }
     for (auto& e : ln.ev) HIP_CHECK(hipEventCreate(&e));
     HIP_CHECK(hipEventCreate(&ln.ev_ws));
+    HIP_CHECK(hipEventCreateWithFlags(&ln.ev_wa, hipEventDisableTiming)); HIP_CHECK(hipEventCreateWithFlags(&ln.ev_wa_done, hipEventDisableTiming));
     HIP_CHECK(hipEventCreateWithFlags(&ln.ev_few, hipEventDisableTiming));
     HIP_CHECK(hipEventCreateWithFlags(&ln.ev_ab, hipEventDisableTiming)); HIP_CHECK(hipEventCreateWithFlags(&ln.ev_fs, hipEventDisableTiming)); HIP_CHECK(hipEventCreateWithFlags(&ln.ev_b2, hipEventDisableTiming)); HIP_CHECK(hipEventCreateWithFlags(&ln.ev_s2, hipEventDisableTiming));
     ln.h_in.alloc(176 * B); ln.h_rs.alloc(64 * B); ln.h_glv.alloc(2 * MSM_FEW_PROOFS); ln.h_out.alloc(256 * B); ln.h_flags.alloc((B + 3) / 4 * 4); ln.h_status.alloc(B); ln.h_words.alloc(56);
     ln.d_clk.alloc(48); HIP_CHECK(hipMemsetAsync(ln.d_clk.p, 0, 48 * 8, ln.stream));      // [0, 32): the Z kernel's eight samples; [32, 44): the three transform kernels
     ln.d_inputs.alloc(176 * B); ln.d_rs.alloc(64 * B); ln.d_out.alloc(256 * B); ln.d_flags.alloc((B + 3) / 4 * 4); ln.d_status.alloc(B); ln.d_fsync.alloc(2); ln.d_glv.alloc(2 * MSM_FEW_PROOFS);
-    // (the buffers that will hold secrets start out clean, so that "nothing of a call is left" can be checked from the first call on)
-    HIP_CHECK(hipMemsetAsync(ln.d_inputs.p, 0, ln.d_inputs.bytes(), ln.stream)); HIP_CHECK(hipMemsetAsync(ln.d_rs.p, 0, ln.d_rs.bytes(), ln.stream)); HIP_CHECK(hipMemsetAsync(ln.d_glv.p, 0, ln.d_glv.bytes(), ln.stream));
+    // (every buffer that will hold key-derived values starts out at its idle image — the wipe at the end of this function — so that "nothing of a call
+    // is left" can be checked from the first call on)
+    HIP_CHECK(hipMemsetAsync(ln.d_out.p, 0, ln.d_out.bytes(), ln.stream)); HIP_CHECK(hipMemsetAsync(ln.d_flags.p, 0, ln.d_flags.bytes(), ln.stream));
+    HIP_CHECK(hipMemsetAsync(ln.d_status.p, 0, ln.d_status.bytes(), ln.stream)); HIP_CHECK(hipMemsetAsync(ln.d_fsync.p, 0, ln.d_fsync.bytes(), ln.stream));
     ln.d_W.alloc((n_wires + 4) * B); ln.d_A.alloc(domain_n * B); ln.d_B.alloc(domain_n * B); ln.d_C.alloc((domain_n + 1) * B);      // (+ one row that stays zero: the padding slots of mC)
     // calls with a handful of statements (k_solver_few) write their own columns only: the others must always hold field elements
-    // (zero, later whatever an earlier call left there) because the transforms and MSMs run over whole 64-column batches
-    HIP_CHECK(hipMemsetAsync(ln.d_W.p, 0, ln.d_W.n * sizeof(fe), ln.stream)); HIP_CHECK(hipMemsetAsync(ln.d_A.p, 0, ln.d_A.n * sizeof(fe), ln.stream));
-    HIP_CHECK(hipMemsetAsync(ln.d_B.p, 0, ln.d_B.n * sizeof(fe), ln.stream)); HIP_CHECK(hipMemsetAsync(ln.d_C.p, 0, ln.d_C.n * sizeof(fe), ln.stream));
+    // (zero: every call leaves them so) because the transforms and MSMs run over whole 64-column batches
     if (small.ok) {      // byte planes of the small-integer witness path (values 0, 1, 0xFF)
         ln.d_W8.alloc((size_t)small.rows_per_group * B); ln.d_A8.alloc(n_constraints * B); ln.d_B8.alloc(n_constraints * B); ln.d_C8.alloc(n_constraints * B); ln.d_wsflag.alloc(1);
-        HIP_CHECK(hipMemsetAsync(ln.d_W8.p, 0, ln.d_W8.n, ln.stream)); HIP_CHECK(hipMemsetAsync(ln.d_A8.p, 0, ln.d_A8.n, ln.stream));
-        HIP_CHECK(hipMemsetAsync(ln.d_B8.p, 0, ln.d_B8.n, ln.stream)); HIP_CHECK(hipMemsetAsync(ln.d_C8.p, 0, ln.d_C8.n, ln.stream));
-        // rows predicted wide: their plane entries say "see the 32-byte element" for good (the rows kernel never writes them)
+        HIP_CHECK(hipMemsetAsync(ln.d_wsflag.p, 0, 4, ln.stream));
+        // rows predicted wide: their plane entries say "see the 32-byte element" for good (the rows kernel never writes them): the planes' idle image,
+        // restored by every wipe of a plane (k_wipe's plane image writes the same marks by the same row classes)
         launch_wit_mark_wide(ln.d_A8.p, n_constraints, n_constraints, ws_cls_a.p, B, ln.stream); launch_wit_mark_wide(ln.d_B8.p, n_constraints, n_constraints, ws_cls_b.p, B, ln.stream);
         launch_wit_mark_wide(ln.d_C8.p, n_constraints, n_constraints, ws_cls_c.p, B, ln.stream);
         HIP_CHECK(hipGetLastError());
@@ -623,12 +627,19 @@ void AlgorithmImpl::alloc_lane(Lane& ln, size_t B) {
         if (m.nwide) { const size_t bw = b * (size_t)m.nwin; part(m.nwide, msm_slices(m.nwide, (size_t)m.nwin, WIN_SLICE, b, per), bw); if (bw > sj) sj = bw; const size_t d = (size_t)m.nwin * (((m.digit_bases ? m.digit_bases : m.nwide) + 7) / 8) * b * msm_digit_words(m.c); if (d > dg) dg = d; }
     };
     MsmSet<G1Aff>* g1sets[Lane::NSETS] = {&mA, &mB1, &mK, &mZ, &mPed, &mPedSigma, &mZfew, &mC};
+    ln.need_at.clear();
     for (size_t b = 64; b <= B; b += 64) {
         for (int k = 0; k < Lane::NSETS; k++) if (g1sets[k] != &mZfew || b == 64) {      // the latency layout only serves 64-column batches
             if (fuse_z_digits && g1sets[k] == &mZ) { const size_t keep = dg; dg = 0; need(mZ, b, p1, p1b, sj1[k]); if (dg > dgz) dgz = dg; dg = keep; }      // Z's digits: a buffer of their own
             else need(*g1sets[k], b, p1, p1b, sj1[k]);
         }
         need(mB2, b, p2, p2b, sj2);
+        // the needs up to this batch size: what a chunk of b columns can have written (the wipe's extents, wipe_plan.hpp)
+        Lane::ScratchNeed nd;
+        nd.part1a = p1 * sizeof(G1Xyzz); nd.part1b = p1b * sizeof(G1Xyzz); nd.part2a = p2 * sizeof(G2Xyzz); nd.part2b = p2b * sizeof(G2Xyzz);
+        nd.digits = (fuse_z_digits ? dgz : dg) * sizeof(uint4); nd.digits_w = fuse_z_digits ? (dg ? dg : 1) * sizeof(uint4) : 0; nd.gok = gk ? gk : 1; nd.sj2 = (sj2 ? sj2 : 1) * sizeof(G2Xyzz);
+        for (int k = 0; k < Lane::NSETS; k++) nd.sj1[k] = (sj1[k] ? sj1[k] : 1) * sizeof(G1Xyzz);
+        ln.need_at.push_back(nd);
     }
     if (fuse_z_digits) { ln.d_digits_w.alloc(dg ? dg : 1); dg = dgz; }
     ln.d_part1a.alloc(p1); ln.d_part1b.alloc(p1b); ln.d_part2a.alloc(p2); ln.d_part2b.alloc(p2b);
@@ -652,7 +663,21 @@ void AlgorithmImpl::alloc_lane(Lane& ln, size_t B) {
     if (has_commitment) {
         ln.d_mask_in.alloc(32 * B); ln.d_mask.alloc(B); ln.d_commit.alloc(B); ln.d_cpts.alloc(128 * B); ln.d_sumD.alloc(B); ln.d_sumPok.alloc(B);
         ln.h_mask.alloc(32 * B); ln.h_cpts.alloc(128 * B);
-        HIP_CHECK(hipMemsetAsync(ln.d_mask_in.p, 0, ln.d_mask_in.bytes(), ln.stream)); HIP_CHECK(hipMemsetAsync(ln.d_mask.p, 0, ln.d_mask.bytes(), ln.stream));
+        HIP_CHECK(hipMemsetAsync(ln.d_cpts.p, 0, ln.d_cpts.bytes(), ln.stream));
     }
+    // The region table: every allocation above by name.  Public: results, verdicts, timing words (the closed list of wipe_plan.hpp); all else is secret.
+    ln.regions.clear();
+    ln.reg(WR_INPUTS, ln.d_inputs); ln.reg(WR_RS, ln.d_rs); ln.reg(WR_GLV, ln.d_glv); ln.reg(WR_MASK_IN, ln.d_mask_in); ln.reg(WR_MASK, ln.d_mask); ln.reg(WR_COMMIT, ln.d_commit);
+    ln.reg(WR_SUM_D, ln.d_sumD); ln.reg(WR_SUM_POK, ln.d_sumPok);
+    ln.reg(WR_W, ln.d_W); ln.reg(WR_A, ln.d_A); ln.reg(WR_B, ln.d_B); ln.reg(WR_C, ln.d_C); ln.reg(WR_W8, ln.d_W8); ln.reg(WR_A8, ln.d_A8); ln.reg(WR_B8, ln.d_B8); ln.reg(WR_C8, ln.d_C8);
+    ln.reg(WR_PART1A, ln.d_part1a); ln.reg(WR_PART1B, ln.d_part1b); ln.reg(WR_PART2A, ln.d_part2a); ln.reg(WR_PART2B, ln.d_part2b); ln.reg(WR_PART1C, ln.d_part1c); ln.reg(WR_PART1D, ln.d_part1d);
+    ln.reg(WR_DIGITS, ln.d_digits); ln.reg(WR_DIGITS_W, ln.d_digits_w); ln.reg(WR_DIGITS_S, ln.d_digits_s); ln.reg(WR_DIGITS_S2, ln.d_digits_s2);
+    ln.reg(WR_GOK, ln.d_gok); ln.reg(WR_GOK_S, ln.d_gok_s); ln.reg(WR_GOK_S2, ln.d_gok_s2);
+    for (int k = 0; k < Lane::NSETS; k++) { ln.reg(WR_SJ1 + k, ln.d_sj1[k]); ln.reg(WR_FLAT1 + k, ln.d_flat1[k]); }
+    ln.reg(WR_SJ2, ln.d_sj2); ln.reg(WR_FLAT2, ln.d_flat2);
+    ln.reg(WR_SUM_A, ln.d_sumA); ln.reg(WR_SUM_B1, ln.d_sumB1); ln.reg(WR_SUM_K, ln.d_sumK); ln.reg(WR_SUM_Z, ln.d_sumZ); ln.reg(WR_SUM_C, ln.d_sumC); ln.reg(WR_SUM_B2, ln.d_sumB2); ln.reg(WR_TMP, ln.d_tmp);
+    ln.reg(WR_OUT, ln.d_out); ln.reg(WR_FLAGS, ln.d_flags); ln.reg(WR_STATUS, ln.d_status); ln.reg(WR_CPTS, ln.d_cpts); ln.reg(WR_CLK, ln.d_clk); ln.reg(WR_FSYNC, ln.d_fsync); ln.reg(WR_WSFLAG, ln.d_wsflag);
+    wipe_whole(ln, ln.stream);      // every secret region to its idle image (the planes: the marks of the rows predicted wide)
+    HIP_CHECK(hipStreamSynchronize(ln.stream));
 }
 }  // namespace gsc

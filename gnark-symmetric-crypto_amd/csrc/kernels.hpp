@@ -131,6 +131,21 @@ constexpr int8_t WS_PLANE_WIDE = -128;
 // ternary inputs are then scalings of twiddles by integers in [-4, 4] instead of field products; the second kernel's scale table absorbs the change of
 // domain (NttPlan::scale_mid_plain).  Evaluation-form launches only (launch_compute_d*).
 struct NttNarrow { const int8_t* plane[3]; size_t crows; int plain = 0; };      // plane[(group * crows + row) * 64 + lane]
+
+// ---- clearing key-derived buffers (k_wipe.hip; what to clear and when: wipe_plan.hpp) ----
+// rows x width bytes at base, rows `pitch` bytes apart (a whole buffer: one row).  cls == nullptr: the image is zero.  Otherwise the region is a
+// byte plane and row i holds WS_PLANE_WIDE where cls[i % cls_period] != 0, else zero (launch_wit_mark_wide's rows).
+struct WipeDesc { uint8_t* base; uint64_t rows, pitch, width; const uint8_t* cls; uint64_t cls_period; };
+constexpr uint32_t WIPE_MAX_DESCS = 64;            // per launch (the list travels as a kernel argument); launch_wipe cuts longer lists
+constexpr uint64_t WIPE_UNIT_BYTES = 4096;         // one block-iteration: 256 lanes x one 16-byte store
+constexpr unsigned WIPE_GRID_DEFAULT = 2048, WIPE_GRID_SCAN = 4096;
+constexpr unsigned WIPE_GRID_BESIDE = 512;         // a wipe launched beside the Z sum: two workgroups per CU, eight of its wave slots
+struct WipeList { WipeDesc d[WIPE_MAX_DESCS]; uint64_t first[WIPE_MAX_DESCS + 1]; uint32_t n; };      // first[k]: the units before descriptor k
+// writes the idle image of every descriptor: at most max_blocks workgroups (0: WIPE_GRID_DEFAULT) walk the list with a grid stride.
+// The caller answers for the descriptors lying inside their buffers.
+void launch_wipe(const WipeDesc* descs, size_t n, unsigned max_blocks, hipStream_t s);
+// *counter += the bytes of the descriptor that differ from its idle image (one atomic add per workgroup that found any)
+void launch_scan_idle(const WipeDesc& desc, unsigned long long* counter, hipStream_t s);
 struct NttPlan { int L; const int32_t* tw_fwd; const int32_t* tw_inv; const fe* scale_mid; const fe* scale_out; const fe* half_c; const int32_t* qr;
                  unsigned long long* clk = nullptr;
                  const int32_t* tw_inv_plain = nullptr; const fe* scale_mid_plain = nullptr; };      // (NttNarrow::plain) tw_inv as canonical integers; scale_mid x 2^256      // clk (diagnostics): kernel k's middle workgroup stamps {100 MHz clock, shader clock} at its start and end into clk[4 k ..]   // tw_*, qr: 12 int32 per entry (limbs)

@@ -142,6 +142,20 @@ extern long long gsc_debug_compute_d(GoUint8 algorithmID, const uint8_t *ab_be, 
 // TEST HOOK: the evaluation-form quotient sum (sum c_i U_i + sum d_i V_i) of 64 columns through the batch kernels and whatever sets InitAlgorithm built.
 // abc_be: a, b, c = a b row by row, [m][64] canonical big-endian values; out: 64 x 64 B big-endian X | Y; flags[i] = 1: the point at infinity.  0 on success.
 extern int gsc_debug_z_sum(GoUint8 algorithmID, const uint8_t *abc_be, size_t m, uint8_t *out, uint8_t *flags);
+/* TEST HOOK: every key-derived device buffer of the algorithm against its idle image.  Synchronises every lane, then counts on the device, over the whole
+ * allocation of every region classed secret (every device allocation of a lane but the public ones: results, verdicts, timing words), the bytes that differ from
+ * the idle image: zero, or 0x80 in the rows of the byte planes that are marked wide for good.  out (cap bytes, NUL-terminated): "lane<i>.<name>=<bytes> " for every
+ * region that is not clean, then "registered=<bytes> allocated=<bytes> public=<comma-separated names>" (registered: the bytes of the lanes' region tables; allocated:
+ * the bytes their allocations took: equal unless a buffer is missing from the table).  Returns the total — 0 after InitAlgorithm and after any call, however it left —
+ * or -1 on error / hooks disabled. */
+extern long long gsc_debug_secret_scan(GoUint8 algorithmID, char *out, size_t cap);
+/* TEST HOOK: the kernels behind that, k_wipe and k_scan_idle, on a buffer of their own (needs a device, no key).  Allocates `bytes` bytes of device memory, fills them
+ * with the byte `fill`, and applies ndesc descriptors {offset, rows, pitch, width, image} (five uint64 each: `rows` rows of `width` bytes, `pitch` apart, from `offset`;
+ * image != 0: instead of zero, row i gets 0x80 where cls[i mod ncls] != 0) with ONE launch sequence of k_wipe.  buf_out (may be NULL; `bytes` bytes): the buffer
+ * afterwards.  win: nwin scan windows in the same five-word format, counts[i] = bytes of window i that differ from its idle image (k_scan_idle), so that large
+ * buffers need no host copy.  *ms (may be NULL): device time of the k_wipe launch.  Descriptors and windows must lie inside the buffer.  0 on success, -1 on error. */
+extern int gsc_debug_wipe(uint64_t bytes, int fill, const uint64_t *desc, size_t ndesc, const uint8_t *cls, size_t ncls, uint8_t *buf_out,
+                          const uint64_t *win, size_t nwin, uint64_t *counts, float *ms);
 // TEST HOOK: the fold of the Z bases that the domain's zero padding makes redundant, by three group transforms, on caller-supplied bases (needs a device, no
 // InitAlgorithm).  n = 2^L, 2 <= L <= 17, 2 <= m <= n; perm: n entries, table position -> coset index (NULL: the identity); u_be (m points) and v_be (n points,
 // table order): 64 B big-endian X | Y each, *_inf[i] = 1: the point at infinity.  Out: U' (m) and V' (m - 1) in the same format.  0 on success, -1 on error.
