@@ -20,7 +20,7 @@ CHACHA20, AES_128, AES_256 = 0, 1, 2                       # prove_impl.go:15-19
 ALGORITHM_NAMES = {0: "chacha20", 1: "aes-128-ctr", 2: "aes-256-ctr"}   # prove_impl.go:21-25
 
 EXPORTS = ["enforce_binding", "InitAlgorithm", "Free", "Prove", "ProveBatch", "gsc_prove_raw", "gsc_setup",
-           "gsc_set_deterministic_randomness", "gsc_debug_prove", "gsc_debug_vector", "gsc_describe", "gsc_last_stage_ms", "gsc_last_dominant_kernel", "gsc_last_kernel_clock", "gsc_debug_field_ops", "gsc_debug_limb_ops", "gsc_debug_curve_ops", "gsc_debug_tower_ops", "gsc_debug_compute_h", "gsc_debug_compute_d", "gsc_debug_z_sum", "gsc_debug_quot_fold_dft", "gsc_debug_secret_residue", "gsc_debug_secret_scan", "gsc_debug_wipe", "gsc_debug_clock_trace", "gsc_debug_glv_split",
+           "gsc_set_deterministic_randomness", "gsc_debug_prove", "gsc_debug_vector", "gsc_describe", "gsc_last_stage_ms", "gsc_last_dominant_kernel", "gsc_last_kernel_clock", "gsc_debug_field_ops", "gsc_debug_limb_ops", "gsc_debug_curve_ops", "gsc_debug_decode_points", "gsc_debug_tower_ops", "gsc_debug_compute_h", "gsc_debug_compute_d", "gsc_debug_z_sum", "gsc_debug_quot_fold_dft", "gsc_debug_secret_residue", "gsc_debug_secret_scan", "gsc_debug_wipe", "gsc_debug_clock_trace", "gsc_debug_glv_split",
            "gsc_verify_init", "gsc_verify_raw", "VerifyBatch", "gsc_debug_pairing",
            "gsc_verify_raw_batched", "gsc_verify_all", "VerifyAll", "gsc_debug_verify_randomizers",
            "gsc_verify_json", "gsc_verify_last_path", "gsc_debug_verify_path", "gsc_debug_pairing_few",
@@ -353,6 +353,20 @@ def debug_curve_ops(group: int, op: int, pts: bytes, inf: bytes, lam: bytes, n: 
     if lib().gsc_debug_curve_ops(group, op, pts, inf, lam, n, k, out, flags):
         raise RuntimeError("gsc_debug_curve_ops failed")
     return out.raw, flags.raw
+
+
+def debug_decode_points(group: int, encoded: bytes, n: int):
+    """TEST HOOK: the key-point decode of InitAlgorithm (host walk + kernels; G2 with the subgroup test) on n encoded elements, each
+    compressed or raw -> (canonical big-endian X | Y bytes, 64 per G1 and 128 per G2 point, status bytes: 0 ok, 1 refused, 2 infinity).
+    Raises RuntimeError when the library returns -1 (a slice that ends inside an element, bytes left over, hooks off)."""
+    L = lib()
+    L.gsc_debug_decode_points.restype = C.c_int
+    L.gsc_debug_decode_points.argtypes = [C.c_int, C.c_char_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]
+    w = 64 if group == 0 else 128
+    out, st = C.create_string_buffer(max(1, w * n)), C.create_string_buffer(max(1, n))
+    if L.gsc_debug_decode_points(group, bytes(encoded), len(encoded), n, out, st):
+        raise RuntimeError("gsc_debug_decode_points failed")
+    return out.raw[:w * n], st.raw[:n]
 
 
 def tower_words(path: int, op: int):

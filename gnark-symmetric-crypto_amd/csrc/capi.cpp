@@ -462,6 +462,12 @@ int gsc_debug_curve_ops(int group, int op, const uint8_t* pts, const uint8_t* in
     catch (const std::exception& e) { printf("%s\n", e.what()); return -1; }
 }
 
+int gsc_debug_decode_points(int group, const uint8_t* bytes, size_t len, size_t n, uint8_t* out_xy, uint8_t* status) {
+    if (hooks_refused("gsc_debug_decode_points") || (len && !bytes) || (n && (!out_xy || !status))) return -1;
+    try { debug_decode_points(config_from_env().device, group, bytes, len, n, out_xy, status); return 0; }
+    catch (const std::exception& e) { printf("%s\n", e.what()); return -1; }
+}
+
 int gsc_debug_tower_ops(int path, int op, const int32_t* in, size_t n, int32_t* out, uint8_t* flags) {
     if (hooks_refused("gsc_debug_tower_ops") || (n && (!in || !out || !flags))) return -1;
     try {

@@ -123,6 +123,35 @@ void debug_curve_ops(int device, int group, int op, const uint8_t* pts, const ui
     HIP_CHECK(hipMemcpy(flags, dflags.p, n, hipMemcpyDeviceToHost));
 }
 
+void debug_decode_points(int device, int group, const uint8_t* bytes, size_t len, size_t n, uint8_t* out_xy, uint8_t* status) {
+    if (group < 0 || group > 1 || n > (1u << 20)) throw std::runtime_error("gsc_debug_decode_points: no such group / too many points");
+    const size_t cb = group == 0 ? 32 : 64, w = cb / 32;
+    KeyPoints pts;
+    const size_t used = walk_points(bytes, len, n, cb, pts.x, pts.y, "points");      // the walk parse_pk makes over every slice
+    if (used != len) throw std::runtime_error("points: trailing bytes");
+    if (!n) return;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) throw std::runtime_error("no HIP device available");
+    HIP_CHECK(hipSetDevice(device));
+    DevBuf<fe> dpts(2 * w * n), dcanon(2 * w * n);
+    const std::vector<uint8_t> st = group == 0 ? decode_g1_points(pts, reinterpret_cast<G1Aff*>(dpts.p), nullptr) : decode_g2_points(pts, reinterpret_cast<G2Aff*>(dpts.p), nullptr);
+    launch_fp_from_mont(dpts.p, dcanon.p, 2 * w * n, nullptr);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipDeviceSynchronize());
+    std::vector<uint8_t> le(64 * w * n);
+    HIP_CHECK(hipMemcpy(le.data(), dcanon.p, le.size(), hipMemcpyDeviceToHost));
+    // device order: G1 x, y; G2 x.a0, x.a1, y.a0, y.a1 (little-endian limbs) -> X | Y big-endian, in G2 A1 before A0 as in the encodings
+    for (size_t i = 0; i < n; i++) {
+        status[i] = st[i];
+        for (size_t c = 0; c < 2 * w; c++) {
+            const size_t src = w == 1 ? c : (c ^ 1);
+            const uint8_t* v = le.data() + 32 * (2 * w * i + src);
+            uint8_t* o = out_xy + 32 * (2 * w * i + c);
+            for (int k = 0; k < 32; k++) o[k] = st[i] == 0 ? v[31 - k] : 0;
+        }
+    }
+}
+
 bool debug_tower_ops(int device, int path, int op, const int32_t* in, size_t n, int32_t* out, uint8_t* flags) {
     int iw, ow;
     if (!tower_ops_words(path, op, &iw, &ow)) return false;

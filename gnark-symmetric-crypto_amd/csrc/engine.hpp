@@ -154,6 +154,9 @@ void debug_field_ops(int device, int field, int op, const uint8_t* a, const uint
 // TEST HOOKS: gsc_debug_limb_ops / gsc_debug_curve_ops of include/libprove.h (host memory in and out); they throw like debug_field_ops.
 void debug_limb_ops(int device, int field, int op, const int32_t* a, const int32_t* b, const int32_t* c, const int32_t* d, int32_t* out, size_t n);
 void debug_curve_ops(int device, int group, int op, const uint8_t* pts, const uint8_t* inf, const uint8_t* lam, size_t n, size_t k, uint8_t* out, uint8_t* flags);
+// TEST HOOK: gsc_debug_decode_points of include/libprove.h: the walk of formats.hpp and the key-point decode kernels InitAlgorithm runs
+// (engine_impl.hpp decode_g1_points / decode_g2_points) on caller bytes; throws like debug_field_ops and on a malformed slice.
+void debug_decode_points(int device, int group, const uint8_t* bytes, size_t len, size_t n, uint8_t* out_xy, uint8_t* status);
 // TEST HOOK: gsc_debug_tower_ops of include/libprove.h (host memory in and out).  false, before anything touches the device, for a path / op
 // that does not exist; throws like debug_field_ops.
 bool debug_tower_ops(int device, int path, int op, const int32_t* in, size_t n, int32_t* out, uint8_t* flags);

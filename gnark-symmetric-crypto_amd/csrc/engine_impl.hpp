@@ -52,6 +52,19 @@ struct PinnedBuf {
     size_t bytes() const { return n * sizeof(T); }
 };
 
+// Encoded points of a key as the walk of formats.hpp leaves them: x at a fixed stride (32 B in G1, 64 B in G2, flag bits in place) and,
+// when some element is raw, y at the same stride (the Y bytes of the raw elements; empty for a compressed-only set).
+struct KeyPoints {
+    std::vector<uint8_t> x, y;
+    KeyPoints() = default;
+    KeyPoints(const std::vector<uint8_t>& x_, const std::vector<uint8_t>& y_ = {}) : x(x_), y(y_) {}
+};
+// The production decode of a key's points, on `stream` (synchronised before returning): the compressed elements by k_decompress_*, the raw
+// ones by k_decode_raw_* (only launched when there are any), and for G2 the subgroup test over every finite point.  out: device memory for
+// x.size() / stride points; returns one status byte per point (0 decoded, 1 refused, 2 the point at infinity).  No key, no engine needed.
+std::vector<uint8_t> decode_g1_points(const KeyPoints& pts, G1Aff* out, hipStream_t stream);
+std::vector<uint8_t> decode_g2_points(const KeyPoints& pts, G2Aff* out, hipStream_t stream);
+
 template <class AffT>
 struct MsmSet {                     // one fixed-base MSM of the proving key (kernels.hpp, "multi-scalar multiplication")
     size_t nbases = 0;              // bases of the key in this set
@@ -213,9 +226,10 @@ class AlgorithmImpl {
     // every wave of proofs and falls back to the digit tables, so a wrong prediction costs time, never correctness.
     void calibrate();
 
-    // decompress `raw` (count points of `sz` bytes) into out[offset...]; returns per-point status
-    std::vector<uint8_t> decompress_g1(const std::vector<uint8_t>& raw, G1Aff* out);
-    std::vector<uint8_t> decompress_g2(const std::vector<uint8_t>& raw, G2Aff* out);
+    // decode the points of `pts` (either encoding, element by element) into out[0 ...] on the init stream; returns per-point status
+    // (decode_g1_points / decode_g2_points below: G2 includes the subgroup test)
+    std::vector<uint8_t> decompress_g1(const KeyPoints& pts, G1Aff* out) { return decode_g1_points(pts, out, stream); }
+    std::vector<uint8_t> decompress_g2(const KeyPoints& pts, G2Aff* out) { return decode_g2_points(pts, out, stream); }
 
     static constexpr size_t EXPAND_MAX = 64;      // up to this many wide wires of a set are laid out as window octets of its flat part
     static constexpr int EXPAND_C = 15, NARROW_MAX_BITS = 14;
@@ -231,7 +245,7 @@ class AlgorithmImpl {
     template <class AffT, class XyzzT, class Decomp>
     // classes: the predicted class per scalar row (default: row_class, the wires); zero_row: a scalar row that is always zero (padding slots; default:
     // row n_wires + 3 of W); latency_layout: also build the (base, window) rows of the windowed part for calls with a handful of statements
-    void build_set(MsmSet<AffT>& set, const std::vector<uint8_t>& raw, size_t point_bytes, const std::vector<uint32_t>& rows, int c, const char* what, Decomp decomp, bool uniform, int expand_cv = 0,
+    void build_set(MsmSet<AffT>& set, const KeyPoints& raw, size_t point_bytes, const std::vector<uint32_t>& rows, int c, const char* what, Decomp decomp, bool uniform, int expand_cv = 0,
                    const std::vector<uint8_t>* classes = nullptr, uint32_t zero_row = 0xFFFFFFFFu, bool latency_layout = true);
     // group tables are built in chunks so that the projective scratch stays below ~2 GiB
     template <class AffT, class XyzzT>

@@ -31,6 +31,9 @@ AlgorithmImpl::AlgorithmImpl(Cipher c, const uint8_t* pk, size_t pk_len, const u
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) throw std::runtime_error("no HIP device available: the GPU prover has no CPU fallback");
     HIP_CHECK(hipSetDevice(cfg.device));
     HIP_CHECK(hipStreamCreate(&stream));
+    // a refused key (a point off the curve or outside the subgroup, a wrong circuit) throws out of this constructor: the members free their
+    // device memory as they unwind, and this gives the init stream back, so that a failed InitAlgorithm leaves nothing behind
+    struct StreamGuard { hipStream_t& s; bool armed = true; ~StreamGuard() { if (armed && s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); s = nullptr; } } } stream_guard{stream};
     { int cus = 0; if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, cfg.device) == hipSuccess && cus > 0) cu_count = cus; }
     const bool trace = cfg.trace_host;
     auto now = [] { return std::chrono::steady_clock::now(); };
@@ -70,6 +73,7 @@ AlgorithmImpl::AlgorithmImpl(Cipher c, const uint8_t* pk, size_t pk_len, const u
     cap = lane_cap;
     if (trace) fprintf(stderr, "InitAlgorithm(%d): %zu lane(s) of %zu proofs + %d of %zu, %.0f ms\n", (int)c, nl, lane_cap, cfg.small_lanes, small_cap, ms(t3, now()));
     HIP_CHECK(hipStreamSynchronize(stream));
+    stream_guard.armed = false;
 }
 
 std::unique_ptr<SolverProgram> AlgorithmImpl::init_program(const R1csFile& cs) {
@@ -207,26 +211,32 @@ void AlgorithmImpl::calibrate() {
     HIP_CHECK(hipStreamSynchronize(stream));
 }
 
-std::vector<uint8_t> AlgorithmImpl::decompress_g1(const std::vector<uint8_t>& raw, G1Aff* out) {
-    const size_t n = raw.size() / 32; std::vector<uint8_t> st(n);
+namespace {
+template <class AffT, size_t STRIDE, class Compressed, class Raw, class After>
+std::vector<uint8_t> decode_points(const KeyPoints& pts, AffT* out, hipStream_t stream, Compressed compressed, Raw raw, After after) {
+    const size_t n = pts.x.size() / STRIDE; std::vector<uint8_t> st(n);
     if (!n) return st;
-    DevBuf<uint8_t> d_raw(raw.size()), d_st(n);
-    d_raw.upload(raw.data(), raw.size(), stream);
-    launch_decompress_g1(d_raw.p, out, d_st.p, n, stream);
+    if (!pts.y.empty() && pts.y.size() != pts.x.size()) throw std::runtime_error("key points: the y bytes do not match the x bytes");
+    DevBuf<uint8_t> d_x(pts.x.size()), d_y(pts.y.size()), d_st(n);
+    d_x.upload(pts.x.data(), pts.x.size(), stream);
+    compressed(d_x.p, out, d_st.p, n, stream);
+    if (!pts.y.empty()) {      // raw elements (flag bits 00) take their Y from the companion bytes; the compressed ones keep what they have
+        d_y.upload(pts.y.data(), pts.y.size(), stream);
+        raw(d_x.p, d_y.p, out, d_st.p, n, stream);
+    }
+    after(out, d_st.p, n, stream);      // G2: the subgroup test over what decoded
+    HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipMemcpyAsync(st.data(), d_st.p, n, hipMemcpyDeviceToHost, stream));
     HIP_CHECK(hipStreamSynchronize(stream));
     return st;
 }
+}  // namespace
 
-std::vector<uint8_t> AlgorithmImpl::decompress_g2(const std::vector<uint8_t>& raw, G2Aff* out) {
-    const size_t n = raw.size() / 64; std::vector<uint8_t> st(n);
-    if (!n) return st;
-    DevBuf<uint8_t> d_raw(raw.size()), d_st(n);
-    d_raw.upload(raw.data(), raw.size(), stream);
-    launch_decompress_g2(d_raw.p, out, d_st.p, n, stream);
-    HIP_CHECK(hipMemcpyAsync(st.data(), d_st.p, n, hipMemcpyDeviceToHost, stream));
-    HIP_CHECK(hipStreamSynchronize(stream));
-    return st;
+std::vector<uint8_t> decode_g1_points(const KeyPoints& pts, G1Aff* out, hipStream_t stream) {
+    return decode_points<G1Aff, 32>(pts, out, stream, launch_decompress_g1, launch_decode_raw_g1, [](G1Aff*, uint8_t*, size_t, hipStream_t) {});
+}
+std::vector<uint8_t> decode_g2_points(const KeyPoints& pts, G2Aff* out, hipStream_t stream) {
+    return decode_points<G2Aff, 64>(pts, out, stream, launch_decompress_g2, launch_decode_raw_g2, launch_g2_subgroup);
 }
 
 template <class AffT, class XyzzT>
@@ -244,10 +254,10 @@ void AlgorithmImpl::build_rows(const AffT* bases, size_t n, const std::vector<ui
 }
 
 template <class AffT, class XyzzT, class Decomp>
-void AlgorithmImpl::build_set(MsmSet<AffT>& set, const std::vector<uint8_t>& raw, size_t point_bytes, const std::vector<uint32_t>& rows, int c, const char* what, Decomp decomp, bool uniform, int expand_cv,
+void AlgorithmImpl::build_set(MsmSet<AffT>& set, const KeyPoints& raw, size_t point_bytes, const std::vector<uint32_t>& rows, int c, const char* what, Decomp decomp, bool uniform, int expand_cv,
                               const std::vector<uint8_t>* classes, uint32_t zero_row, bool latency_layout) {
     const std::vector<uint8_t>& cls = classes ? *classes : row_class;
-    const size_t n = raw.size() / point_bytes;
+    const size_t n = raw.x.size() / point_bytes;
     if (rows.size() != n) throw std::runtime_error(std::string("pk: row map size mismatch for ") + what);
     set.nbases = n; set.c = c; set.nwin = msm_windows(c);
     DevBuf<AffT> bases(n ? n : 1);
@@ -320,8 +330,12 @@ void AlgorithmImpl::build_set(MsmSet<AffT>& set, const std::vector<uint8_t>& raw
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipStreamSynchronize(stream));
         if (!uniform && cfg.few_path && cfg.few_wide && latency_layout) {      // (the quotient bases have their own budgeted layout: init_key)
-            std::vector<uint8_t> raw_w(set.nwide * point_bytes); std::vector<uint32_t> rows_w(set.nwide);
-            for (size_t i = 0; i < set.nwide; i++) { memcpy(raw_w.data() + i * point_bytes, raw.data() + (size_t)wide[i] * point_bytes, point_bytes); rows_w[i] = rows[wide[i]]; }
+            KeyPoints raw_w; raw_w.x.resize(set.nwide * point_bytes); if (!raw.y.empty()) raw_w.y.resize(set.nwide * point_bytes);
+            std::vector<uint32_t> rows_w(set.nwide);
+            for (size_t i = 0; i < set.nwide; i++) {
+                memcpy(raw_w.x.data() + i * point_bytes, raw.x.data() + (size_t)wide[i] * point_bytes, point_bytes); rows_w[i] = rows[wide[i]];
+                if (!raw.y.empty()) memcpy(raw_w.y.data() + i * point_bytes, raw.y.data() + (size_t)wide[i] * point_bytes, point_bytes);
+            }
             set.few_wide.reset(new MsmSet<AffT>());
             build_set<AffT, XyzzT>(*set.few_wide, raw_w, point_bytes, rows_w, c, what, decomp, true, 8, classes, zero_row);
         }
@@ -438,7 +452,17 @@ void AlgorithmImpl::init_key(const R1csFile& cs, const PkFile& key) {
         HIP_CHECK(hipStreamSynchronize(stream));
         if (flag) throw std::runtime_error("pk: the domain generator is not gnark-crypto's root of unity for this size");
     }
-    auto cat = [](std::vector<uint8_t> a, std::initializer_list<const std::vector<uint8_t>*> more) { for (auto* m : more) a.insert(a.end(), m->begin(), m->end()); return a; };
+    // a slice and single points behind it as one set; the y bytes follow along when any part has raw elements (zeros for the parts that have none)
+    auto cat = [](KeyPoints a, std::initializer_list<KeyPoints> more) {
+        bool any_y = !a.y.empty();
+        for (auto& m : more) any_y = any_y || !m.y.empty();
+        if (any_y) a.y.resize(a.x.size(), 0);
+        for (auto& m : more) {
+            a.x.insert(a.x.end(), m.x.begin(), m.x.end());
+            if (any_y) { a.y.insert(a.y.end(), m.y.begin(), m.y.end()); a.y.resize(a.x.size(), 0); }
+        }
+        return a;
+    };
     const uint32_t ROW_ONE = 0, ROW_R = (uint32_t)n_wires, ROW_S = ROW_R + 1, ROW_NRS = ROW_R + 2;
     std::vector<uint32_t> rowsA, rowsB, rowsK;
     for (size_t i = 0; i < n_wires; i++) { if (!key.inf_A[i]) rowsA.push_back((uint32_t)i); if (!key.inf_B[i]) rowsB.push_back((uint32_t)i); }
@@ -488,17 +512,17 @@ void AlgorithmImpl::init_key(const R1csFile& cs, const PkFile& key) {
         cfg.window_w = 4;
         for (int c = 16; c >= 4; c--) if ((g1 * 64.0 + g2 * 128.0) * (double)((size_t)1 << (c - 1)) <= cfg.w_table_gb * 1e9) { cfg.window_w = c; break; }
     }
-    auto dec1 = [this](const std::vector<uint8_t>& raw, G1Aff* out) { return decompress_g1(raw, out); };
-    auto dec2 = [this](const std::vector<uint8_t>& raw, G2Aff* out) { return decompress_g2(raw, out); };
+    auto dec1 = [this](const KeyPoints& raw, G1Aff* out) { return decompress_g1(raw, out); };
+    auto dec2 = [this](const KeyPoints& raw, G2Aff* out) { return decompress_g2(raw, out); };
     const bool trace = cfg.trace_host;
     auto timed = [&](const char* what, auto&& fn) {
         const auto a0 = std::chrono::steady_clock::now(); const size_t b0 = table_bytes; fn();
         if (trace) fprintf(stderr, "  tables %-8s %7.0f ms %8.2f GiB\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a0).count(), (table_bytes - b0) / 1073741824.0);
     };
-    timed("G1.A", [&] { build_set<G1Aff, G1Xyzz>(mA, cat(key.g1_A, {&key.g1_alpha, &key.g1_delta}), 32, rowsA, cfg.window_w, "G1.A", dec1, false); });
-    timed("G1.B", [&] { build_set<G1Aff, G1Xyzz>(mB1, cat(key.g1_B, {&key.g1_beta, &key.g1_delta}), 32, rowsB, cfg.window_w, "G1.B", dec1, false); });
-    timed("G1.K", [&] { build_set<G1Aff, G1Xyzz>(mK, cat(key.g1_K, {&key.g1_delta}), 32, rowsK, cfg.window_w, "G1.K", dec1, false); });
-    if (!quotient_eval) timed("G1.Z", [&] { build_set<G1Aff, G1Xyzz>(mZ, key.g1_Z, 32, rowsZ, cfg.window_z, "G1.Z", dec1, true); });      // uniform full-width scalars
+    timed("G1.A", [&] { build_set<G1Aff, G1Xyzz>(mA, cat({key.g1_A, key.g1_A_y}, {{key.g1_alpha, key.g1_alpha_y}, {key.g1_delta, key.g1_delta_y}}), 32, rowsA, cfg.window_w, "G1.A", dec1, false); });
+    timed("G1.B", [&] { build_set<G1Aff, G1Xyzz>(mB1, cat({key.g1_B, key.g1_B_y}, {{key.g1_beta, key.g1_beta_y}, {key.g1_delta, key.g1_delta_y}}), 32, rowsB, cfg.window_w, "G1.B", dec1, false); });
+    timed("G1.K", [&] { build_set<G1Aff, G1Xyzz>(mK, cat({key.g1_K, key.g1_K_y}, {{key.g1_delta, key.g1_delta_y}}), 32, rowsK, cfg.window_w, "G1.K", dec1, false); });
+    if (!quotient_eval) timed("G1.Z", [&] { build_set<G1Aff, G1Xyzz>(mZ, KeyPoints(key.g1_Z, key.g1_Z_y), 32, rowsZ, cfg.window_z, "G1.Z", dec1, true); });      // uniform full-width scalars
     else {
         // The key's Z in evaluation form: U (scalars: the solver's c rows) and V (scalars: d on the zeta-coset), computed on the device from the
         // decompressed points; build_set then lays them out like any other set — "decompression" is a device copy of the finished bases.
@@ -506,7 +530,7 @@ void AlgorithmImpl::init_key(const R1csFile& cs, const PkFile& key) {
         if (nz + 1 != domain_n) throw std::runtime_error("pk: G1.Z does not hold n - 1 points");
         DevBuf<G1Aff> d_U(domain_n), d_V(domain_n); std::vector<uint8_t> stU(domain_n), stV(domain_n);
         timed("G1.Z -> U, V", [&] {
-            DevBuf<G1Aff> zb(nz); const std::vector<uint8_t> st = decompress_g1(key.g1_Z, zb.p);
+            DevBuf<G1Aff> zb(nz); const std::vector<uint8_t> st = decompress_g1(KeyPoints(key.g1_Z, key.g1_Z_y), zb.p);
             for (size_t i = 0; i < nz; i++) if (st[i] == 1) throw std::runtime_error("pk: invalid point in G1.Z");
             DevBuf<uint8_t> d_st(nz), d_stU(domain_n), d_stV(domain_n); d_st.upload(st.data(), nz, stream);
             DevBuf<fe> tw(domain_n / 2); DevBuf<G1Xyzz> scratch(domain_n); DevBuf<uint32_t> d_perm(domain_n);
@@ -519,8 +543,8 @@ void AlgorithmImpl::init_key(const R1csFile& cs, const PkFile& key) {
             HIP_CHECK(hipStreamSynchronize(stream));
         });
         auto from_dev = [this](const DevBuf<G1Aff>& src, const std::vector<uint8_t>& st) {
-            return [this, &src, &st](const std::vector<uint8_t>& raw, G1Aff* out) {
-                const size_t n = raw.size() / 32;
+            return [this, &src, &st](const KeyPoints& raw, G1Aff* out) {
+                const size_t n = raw.x.size() / 32;
                 HIP_CHECK(hipMemcpyAsync(out, src.p, n * sizeof(G1Aff), hipMemcpyDeviceToDevice, stream));
                 HIP_CHECK(hipStreamSynchronize(stream));
                 return std::vector<uint8_t>(st.begin(), st.begin() + n);
@@ -555,14 +579,14 @@ void AlgorithmImpl::init_key(const R1csFile& cs, const PkFile& key) {
         const size_t nz = key.g1_Z.size() / 32;
         int cv = 0;
         for (int t : {8, 6, 4}) if ((double)nz * msm_windows(t) * (double)((size_t)1 << (t - 1)) * sizeof(G1Aff) <= (double)cfg.few_z_gb * 1e9) { cv = t; break; }
-        if (cv) timed("G1.Z (latency layout)", [&] { build_set<G1Aff, G1Xyzz>(mZfew, key.g1_Z, 32, rowsZkey, cfg.window_z, "G1.Z", dec1, true, cv); });
+        if (cv) timed("G1.Z (latency layout)", [&] { build_set<G1Aff, G1Xyzz>(mZfew, KeyPoints(key.g1_Z, key.g1_Z_y), 32, rowsZkey, cfg.window_z, "G1.Z", dec1, true, cv); });
     }
-    timed("G2.B", [&] { build_set<G2Aff, G2Xyzz>(mB2, cat(key.g2_B, {&key.g2_beta, &key.g2_delta}), 64, rowsB2, cfg.window_w, "G2.B", dec2, false); });
+    timed("G2.B", [&] { build_set<G2Aff, G2Xyzz>(mB2, cat({key.g2_B, key.g2_B_y}, {{key.g2_beta, key.g2_beta_y}, {key.g2_delta, key.g2_delta_y}}), 64, rowsB2, cfg.window_w, "G2.B", dec2, false); });
     if (cs.has_commitment) {
         if (cs.n_public_committed) throw std::runtime_error("r1cs: public committed wires are not supported");
         if (key.ped_basis.size() != cs.commit_private.size() * 32) throw std::runtime_error("pk: commitment basis size does not match the r1cs");
-        build_set<G1Aff, G1Xyzz>(mPed, key.ped_basis, 32, cs.commit_private, cfg.window_w, "commitment basis", dec1, false);
-        build_set<G1Aff, G1Xyzz>(mPedSigma, key.ped_basis_sigma, 32, cs.commit_private, cfg.window_w, "commitment basis (sigma)", dec1, false);
+        build_set<G1Aff, G1Xyzz>(mPed, KeyPoints(key.ped_basis, key.ped_basis_y), 32, cs.commit_private, cfg.window_w, "commitment basis", dec1, false);
+        build_set<G1Aff, G1Xyzz>(mPedSigma, KeyPoints(key.ped_basis_sigma, key.ped_basis_sigma_y), 32, cs.commit_private, cfg.window_w, "commitment basis (sigma)", dec1, false);
     }
 }
 

@@ -4,6 +4,7 @@
 #include <algorithm>
 #include <cstring>
 #include <stdexcept>
+#include <string>
 
 namespace gsc {
 namespace {
@@ -216,6 +217,25 @@ R1csFile parse_r1cs(const uint8_t* buf, size_t len) {
     return cs;
 }
 
+size_t walk_points(const uint8_t* p, size_t len, size_t count, size_t cb, std::vector<uint8_t>& x, std::vector<uint8_t>& y, const char* what) {
+    // every element takes at least cb bytes: a count the data cannot hold is refused before anything is allocated for it
+    if (count > len / cb) throw std::runtime_error(std::string(what) + ": point count exceeds the data");
+    x.assign(count * cb, 0); y.clear();
+    size_t i = 0;
+    for (size_t k = 0; k < count; k++) {
+        if (i >= len) throw std::runtime_error(std::string(what) + ": data ends before point " + std::to_string(k));
+        const bool raw = (p[i] & 0xC0) == 0;
+        if ((raw ? 2 * cb : cb) > len - i) throw std::runtime_error(std::string(what) + ": data ends inside point " + std::to_string(k));
+        memcpy(x.data() + k * cb, p + i, cb);
+        if (raw) {
+            if (y.empty()) y.assign(count * cb, 0);
+            memcpy(y.data() + k * cb, p + i + cb, cb);
+        }
+        i += raw ? 2 * cb : cb;
+    }
+    return i;
+}
+
 PkFile parse_pk(const uint8_t* buf, size_t len) {
     PkFile pk; Cursor c(buf, len);
     pk.domain_n = c.u64be();
@@ -223,27 +243,29 @@ PkFile parse_pk(const uint8_t* buf, size_t len) {
     memcpy(pk.n_inv, c.take(32), 32); memcpy(pk.omega, c.take(32), 32); memcpy(pk.omega_inv, c.take(32), 32);
     memcpy(pk.coset_g, c.take(32), 32); memcpy(pk.coset_g_inv, c.take(32), 32);
     c.u8();   // "with precompute" flag
-    auto g1 = [&](std::vector<uint8_t>& v) { const uint8_t* q = c.take(32); v.assign(q, q + 32); };
-    auto g2 = [&](std::vector<uint8_t>& v) { const uint8_t* q = c.take(64); v.assign(q, q + 64); };
-    auto slice = [&](std::vector<uint8_t>& v, size_t sz) { const uint32_t n = c.u32be(); const uint8_t* q = c.take(size_t(n) * sz); v.assign(q, q + size_t(n) * sz); };
-    g1(pk.g1_alpha); g1(pk.g1_beta); g1(pk.g1_delta);
-    slice(pk.g1_A, 32); slice(pk.g1_B, 32); slice(pk.g1_Z, 32); slice(pk.g1_K, 32);
-    g2(pk.g2_beta); g2(pk.g2_delta); slice(pk.g2_B, 64);
+    // points and point slices as gnark's decoder walks them: compressed or raw, element by element (formats.hpp)
+    auto points = [&](std::vector<uint8_t>& x, std::vector<uint8_t>& y, size_t n, size_t cb) { c.i += walk_points(c.p + c.i, c.n - c.i, n, cb, x, y, "pk"); };
+    auto g1 = [&](std::vector<uint8_t>& x, std::vector<uint8_t>& y) { points(x, y, 1, 32); };
+    auto g2 = [&](std::vector<uint8_t>& x, std::vector<uint8_t>& y) { points(x, y, 1, 64); };
+    auto slice = [&](std::vector<uint8_t>& x, std::vector<uint8_t>& y, size_t cb) { const uint32_t n = c.u32be(); points(x, y, n, cb); };
+    g1(pk.g1_alpha, pk.g1_alpha_y); g1(pk.g1_beta, pk.g1_beta_y); g1(pk.g1_delta, pk.g1_delta_y);
+    slice(pk.g1_A, pk.g1_A_y, 32); slice(pk.g1_B, pk.g1_B_y, 32); slice(pk.g1_Z, pk.g1_Z_y, 32); slice(pk.g1_K, pk.g1_K_y, 32);
+    g2(pk.g2_beta, pk.g2_beta_y); g2(pk.g2_delta, pk.g2_delta_y); slice(pk.g2_B, pk.g2_B_y, 64);
     pk.n_wires = c.u64be(); c.u64be(); c.u64be();   // NbInfinityA / NbInfinityB are implied by the flag arrays
     { const uint8_t* q = c.take(pk.n_wires); pk.inf_A.assign(q, q + pk.n_wires); }
     { const uint8_t* q = c.take(pk.n_wires); pk.inf_B.assign(q, q + pk.n_wires); }
     const uint32_t nck = c.u32be();
     if (nck > 1) throw std::runtime_error("pk: more than one commitment key is not supported");
-    if (nck == 1) { pk.has_commitment_key = true; slice(pk.ped_basis, 32); slice(pk.ped_basis_sigma, 32); if (pk.ped_basis.size() != pk.ped_basis_sigma.size()) throw std::runtime_error("pk: commitment key size mismatch"); }
+    if (nck == 1) {
+        pk.has_commitment_key = true; slice(pk.ped_basis, pk.ped_basis_y, 32); slice(pk.ped_basis_sigma, pk.ped_basis_sigma_y, 32);
+        if (pk.ped_basis.size() != pk.ped_basis_sigma.size()) throw std::runtime_error("pk: commitment key size mismatch");
+    }
     if (c.i != len) throw std::runtime_error("pk: trailing bytes");
     size_t na = 0, nb = 0;
     for (size_t i = 0; i < pk.n_wires; i++) { na += !pk.inf_A[i]; nb += !pk.inf_B[i]; }
-    if (na * 32 != pk.g1_A.size() || nb * 32 != pk.g1_B.size() || nb * 64 != pk.g2_B.size() || pk.g1_Z.size() != (pk.domain_n - 1) * 32)
+    // counts of points (the vectors have one fixed stride whatever the encoding of an element was)
+    if (na != pk.g1_A.size() / 32 || nb != pk.g1_B.size() / 32 || nb != pk.g2_B.size() / 64 || pk.g1_Z.size() / 32 != pk.domain_n - 1)
         throw std::runtime_error("pk: inconsistent slice sizes");
-    // only the compressed encoding written by ProvingKey.WriteTo (keygen.go:350-352) is accepted
-    auto check = [](const std::vector<uint8_t>& v, size_t sz) { for (size_t o = 0; o < v.size(); o += sz) if ((v[o] & 0xC0) == 0) throw std::runtime_error("pk: uncompressed point encoding is not supported"); };
-    check(pk.g1_alpha, 32); check(pk.g1_beta, 32); check(pk.g1_delta, 32); check(pk.g1_A, 32); check(pk.g1_B, 32); check(pk.g1_Z, 32); check(pk.g1_K, 32);
-    check(pk.g2_beta, 64); check(pk.g2_delta, 64); check(pk.g2_B, 64); check(pk.ped_basis, 32); check(pk.ped_basis_sigma, 32);
     return pk;
 }
 

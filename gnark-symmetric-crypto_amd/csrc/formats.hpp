@@ -1,5 +1,5 @@
 // Host-side decoders for the reference's binary artefacts (no field arithmetic on the host:
-// everything numeric is shipped to the GPU as raw limbs / compressed coordinates).
+// everything numeric is shipped to the GPU as raw limbs / encoded coordinates, compressed or raw as the file has them).
 //
 //  * R1CS  : gnark v0.11.0 constraint.ConstraintSystem.WriteTo layout, read by the reference at
 //            libraries/prover/impl/prove_impl.go:102-103 (format: SURVEY.md App. A).
@@ -40,19 +40,35 @@ struct R1csFile {
 // throws std::runtime_error on malformed input
 R1csFile parse_r1cs(const uint8_t* buf, size_t len);
 
-// One compressed point as stored in the key file, split into (x bytes big-endian with the flag bits
-// cleared, flag).  flag: 0x80 smaller y, 0xC0 larger y, 0x40 infinity.
+// ---- gnark-crypto point encodings ----
+// The two top bits of an element's first byte select its form, element by element, as gnark's decoder reads them:
+//   10 / 11  compressed, X only (smaller / larger Y)        32 B in G1, 64 B in G2 (X.A1 | X.A0)
+//   01       compressed point at infinity                   32 B / 64 B
+//   00       raw (WriteRawTo), X | Y                        64 B in G1, 128 B in G2 (X.A1 | X.A0 | Y.A1 | Y.A0)
+// A raw element whose bytes are all zero is the point at infinity.
+// walk_points reads `count` elements from p[0, len) into fixed strides: x gets coord_bytes (32 / 64) per element — the X bytes, flag
+// bits in place — and y the same stride: the Y bytes of a raw element, zeros for a compressed one.  y stays EMPTY when no element
+// is raw, so a compressed-only slice looks exactly as it did before raw keys were read.  Returns the bytes consumed; throws
+// std::runtime_error("<what>: ...") when the data ends inside an element.  Pure host code: no arithmetic, no device.
+size_t walk_points(const uint8_t* p, size_t len, size_t count, size_t coord_bytes, std::vector<uint8_t>& x, std::vector<uint8_t>& y, const char* what);
+
+// The proving key as stored in the key file.  Every point set is a fixed-stride vector of X bytes (big-endian, flag bits still in the top
+// bits of byte 0: 0x80 smaller y, 0xC0 larger y, 0x40 infinity, 0x00 raw) and a companion `_y` vector of the same stride that holds
+// the Y bytes of the raw elements; the companion is empty when the whole set is compressed (see walk_points).
 struct PkFile {
     uint64_t domain_n = 0;
     uint8_t n_inv[32], omega[32], omega_inv[32], coset_g[32], coset_g_inv[32];   // Fr, big-endian canonical
-    // G1 points: 32 bytes each (flag still in the top bits of byte 0)
+    // G1 points: 32 bytes each
     std::vector<uint8_t> g1_alpha, g1_beta, g1_delta, g1_A, g1_B, g1_Z, g1_K;
+    std::vector<uint8_t> g1_alpha_y, g1_beta_y, g1_delta_y, g1_A_y, g1_B_y, g1_Z_y, g1_K_y;
     // G2 points: 64 bytes each (X.A1 | X.A0)
     std::vector<uint8_t> g2_beta, g2_delta, g2_B;
+    std::vector<uint8_t> g2_beta_y, g2_delta_y, g2_B_y;
     uint64_t n_wires = 0;
     std::vector<uint8_t> inf_A, inf_B;
     bool has_commitment_key = false;
     std::vector<uint8_t> ped_basis, ped_basis_sigma;   // G1, 32 bytes each
+    std::vector<uint8_t> ped_basis_y, ped_basis_sigma_y;
 };
 PkFile parse_pk(const uint8_t* buf, size_t len);
 

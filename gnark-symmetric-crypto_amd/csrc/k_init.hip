@@ -40,8 +40,11 @@ __global__ void k_decompress_g1(const uint8_t* in, G1Aff* out, uint8_t* status, 
     const uint8_t* b = in + 32 * i;
     uint8_t flag = b[0] & 0xC0;
     G1Aff r; uint8_t st = 0;
-    if (flag == 0x40) { r.x = Fp::from_u32(1); r.y = Fp::from_u32(2); st = 2; }
-    else {
+    if (flag == 0x40) {      // infinity only when every other bit is zero, as gnark-crypto's decoder (and verify_dev.hpp's decode_g1) has it
+        uint32_t stray = b[0] & 0x3F;
+        for (int k = 1; k < 32; k++) stray |= b[k];
+        r.x = Fp::from_u32(1); r.y = Fp::from_u32(2); st = stray ? 1 : 2;
+    } else {
         fe xc = fe_from_be_bytes(b, true);
         if (!fe_lt_mod_p(xc) || flag == 0) st = 1;
         fe x = Fp::to_mont(xc);
@@ -98,6 +101,9 @@ __global__ void k_decompress_g2(const uint8_t* in, G2Aff* out, uint8_t* status, 
             fe2 rhs = Fp2::add(Fp2::mul(Fp2::sqr(x), x), bt), y;
             if (fp2_sqrt(rhs, y)) { r.x = x; r.y = y; break; }
         }
+        uint32_t stray = b[0] & 0x3F;      // infinity only when every other bit is zero
+        for (int k = 1; k < 64; k++) stray |= b[k];
+        if (stray) st = 1;
     } else {
         fe x1c = fe_from_be_bytes(b, true), x0c = fe_from_be_bytes(b + 32, false);
         if (!fe_lt_mod_p(x1c) || !fe_lt_mod_p(x0c) || flag == 0) st = 1;
@@ -127,6 +133,83 @@ __device__ __forceinline__ fe9 to_fp29(const fe& old_mont) { return Fp29::to_mon
 __device__ __forceinline__ Aff9<Fp29f> base_to_fp29(const Aff<Fp>* b) { return Aff9<Fp29f>{to_fp29(b->x), to_fp29(b->y)}; }
 __device__ __forceinline__ Aff9<Fp2x> base_to_fp29(const Aff<Fp2>* b) {
     return Aff9<Fp2x>{fe9x2{to_fp29(b->x.a0), to_fp29(b->x.a1)}, fe9x2{to_fp29(b->y.a0), to_fp29(b->y.a1)}};
+}
+
+// ---- raw (uncompressed) key points: X | Y as gnark's WriteRawTo stores them (formats.hpp walk_points) ----
+// The raw kernels run AFTER k_decompress_g1/g2 over the same n elements and only touch those whose flag bits are 00 (which the
+// compressed kernels marked bad): a compressed element keeps what it got, bit for bit.  in_y has the stride of in_x (32 / 64 B) and
+// holds the Y bytes of the raw elements.  Both coordinates canonical, the curve equation exactly, no square root; all-zero bytes are
+// the point at infinity (status 2 and a finite stand-in, like the compressed infinity).  Status and output as the compressed path.
+__device__ __forceinline__ bool fe_is_zero_raw(const fe& a) { uint32_t o = 0; for (int i = 0; i < 8; i++) o |= a.l[i]; return o == 0; }
+
+__global__ __launch_bounds__(64) void k_decode_raw_g1(const uint8_t* in_x, const uint8_t* in_y, G1Aff* out, uint8_t* status, size_t n) {
+    size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint8_t* bx = in_x + 32 * i;
+    if ((bx[0] & 0xC0) != 0) return;
+    const fe xc = fe_from_be_bytes(bx, false), yc = fe_from_be_bytes(in_y + 32 * i, false);
+    G1Aff r; r.x = Fp::from_u32(1); r.y = Fp::from_u32(2);
+    uint8_t st = 1;
+    if (fe_is_zero_raw(xc) && fe_is_zero_raw(yc)) st = 2;
+    else if (fe_lt_mod_p(xc) && fe_lt_mod_p(yc)) {
+        const fe x = Fp::to_mont(xc), y = Fp::to_mont(yc);
+        if (Fp::eq(Fp::sqr(y), Fp::add(Fp::mul(Fp::sqr(x), x), Fp::from_u32(3)))) { st = 0; r.x = x; r.y = y; }
+    }
+    out[i] = r; status[i] = st;
+}
+
+__global__ __launch_bounds__(64) void k_decode_raw_g2(const uint8_t* in_x, const uint8_t* in_y, G2Aff* out, uint8_t* status, size_t n) {
+    size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint8_t* bx = in_x + 64 * i;
+    if ((bx[0] & 0xC0) != 0) return;
+    const uint8_t* by = in_y + 64 * i;
+    const fe x1c = fe_from_be_bytes(bx, false), x0c = fe_from_be_bytes(bx + 32, false), y1c = fe_from_be_bytes(by, false), y0c = fe_from_be_bytes(by + 32, false);
+    const fe inv82 = Fp::inv(Fp::from_u32(82));      // twist coefficient b' = 3/(9+u) = 3*(9-u)/82, as in k_decompress_g2
+    fe2 bt; bt.a0 = Fp::mul(Fp::from_u32(27), inv82); bt.a1 = Fp::neg(Fp::mul(Fp::from_u32(3), inv82));
+    G2Aff r; uint8_t st = 1;
+    r.x = Fp2::zero(); r.y = Fp2::zero();
+    if (fe_is_zero_raw(x1c) && fe_is_zero_raw(x0c) && fe_is_zero_raw(y1c) && fe_is_zero_raw(y0c)) {
+        st = 2;      // a finite stand-in for a base that is never selected: the first x = (k, 0) with a point above it (k_decompress_g2's choice)
+        for (uint32_t k = 1; k < 64; k++) {
+            fe2 x; x.a0 = Fp::from_u32(k); x.a1 = Fp::zero();
+            fe2 rhs = Fp2::add(Fp2::mul(Fp2::sqr(x), x), bt), y;
+            if (fp2_sqrt(rhs, y)) { r.x = x; r.y = y; break; }
+        }
+    } else if (fe_lt_mod_p(x1c) && fe_lt_mod_p(x0c) && fe_lt_mod_p(y1c) && fe_lt_mod_p(y0c)) {
+        fe2 x, y; x.a0 = Fp::to_mont(x0c); x.a1 = Fp::to_mont(x1c); y.a0 = Fp::to_mont(y0c); y.a1 = Fp::to_mont(y1c);
+        if (Fp2::eq(Fp2::sqr(y), Fp2::add(Fp2::mul(Fp2::sqr(x), x), bt))) st = 0;
+        r.x = x; r.y = y;
+    }
+    out[i] = r; status[i] = st;
+}
+
+// G2 subgroup test for the key's G2 points, whichever encoding they came in: the twist has order r (2p - r), so a point on it need not
+// have order r, and gnark's decoder refuses one that has not ("subgroup check failed").  One thread per point, the plain definition
+// [r] Q == O — the predicate of libverify (verifier.cpp g2_in_subgroup) and of the GPU verifier (verify_dev.hpp), no endomorphism
+// shortcut — by double-and-add over the bits of r with the exact group law of Curve9<Fp2x>: 253 doublings and 127 additions.  The
+// scalar is the same in every lane, so the loop's control flow is wave-uniform.  Only points with status 0 are tested (1: refused
+// already, 2: infinity); a point outside the subgroup gets status 1.
+__global__ __launch_bounds__(64) void k_g2_subgroup(const G2Aff* pts, uint8_t* status, size_t n) {
+    size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i >= n || status[i] != 0) return;
+    using C = Curve9<Fp2x>;
+    constexpr uint32_t R[8] = {0xf0000001u, 0x43e1f593u, 0x79b97091u, 0x2833e848u, 0x8181585du, 0xb85045b6u, 0xe131a029u, 0x30644e72u};
+    const Aff9<Fp2x> q = base_to_fp29(reinterpret_cast<const Aff<Fp2>*>(pts) + i);
+    Xyzz9<Fp2x> acc = C::from_aff(q);
+#pragma unroll 1
+    for (int b = 252; b >= 0; b--) {      // r < 2^254, bit 253 set
+        acc = C::dbl(acc);
+        if ((R[b >> 5] >> (b & 31)) & 1) acc = C::template madd<true>(acc, q);
+    }
+    if (!(acc.inf || Fp2x::is_zero(acc.zz))) status[i] = 1;
+}
+
+// TEST HOOK kernel (gsc_debug_decode_points): Montgomery coordinates as the decode kernels store them -> canonical integers
+__global__ void k_fp_from_mont(const fe* in, fe* out, size_t n) {
+    size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    out[i] = Fp::from_mont(in[i]);
 }
 
 // Signed subset-sum tables for groups of eight bases whose scalars are -1, 0 or 1 in (almost) every proof: entry v-1 of group g is
@@ -366,6 +449,18 @@ void launch_decompress_g1(const uint8_t* in, G1Aff* out, uint8_t* status, size_t
 }
 void launch_decompress_g2(const uint8_t* in, G2Aff* out, uint8_t* status, size_t n, hipStream_t s) {
     if (n) hipLaunchKernelGGL(k_decompress_g2, dim3(blocks_for(n, 64)), dim3(64), 0, s, in, out, status, n);
+}
+void launch_decode_raw_g1(const uint8_t* in_x, const uint8_t* in_y, G1Aff* out, uint8_t* status, size_t n, hipStream_t s) {
+    if (n) hipLaunchKernelGGL(k_decode_raw_g1, dim3(blocks_for(n, 64)), dim3(64), 0, s, in_x, in_y, out, status, n);
+}
+void launch_decode_raw_g2(const uint8_t* in_x, const uint8_t* in_y, G2Aff* out, uint8_t* status, size_t n, hipStream_t s) {
+    if (n) hipLaunchKernelGGL(k_decode_raw_g2, dim3(blocks_for(n, 64)), dim3(64), 0, s, in_x, in_y, out, status, n);
+}
+void launch_g2_subgroup(const G2Aff* pts, uint8_t* status, size_t n, hipStream_t s) {
+    if (n) hipLaunchKernelGGL(k_g2_subgroup, dim3(blocks_for(n, 64)), dim3(64), 0, s, pts, status, n);
+}
+void launch_fp_from_mont(const fe* in, fe* out, size_t n, hipStream_t s) {
+    if (n) hipLaunchKernelGGL(k_fp_from_mont, dim3(blocks_for(n, 64)), dim3(64), 0, s, in, out, n);
 }
 void launch_fr_from_be(const uint8_t* in, fe* out, size_t n, hipStream_t s) {
     if (n) hipLaunchKernelGGL(k_fr_from_be, dim3(blocks_for(n, 64)), dim3(64), 0, s, in, out, n);

@@ -14,8 +14,9 @@ namespace {
 // key points: n1 compressed G1 (32 bytes) then n2 compressed G2 (64 bytes, with the subgroup test); st: 0 finite, 1 infinity, -1 bad
 __global__ __launch_bounds__(64) void k_verify_key_points(const uint8_t* g1, size_t n1, const uint8_t* g2, size_t n2, VP1* o1, VP2* o2, int8_t* st) {
     const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
-    if (i < n1) st[i] = (int8_t)decode_g1(g1 + 32 * i, o1[i]);
-    else if (i < n1 + n2) st[i] = (int8_t)decode_g2(g2 + 64 * (i - n1), o2[i - n1]);
+    // slots of 64 / 128 bytes: a raw point fills its slot, a compressed one the first half (verify_dev.hpp decode_g1_key / decode_g2_key)
+    if (i < n1) st[i] = (int8_t)decode_g1_key(g1 + 64 * i, o1[i]);
+    else if (i < n1 + n2) st[i] = (int8_t)decode_g2_key(g2 + 128 * (i - n1), o2[i - n1]);
 }
 // window tables: entry (w, v) for w < nwin; desc[w] = (first K index, shift | subset << 16)
 __global__ __launch_bounds__(64) void k_verify_tables(const VP1* K, const uint32_t* desc, size_t nwin, VP1* table) {

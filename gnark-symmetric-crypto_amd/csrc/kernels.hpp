@@ -21,6 +21,15 @@ struct G2Xyzz { fe2 x, y, zz, zzz; };      // 256 B
 // Infinity encodings produce the generator and status 2 (caller maps the base to the zero scalar row).
 void launch_decompress_g1(const uint8_t* in, G1Aff* out, uint8_t* status, size_t n, hipStream_t s);
 void launch_decompress_g2(const uint8_t* in, G2Aff* out, uint8_t* status, size_t n, hipStream_t s);
+// Raw (X | Y) elements of the same slice: launched after launch_decompress_* over the same n elements, they rewrite out / status of the
+// elements whose flag bits are 00 and leave the compressed ones alone.  in_y: the stride of in_x, the Y bytes of the raw elements.
+// status 0: canonical coordinates on the curve; 1: refused; 2: all-zero bytes, the point at infinity (a finite stand-in in out).
+void launch_decode_raw_g1(const uint8_t* in_x, const uint8_t* in_y, G1Aff* out, uint8_t* status, size_t n, hipStream_t s);
+void launch_decode_raw_g2(const uint8_t* in_x, const uint8_t* in_y, G2Aff* out, uint8_t* status, size_t n, hipStream_t s);
+// [r] Q == O for every decoded G2 point with status 0; status becomes 1 where it does not hold (a twist point outside G2)
+void launch_g2_subgroup(const G2Aff* pts, uint8_t* status, size_t n, hipStream_t s);
+// TEST HOOK (gsc_debug_decode_points): n Montgomery Fp values -> canonical
+void launch_fp_from_mont(const fe* in, fe* out, size_t n, hipStream_t s);
 // canonical big-endian Fr -> Montgomery limbs
 void launch_fr_from_be(const uint8_t* in, fe* out, size_t n, hipStream_t s);
 void launch_fr_inverse(const fe* in, fe* out, size_t n, hipStream_t s);

@@ -210,6 +210,27 @@ bool g2_decode(const uint8_t* b, G2& p) {
     return g2_in_subgroup(p);
 }
 
+// Points of a KEY come in either encoding (verify_common.hpp point_is_raw); proofs keep their compressed 196-byte slots and go through
+// g1_decode / g2_decode above.  A raw point: canonical coordinates, the curve equation exactly, no square root; all-zero bytes are the
+// point at infinity.  G2 gets the same subgroup test as the compressed form.
+bool g1_decode_key(const uint8_t* b, G1& p) {
+    if (!gsc::verify::point_is_raw(b)) return g1_decode(b, p);
+    bool zero = true; for (int i = 0; i < 64; i++) zero = zero && !b[i];
+    if (zero) { p = {Fp::zero(), Fp::zero(), true}; return true; }
+    if (!Fp::from_be(b, p.x) || !Fp::from_be(b + 32, p.y)) return false;
+    p.inf = false;
+    return p.y.sq() == p.x.sq() * p.x + K().three;
+}
+bool g2_decode_key(const uint8_t* b, G2& p) {
+    if (!gsc::verify::point_is_raw(b)) return g2_decode(b, p);
+    bool zero = true; for (int i = 0; i < 128; i++) zero = zero && !b[i];
+    if (zero) { p = {Fp2::zero(), Fp2::zero(), true}; return true; }
+    if (!Fp::from_be(b, p.x.b) || !Fp::from_be(b + 32, p.x.a) || !Fp::from_be(b + 64, p.y.b) || !Fp::from_be(b + 96, p.y.a)) return false;
+    p.inf = false;
+    if (!(p.y.sq() == p.x.sq() * p.x + K().twist_b)) return false;
+    return g2_in_subgroup(p);
+}
+
 // Fp12 = Fp2[w]/(w^6 - xi)
 struct Fp12 {
     Fp2 c[6];
@@ -301,8 +322,8 @@ std::unique_ptr<VerifyingKey> parse_vk(const uint8_t* b, size_t n) {
     gsc::verify::VkLayout lay; std::string err;
     if (!gsc::verify::parse_vk_layout(b, n, lay, &err)) throw std::runtime_error(err);
     auto vk = std::make_unique<VerifyingKey>(); G1 skip1;
-    auto g1 = [&](size_t at, G1& p) { if (!g1_decode(b + at, p)) throw std::runtime_error("vk: bad G1 point"); };
-    auto g2 = [&](size_t at, G2& p) { if (!g2_decode(b + at, p)) throw std::runtime_error("vk: bad G2 point"); };
+    auto g1 = [&](size_t at, G1& p) { if (!g1_decode_key(b + at, p)) throw std::runtime_error("vk: bad G1 point"); };
+    auto g2 = [&](size_t at, G2& p) { if (!g2_decode_key(b + at, p)) throw std::runtime_error("vk: bad G2 point"); };
     g1(lay.alpha, vk->alpha); g1(lay.g1_beta, skip1); g2(lay.beta, vk->beta); g2(lay.gamma, vk->gamma); g1(lay.g1_delta, skip1); g2(lay.delta, vk->delta);
     vk->K.resize(lay.K.size()); for (size_t k = 0; k < lay.K.size(); k++) g1(lay.K[k], vk->K[k]);
     vk->has_commitment = lay.has_commitment;

@@ -10,14 +10,16 @@ uint32_t be32(const uint8_t* p) { return (uint32_t)p[0] << 24 | (uint32_t)p[1] <
 bool parse_vk_layout(const uint8_t* b, size_t n, VkLayout& vk, std::string* err) {
     size_t i = 0;
     auto fail = [&](const char* m) { if (err) *err = m; return false; };
-    auto take = [&](size_t k, size_t& at) { if (i + k > n) return false; at = i; i += k; return true; };
+    auto take = [&](size_t k, size_t& at) { if (k > n - i) return false; at = i; i += k; return true; };
+    // one point as gnark's decoder reads it: flag bits 00 in its first byte -> raw, X | Y (2 x cb bytes), anything else -> cb bytes
+    auto point = [&](size_t cb, size_t& at) { if (i >= n) return false; return take(point_is_raw(b + i) ? 2 * cb : cb, at); };
     size_t at;
-    if (!take(32, vk.alpha) || !take(32, vk.g1_beta) || !take(64, vk.beta) || !take(64, vk.gamma) || !take(32, vk.g1_delta) || !take(64, vk.delta)) return fail("vk: truncated");
+    if (!point(32, vk.alpha) || !point(32, vk.g1_beta) || !point(64, vk.beta) || !point(64, vk.gamma) || !point(32, vk.g1_delta) || !point(64, vk.delta)) return fail("vk: truncated");
     if (!take(4, at)) return fail("vk: truncated");
     const uint32_t nk = be32(b + at);
-    if ((size_t)nk > (n - i) / 32) return fail("vk: truncated");
+    if ((size_t)nk > (n - i) / 32) return fail("vk: K count exceeds the key");
     vk.K.resize(nk);
-    for (auto& k : vk.K) take(32, k);
+    for (auto& k : vk.K) if (!point(32, k)) return fail("vk: truncated inside K");
     if (!take(4, at)) return fail("vk: truncated");
     const uint32_t outer = be32(b + at);
     if (outer > 1) return fail("vk: more than one commitment");
@@ -29,7 +31,7 @@ bool parse_vk_layout(const uint8_t* b, size_t n, VkLayout& vk, std::string* err)
     const uint32_t nck = be32(b + at);
     if (nck != outer) return fail("vk: commitment key count");
     vk.has_commitment = nck != 0;
-    if (nck && (!take(64, vk.ped_g) || !take(64, vk.ped_gsn))) return fail("vk: truncated");
+    if (nck && (!point(64, vk.ped_g) || !point(64, vk.ped_gsn))) return fail("vk: truncated");
     if (i != n) return fail("vk: trailing bytes");
     return true;
 }

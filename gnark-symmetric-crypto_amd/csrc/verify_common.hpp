@@ -16,9 +16,13 @@ constexpr size_t kSignalBytes = 144;                  // ct[64] | nonce[12] | co
 constexpr size_t kWindows = 144;                      // public-input byte windows per statement (both circuits)
 constexpr size_t kChachaInputs = 1152, kAesInputs = 141;
 
-// gnark VerifyingKey.WriteTo layout: offsets of the compressed points in the key bytes
+// A point of a key is compressed (flag bits 10 / 11, or 01 for infinity: 32 B in G1, 64 B in G2) or raw (flag bits 00: X | Y, 64 B / 128 B,
+// all zero for infinity), element by element, as gnark's decoder reads what WriteTo / WriteRawTo wrote.
+inline bool point_is_raw(const uint8_t* first_byte) { return (*first_byte & 0xC0) == 0; }
+
+// gnark VerifyingKey.WriteTo / WriteRawTo layout: offsets of the points in the key bytes (each in either encoding: point_is_raw)
 struct VkLayout {
-    size_t alpha = 0, g1_beta = 0, beta = 0, gamma = 0, g1_delta = 0, delta = 0;   // G1 32 bytes, G2 64 bytes
+    size_t alpha = 0, g1_beta = 0, beta = 0, gamma = 0, g1_delta = 0, delta = 0;   // G1 32 (raw 64) bytes, G2 64 (raw 128) bytes
     std::vector<size_t> K;                                                        // G1
     bool has_commitment = false;
     size_t ped_g = 0, ped_gsn = 0;                                                // G2, when has_commitment

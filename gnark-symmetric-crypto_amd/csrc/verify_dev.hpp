@@ -224,6 +224,34 @@ DEVFN int decode_g2(const uint8_t* b, VP2& p) {
     return s;
 }
 
+// ---- points of a KEY: compressed as above, or raw (flag bits 00: X | Y as WriteRawTo writes them), as strict as libverify's g1_decode_key /
+// g2_decode_key.  b is a slot of 64 (G1) / 128 (G2) bytes: a compressed element sits in its first half.  Raw: canonical coordinates, the
+// curve equation exactly, no square root; all-zero bytes are the point at infinity.  Proofs never come this way. ----
+DEVFN int decode_g1_key(const uint8_t* b, VP1& p) {
+    if ((b[0] & 0xC0) != 0) return decode_g1(b, p);
+    p.x = F::zero(); p.y = F::zero(); p.inf = 1;
+    uint32_t o = 0;
+    for (int i = 0; i < 64; i++) o |= b[i];
+    if (!o) return 1;
+    e1 x, y;
+    if (!fp_from_be(b, false, x) || !fp_from_be(b + 32, false, y)) return -1;
+    if (!eq1(F::sqr(y), red(F::add(F::mul(F::sqr(x), x), three1())))) return -1;
+    p.x = x; p.y = y; p.inf = 0;
+    return 0;
+}
+DEVFN int decode_g2_key(const uint8_t* b, VP2& p) {      // with the subgroup test
+    if ((b[0] & 0xC0) != 0) return decode_g2(b, p);
+    p.x = F2::zero(); p.y = F2::zero(); p.inf = 1;
+    uint32_t o = 0;
+    for (int i = 0; i < 128; i++) o |= b[i];
+    if (!o) return 1;
+    e2 x, y;
+    if (!fp_from_be(b, false, x.a1) || !fp_from_be(b + 32, false, x.a0) || !fp_from_be(b + 64, false, y.a1) || !fp_from_be(b + 96, false, y.a0)) return -1;
+    if (!eq2(sqr2(y), add2(mul2(sqr2(x), x), twist_b()))) return -1;
+    p.x = x; p.y = y; p.inf = 0;
+    return g2_in_subgroup(p) ? 0 : -1;
+}
+
 // ---- G1 sums (exact XYZZ) ----
 using G1X = bn254::Xyzz9<bn254::Fp29f>;
 DEVFN G1X g1_inf() { return bn254::G1x::infinity(); }

@@ -121,14 +121,18 @@ std::shared_ptr<GpuKey> build_key(int algo, const uint8_t* b, size_t n) {
     ck(hipSetDevice(k->device), "hipSetDevice");
     ck(hipStreamCreateWithFlags(&k->stream, hipStreamNonBlocking), "hipStreamCreate");
     hipStream_t s = k->stream;
-    // compressed points: G1 alpha, beta1, delta1, K...; G2 beta, gamma, delta (, ped_g, ped_gsn)
+    // the key's points: G1 alpha, beta1, delta1, K...; G2 beta, gamma, delta (, ped_g, ped_gsn) — each compressed or raw, in slots of
+    // 64 / 128 bytes (a compressed point fills the first half of its slot, the rest stays zero)
     std::vector<uint8_t> g1, g2;
-    auto add = [&](std::vector<uint8_t>& v, size_t at, size_t len) { v.insert(v.end(), b + at, b + at + len); };
+    auto add = [&](std::vector<uint8_t>& v, size_t at, size_t cb) {
+        const size_t len = V::point_is_raw(b + at) ? 2 * cb : cb, o = v.size();
+        v.resize(o + 2 * cb, 0); memcpy(v.data() + o, b + at, len);
+    };
     add(g1, lay.alpha, 32); add(g1, lay.g1_beta, 32); add(g1, lay.g1_delta, 32);
     for (size_t at : lay.K) add(g1, at, 32);
     add(g2, lay.beta, 64); add(g2, lay.gamma, 64); add(g2, lay.delta, 64);
     if (lay.has_commitment) { add(g2, lay.ped_g, 64); add(g2, lay.ped_gsn, 64); }
-    const size_t n1 = g1.size() / 32, n2 = g2.size() / 64;
+    const size_t n1 = g1.size() / 64, n2 = g2.size() / 128;
     DevBuf<uint8_t> d1, d2; DevBuf<VP1> p1; DevBuf<VP2> p2; DevBuf<int8_t> st;
     d1.alloc(g1.size()); d2.alloc(g2.size()); p1.alloc(n1); p2.alloc(5); st.alloc(n1 + n2);
     ck(hipMemcpyAsync(d1.p, g1.data(), g1.size(), hipMemcpyHostToDevice, s), "copy");

@@ -24,8 +24,12 @@ extern void enforce_binding(void);
 /* libprove.go:20-23 -> impl.InitAlgorithm (prove_impl.go:65-114).
  * algorithmID: 0 chacha20, 1 aes-128-ctr, 2 aes-256-ctr (prove_impl.go:15-25).
  * provingKey / r1cs: the gnark v0.11.0 files written by keygen.go:341-352 (read only during the call).
- * Returns 1 on success or if the algorithm is already initialised, 0 on unknown id / parse failure
- * (message on stdout, as the reference prints it). */
+ * Key points are read as gnark's ReadFrom reads them, element by element: the two top bits of an element's first byte say whether it is
+ * compressed (10 / 11, 01 = infinity: what WriteTo writes) or raw (00: X | Y, what WriteRawTo writes; all-zero bytes = infinity), and one
+ * key may mix the two.  Every point must have canonical coordinates and lie on its curve, and every G2 point (G2.B, beta, delta) must
+ * lie in the subgroup of order r: a key gnark refuses with "subgroup check failed" is refused here.
+ * Returns 1 on success or if the algorithm is already initialised, 0 on unknown id / parse failure / a refused key
+ * (one line on stdout, as the reference prints it; nothing of the failed attempt stays allocated and a later call may succeed). */
 extern GoUint8 InitAlgorithm(GoUint8 algorithmID, GoSlice provingKey, GoSlice r1cs);
 
 /* libprove.go:25-28 — releases a buffer returned by Prove / ProveBatch (C free()). */
@@ -102,6 +106,14 @@ extern int gsc_debug_limb_ops(int field, int op, const int32_t *a, const int32_t
  * out: n affine results (zeros when there is none); flags: n bytes, bit 0 the result is infinity, bit 1 (op 2) ZZ was 0 mod p after the
  * first addition, bit 2 (op 2) ZZ was 0 mod p after the last one: then there is no result.  0 on success, -1 on error. */
 extern int gsc_debug_curve_ops(int group, int op, const uint8_t *pts, const uint8_t *inf, const uint8_t *lam, size_t n, size_t k, uint8_t *out, uint8_t *flags);
+
+/* TEST HOOK: decodes a slice of encoded key points exactly as InitAlgorithm does: the host walk over the elements (each compressed or
+ * raw by the flag bits of its first byte, see InitAlgorithm above) and the decode kernels, for G2 with the subgroup test [r]Q = O.
+ * Needs a device, no key.  group: 0 = G1, 1 = G2.  bytes / len: n encoded elements and nothing else (a slice that ends inside an
+ * element, or bytes left over: -1).  out_xy: n x 64 (G1: X | Y) or n x 128 (G2: X.A1 | X.A0 | Y.A1 | Y.A0) canonical big-endian bytes,
+ * zeros unless the status is 0.  status: n bytes, 0 a point of the group, 1 refused (a coordinate >= p, off the curve, a malformed
+ * infinity, G2: outside the subgroup), 2 the point at infinity.  0 on success, -1 on error. */
+extern int gsc_debug_decode_points(int group, const uint8_t *bytes, size_t len, size_t n, uint8_t *out_xy, uint8_t *status);
 
 /* TEST HOOK: one operation of the GPU verifier's arithmetic per element on RAW limbs: the Fp / Fp2 helpers, the Fp12 tower, the Miller steps
  * and the final exponentiation of csrc/verify_dev.hpp (path 0: one element per thread) and the Fp12 operations of its lane-sliced twin
@@ -186,7 +198,8 @@ extern int gsc_last_kernel_clock(GoUint8 algorithmID, float *clock_mhz, int *win
 /* ---- GPU verifier (k_verify.hip): verdicts identical to libverify.so's Verify, computed on the device ---- */
 /* Loads a verifying key (gnark VerifyingKey.WriteTo bytes, as InitVerifier takes) for the GPU verifier.  algorithmID: 0 chacha20,
  * 1 aes-128-ctr, 2 aes-256-ctr.  Needs no InitAlgorithm.  1 on success, 0 on a bad key (a point that does not decode, a beta / gamma /
- * delta outside G2, as libverify refuses it).  Loading again replaces the key.  Without a call, keys load on first use from
+ * delta outside G2, as libverify refuses it).  Each point of the key may be compressed or raw (WriteRawTo's X | Y, flag bits 00), as for
+ * InitAlgorithm; proofs stay compressed in their 196-byte slots.  Loading again replaces the key.  Without a call, keys load on first use from
  * GSC_VK_DIR (vk.chacha20, vk.aes128, vk.aes256), as libverify does.  Device: GSC_DEVICE, or the first of GSC_DEVICES. */
 extern int gsc_verify_init(GoUint8 algorithmID, GoSlice verifyingKey);
 /* n proofs of one algorithm.  proofs: n x 196-byte slots (gsc_prove_raw's layout), proof_lens[i] the length of proof i; signals:

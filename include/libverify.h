@@ -24,6 +24,9 @@ extern GoUint8 Verify(GoSlice params);
 /* Addition.  The reference embeds its three verifying keys at build time (verify_impl.go:24-31); this library loads them:
  * either explicitly (gnark VerifyingKey.WriteTo bytes) or, on first use, from the directory named by
  * the environment variable GSC_VK_DIR (files vk.chacha20, vk.aes128, vk.aes256 — the reference's generated/ folder).
+ * Each point of the key may be compressed (WriteTo) or raw (WriteRawTo: X | Y, flag bits 00 in its first byte; all-zero bytes = the
+ * point at infinity), as gnark's ReadFrom reads them; a raw point must have canonical coordinates and satisfy the curve equation, and
+ * a G2 point in either form must lie in the subgroup of order r.  Proofs are compressed only.
  * algorithmID: 0 chacha20, 1 aes-128-ctr, 2 aes-256-ctr.  Returns 1 on success. */
 extern GoUint8 InitVerifier(GoUint8 algorithmID, GoSlice verifyingKey);
 
