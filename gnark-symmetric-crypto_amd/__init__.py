@@ -24,7 +24,8 @@ EXPORTS = ["enforce_binding", "InitAlgorithm", "Free", "Prove", "ProveBatch", "g
            "gsc_verify_init", "gsc_verify_raw", "VerifyBatch", "gsc_debug_pairing",
            "gsc_verify_raw_batched", "gsc_verify_all", "VerifyAll", "gsc_debug_verify_randomizers",
            "gsc_verify_json", "gsc_verify_last_path", "gsc_debug_verify_path", "gsc_debug_pairing_few",
-           "gsc_verify_claims", "VerifyClaims"]
+           "gsc_verify_claims", "VerifyClaims",
+           "gsc_prove_check_init", "gsc_prove_check_stats", "gsc_debug_prove_corrupt"]
 
 
 class GoSlice(C.Structure):
@@ -110,6 +111,12 @@ def lib():
         L.gsc_verify_claims.argtypes = [C.c_ubyte, C.c_char_p, C.c_void_p, C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
         L.VerifyClaims.restype = ProveReturn
         L.VerifyClaims.argtypes = [GoSlice]
+        L.gsc_prove_check_init.restype = C.c_int
+        L.gsc_prove_check_init.argtypes = [C.c_ubyte, GoSlice]
+        L.gsc_prove_check_stats.restype = C.c_int
+        L.gsc_prove_check_stats.argtypes = [C.c_ubyte, C.POINTER(C.c_uint64)]
+        L.gsc_debug_prove_corrupt.restype = C.c_int
+        L.gsc_debug_prove_corrupt.argtypes = [C.c_ubyte, C.c_uint32, C.c_int, C.c_int]
         L.enforce_binding()
         _lib = L
     return _lib
@@ -593,6 +600,35 @@ def debug_pairing(g1_points, g2_points, few: bool = False):
     if (lib().gsc_debug_pairing_few if few else lib().gsc_debug_pairing)(b1, b2, n, out) != n:
         raise RuntimeError("gsc_debug_pairing failed (test hooks off?)")
     return [tuple(int.from_bytes(out.raw[384 * i + 32 * c:384 * i + 32 * c + 32], "big") for c in range(12)) for i in range(n)]
+
+
+# ---- the prover's self-check ----
+def prove_check_init(algorithm_id: int, verifying_key: bytes = b"") -> int:
+    """gsc_prove_check_init: from now on every chunk of the algorithm is verified on the device under this key (gnark VerifyingKey.WriteTo
+    bytes) before its proofs are released.  1 on; 0 key refused (the state stays as it was); -1 algorithm not initialised.  Empty bytes: off (1)."""
+    if not verifying_key:
+        return lib().gsc_prove_check_init(algorithm_id, GoSlice(None, 0, 0))
+    s, keep = _slice(verifying_key)
+    return lib().gsc_prove_check_init(algorithm_id, s)
+
+
+def prove_check_stats(algorithm_id: int):
+    """gsc_prove_check_stats: (chunks checked, proofs checked, proofs refused by the check, chunks that needed the proof-by-proof pass); all 0
+    while the check is off; None when the algorithm is not initialised."""
+    out = (C.c_uint64 * 4)()
+    if lib().gsc_prove_check_stats(algorithm_id, out) != 0:
+        return None
+    return tuple(int(v) for v in out)
+
+
+PROOF_POINTS = {"A": 0, "B": 1, "C": 2, "D": 3, "PoK": 4}
+
+
+def debug_prove_corrupt(algorithm_id: int, index: int, which, mode: int = 0) -> int:
+    """TEST HOOK: arms a one-shot change to statement `index` of the algorithm's next chunk, on the device in front of the self-check and the
+    download.  which: "A", "B", "C", "D", "PoK" (or 0..4); mode 0: the same point of statement (index + 1) mod n, mode 1: bit 0 of its y
+    flipped.  Returns 0, -1 when hooks are off / the algorithm is not initialised / the proofs have no such point."""
+    return lib().gsc_debug_prove_corrupt(algorithm_id, index, PROOF_POINTS.get(which, which), mode)
 
 
 # ---- libverify (CPU-side, libraries/verifier/libverify.go:14-17) ----

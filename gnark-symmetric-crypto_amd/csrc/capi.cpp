@@ -312,8 +312,21 @@ GoUint8 InitAlgorithm(GoUint8 algorithmID, GoSlice provingKey, GoSlice r1cs) {
     if (g_algo[algorithmID]) return 1;                           // already initialised (prove_impl.go:74-76)
     try {
         if (!provingKey.data || provingKey.len <= 0 || !r1cs.data || r1cs.len <= 0) throw std::runtime_error("error reading proving key: EOF");
-        g_algo[algorithmID].reset(new Algorithm((Cipher)algorithmID, (const uint8_t*)provingKey.data, (size_t)provingKey.len,
-                                                (const uint8_t*)r1cs.data, (size_t)r1cs.len, config_from_env()));
+        const EngineConfig cfg = config_from_env();
+        std::unique_ptr<Algorithm> algo(new Algorithm((Cipher)algorithmID, (const uint8_t*)provingKey.data, (size_t)provingKey.len, (const uint8_t*)r1cs.data, (size_t)r1cs.len, cfg));
+        if (cfg.prove_check) {      // GSC_PROVE_CHECK=1: the self-check under the verifying key of GSC_VK_DIR, or no algorithm at all
+            static const char* const files[3] = {"vk.chacha20", "vk.aes128", "vk.aes256"};
+            const std::string path = cfg.vk_dir + "/" + files[algorithmID];
+            std::vector<uint8_t> vk;
+            if (FILE* f = cfg.vk_dir.empty() ? nullptr : fopen(path.c_str(), "rb")) {
+                uint8_t buf[4096]; size_t got;
+                while ((got = fread(buf, 1, sizeof buf, f)) > 0) vk.insert(vk.end(), buf, buf + got);
+                fclose(f);
+            }
+            if (vk.empty()) throw std::runtime_error("GSC_PROVE_CHECK=1: cannot read " + (cfg.vk_dir.empty() ? std::string("a verifying key: GSC_VK_DIR is not set") : path));
+            if (!algo->prove_check_init(vk.data(), vk.size())) throw std::runtime_error("GSC_PROVE_CHECK=1: " + path + " refused");
+        }
+        g_algo[algorithmID] = std::move(algo);
         g_batcher[algorithmID].reset(new Batcher(g_algo[algorithmID].get()));
         return 1;
     } catch (const std::exception& e) {
@@ -405,6 +418,29 @@ long long gsc_prove_raw(GoUint8 cipher, const uint8_t* inputs, size_t n, uint8_t
         }
         return good;
     } catch (const std::exception& e) { printf("%s\n", e.what()); return -1; }
+}
+
+int gsc_prove_check_init(GoUint8 algorithmID, GoSlice verifyingKey) {
+    if (algorithmID > 2) return -1;
+    Algorithm* a = lookup(algorithmID);
+    if (!a) return -1;
+    try {
+        if (!verifyingKey.data || verifyingKey.len <= 0) { a->prove_check_off(); return 1; }
+        return a->prove_check_init((const uint8_t*)verifyingKey.data, (size_t)verifyingKey.len) ? 1 : 0;
+    } catch (const std::exception& e) { printf("gsc_prove_check_init: %s\n", e.what()); return 0; }
+}
+int gsc_prove_check_stats(GoUint8 algorithmID, uint64_t out[4]) {
+    if (algorithmID > 2 || !out) return -1;
+    Algorithm* a = lookup(algorithmID);
+    if (!a) return -1;
+    a->prove_check_stats(out);
+    return 0;
+}
+int gsc_debug_prove_corrupt(GoUint8 algorithmID, uint32_t index, int which, int mode) {
+    if (hooks_refused("gsc_debug_prove_corrupt") || algorithmID > 2) return -1;
+    Algorithm* a = lookup(algorithmID);
+    if (!a) return -1;
+    return a->debug_prove_corrupt(index, which, mode) ? 0 : -1;
 }
 
 int gsc_setup(GoSlice r1cs, const uint8_t* seed32, void** pk, size_t* pk_len, void** vk, size_t* vk_len) {

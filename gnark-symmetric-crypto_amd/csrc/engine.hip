@@ -63,6 +63,8 @@ EngineConfig config_from_env() {
     if (c.small_witness < 0 || c.small_witness > 2 || (c.small_witness == 2 && !test_hooks_enabled())) throw std::runtime_error("GSC_SMALL_WITNESS must be 0 or 1");
     if (c.few_workgroups < 0 || c.few_workgroups > 256) throw std::runtime_error("GSC_FEW_WGS must be in [0, 256]");
     c.trace_host = getenv("GSC_TRACE_HOST") != nullptr;
+    c.prove_check = env_int("GSC_PROVE_CHECK", 0) != 0;
+    if (const char* d = getenv("GSC_VK_DIR")) c.vk_dir = d;
     if (test_hooks_enabled()) { c.solver_trace = getenv("GSC_SOLVER_TRACE") != nullptr; c.few_test_abort = getenv("GSC_FEW_TEST_ABORT") != nullptr; c.keep_secrets = getenv("GSC_KEEP_SECRETS") != nullptr; c.wipe_full = env_int("GSC_WIPE", 1) != 0; c.fail_after_stage = env_int("GSC_FAIL_AFTER_STAGE", 0); c.wipe_grid = env_int("GSC_WIPE_GRID", 0); if (c.wipe_grid < 0 || c.wipe_grid > 65536) throw std::runtime_error("GSC_WIPE_GRID must be in [0, 65536]"); c.z_exp_entry_bits = env_int("GSC_Z_EXP_ENTRY_BITS", 0); }
     if (c.max_batch < 64) c.max_batch = 64;
     c.max_batch = (c.max_batch + 63) / 64 * 64;
@@ -269,7 +271,28 @@ Algorithm::Algorithm(Cipher cipher, const uint8_t* pk, size_t pk_len, const uint
     make(0);
     for (auto& t : th) t.join();
     if (err) { impls_.clear(); std::rethrow_exception(err); }
+    for (auto& i : impls_) i->corrupt = &corrupt_;
     picker_.reset(new ReplicaPicker(impls_.size()));
+}
+bool Algorithm::prove_check_init(const uint8_t* vk, size_t len) {
+    // every replica's context first (its device, its largest lane), then all of them in: a refused key changes nothing
+    std::vector<std::shared_ptr<ProveCheckCtx>> ctx;
+    for (auto& i : impls_) {
+        ctx.push_back(prove_check_create((int)i->cipher, vk, len, i->cfg.device, i->cap));
+        if (!ctx.back()) return false;
+    }
+    for (size_t k = 0; k < impls_.size(); k++) { std::lock_guard<std::mutex> l(impls_[k]->check_mu); impls_[k]->check = ctx[k]; }
+    return true;
+}
+void Algorithm::prove_check_off() { for (auto& i : impls_) { std::lock_guard<std::mutex> l(i->check_mu); i->check.reset(); } }
+void Algorithm::prove_check_stats(uint64_t out[4]) const {
+    for (int k = 0; k < 4; k++) out[k] = 0;
+    for (auto& i : impls_) if (auto c = i->check_now()) prove_check_add_stats(*c, out);
+}
+bool Algorithm::debug_prove_corrupt(uint32_t index, int which, int mode) {
+    if (which < 0 || which > 4 || mode < 0 || mode > 1 || (which > 2 && !impls_[0]->has_commitment)) return false;
+    corrupt_.store((uint64_t)1 << 63 | (uint64_t)mode << 40 | (uint64_t)which << 32 | index);
+    return true;
 }
 Algorithm::~Algorithm() = default;
 Cipher Algorithm::cipher() const { return impls_[0]->cipher; }
@@ -298,6 +321,11 @@ std::string Algorithm::describe() const {
     if (impl_->quotient_eval) out += " Qtiles=" + std::to_string(quot_live_tiles(impl_->L, impl_->quot_live)) + "/" + std::to_string(1u << (impl_->L - (impl_->L + 1) / 2));      // tiles the last quotient kernel runs
     out += impl_->small.ok ? " witness=small-integer(" + std::to_string(impl_->small.n_levels) + " chained levels, fallbacks " + std::to_string(impl_->small_fallbacks.load()) + ")" : " witness=generic" + (impl_->small.why.empty() ? std::string() : "(" + impl_->small.why + ")");
     out += impl_->cfg.keep_secrets ? " wipe=off" : impl_->cfg.wipe_full ? " wipe=full" : " wipe=inputs";
+    {   // the self-check: off, or on with the device memory its contexts take (all replicas)
+        size_t bytes = 0; bool on = false;
+        for (auto& i : impls_) if (auto c = i->check_now()) { on = true; bytes += prove_check_device_bytes(*c); }
+        out += on ? " check=on(" + std::to_string(bytes) + ")" : " check=off";
+    }
     out += " served(calls/statements)=";
     const auto sv = picker_->served();
     for (size_t i = 0; i < sv.size(); i++) out += (i ? "," : "") + std::to_string(sv[i].calls) + "/" + std::to_string(sv[i].statements);

@@ -26,7 +26,7 @@ struct ProofRequest {
     ~ProofRequest() { explicit_bzero(this, sizeof *this); }
 };
 struct ProofResult {
-    int status = 0;                  // 0 ok; 1 unsatisfied constraint system; 2 degenerate point
+    int status = 0;                  // 0 ok; 1 unsatisfied constraint system; 2 degenerate point; 3 refused by the self-check (gsc_prove_check_init)
     uint8_t proof[196]; size_t proof_len = 0;   // gnark proof.WriteTo bytes
 };
 
@@ -67,6 +67,8 @@ struct EngineConfig {
     int stream_priorities = 1;   // GSC_STREAM_PRIORITIES: a lane's three streams at three priority levels = in three pools of hardware queues (alloc_lane); 0 = plain streams
     int small_witness_few = 1;   // GSC_SMALL_WITNESS_FEW: calls on the latency path take it too (one workgroup walks the levels: no device-wide barriers); 0 = they keep the resident lanes-are-terms solver
     int win_slice = 256;         // GSC_WIN_SLICE (test hooks): bases per slice of the windowed MSM kernel at full batches
+    bool prove_check = false;    // GSC_PROVE_CHECK=1: InitAlgorithm also loads the algorithm's verifying key from vk_dir and turns the self-check on (gsc_prove_check_init)
+    std::string vk_dir;          // GSC_VK_DIR as it stood then (vk.chacha20, vk.aes128, vk.aes256, as the verifier reads them)
     bool trace_host = false;     // GSC_TRACE_HOST: host-side timing lines on stderr (InitAlgorithm breakdown, per-chunk enqueue / wait / serialise)
     // diagnostics that change what the device does: honoured only when the test hooks were enabled at load time (test_hooks_enabled())
     bool solver_trace = false;   // GSC_SOLVER_TRACE: per-level clock stamps of the witness kernels
@@ -130,7 +132,15 @@ class Algorithm {
     // TEST HOOK: bytes off the idle image in EVERY secret region of every lane over its whole allocation, all replicas (after draining the lanes);
     // report: "lane<i>.<name>=<bytes>" for the regions that are not clean, then "registered=<bytes> allocated=<bytes> public=<names>"
     size_t debug_secret_scan(std::string& report);
+    // The self-check (include/libprove.h gsc_prove_check_init): one context per replica under the gnark VerifyingKey.WriteTo bytes; false (the
+    // state stays as it was) for a key the verifier would refuse.  Chunks enqueued from then on are checked under this key.  Throws on a HIP error.
+    bool prove_check_init(const uint8_t* vk, size_t len);
+    void prove_check_off();                              // frees the contexts (a chunk in flight keeps its own until it is through)
+    void prove_check_stats(uint64_t out[4]) const;      // summed over the replicas; zeros while the check is off
+    // TEST HOOK (gsc_debug_prove_corrupt): arms a one-shot change to statement `index` of the next chunk; false for a point the algorithm's proofs do not have
+    bool debug_prove_corrupt(uint32_t index, int which, int mode);
   private:
+    std::atomic<uint64_t> corrupt_{0};                       // the armed change, shared by the replicas (AlgorithmImpl::corrupt)
     std::vector<std::unique_ptr<AlgorithmImpl>> impls_;      // one per device
     std::unique_ptr<class ReplicaPicker> picker_;            // dispatch.hpp: least-loaded replica for calls that are not split
     mutable std::atomic<size_t> last_replica_{0};            // the replica whose chunk finished last (last_kernel_stat)

@@ -9,6 +9,7 @@
 #include "kernels.hpp"
 #include "wit_small.hpp"
 #include "wipe_plan.hpp"
+#include "prove_check.hpp"
 #include <atomic>
 #include <chrono>
 #include <cstring>
@@ -115,6 +116,12 @@ class AlgorithmImpl {
     // instead of spinning through the same timeouts; the penalty doubles up to 4096 calls and is forgotten after a success.
     std::atomic<uint32_t> few_skip{0}; std::atomic<uint32_t> few_penalty{16};
     std::mutex stat_mu; KernelStat last_stat;      // timing of the chunk that finished last on this replica
+    // The self-check (prove_check.hpp): this replica's context, or none while the check is off.  A chunk takes the pointer when it starts and is
+    // checked under that key, whatever is loaded meanwhile; the context's buffers are no part of any lane (public data only, never wiped).
+    std::mutex check_mu; std::shared_ptr<ProveCheckCtx> check;
+    std::shared_ptr<ProveCheckCtx> check_now() { std::lock_guard<std::mutex> l(check_mu); return check; }
+    // TEST HOOK: the one-shot change gsc_debug_prove_corrupt armed (Algorithm's word: 1 << 63 | mode << 40 | which << 32 | index; 0: none)
+    std::atomic<uint64_t>* corrupt = nullptr;
     void release_lane(size_t i) { { std::lock_guard<std::mutex> l(pool_mu); lane_busy[i] = 0; } pool_cv.notify_all(); }
     hipStream_t stream = nullptr;   // init-time work; proving runs on the lanes' streams
     size_t table_bytes = 0;
@@ -271,6 +278,10 @@ class AlgorithmImpl {
     struct Chunk {
         const ProofRequest* reqs; size_t n, B; DebugVectors* dbg; ChunkRoute rt;
         std::chrono::steady_clock::time_point t_start, t_enqueued, t_done;      // host clock: entry, everything enqueued, results back (GSC_TRACE_HOST)
+        std::shared_ptr<ProveCheckCtx> check = nullptr;      // the self-check context loaded when the chunk started (none: not checked)
+        uint64_t corrupt = 0;                                // TEST HOOK: the armed change this chunk took (AlgorithmImpl::corrupt)
+        std::vector<uint8_t> verdict = {};                   // with check: one byte per statement, 0 = not to be released
+        bool check_fell_back = false;
     };
     size_t WIN_SLICE = 256;      // bases per slice of the windowed kernel at full batches (measured 64 .. 512: kernel time within 1 %)
     struct MsmCtx { hipStream_t stream; uint4* digits; uint8_t* gok; const int8_t* plane = nullptr; size_t plane_rows = 0, plane_stride = 0; };      // plane: the scalars' byte plane (small-integer witness path)
@@ -322,6 +333,8 @@ class AlgorithmImpl {
 
     // allow_few_solver / allow_small = false: the retries after the resident solver gave up / a small-integer prediction failed
     void prove_chunk(Lane& ln, const ProofRequest* reqs, size_t n, ProofResult* results, DebugVectors* dbg, bool allow_few_solver = true, bool allow_small = true);
+    // the self-check of the chunk, from stage_assembly: enqueued on the lane's stream behind k_fin_combine; the pass is finished behind the lane's wait
+    std::unique_ptr<ProveCheckPass> check_enqueue(Lane& ln, const Chunk& ck);
     // its stages, in this order; each enqueues on the lane's streams up to the stage event named (Lane::ev)
     void stage_upload(Lane& ln, const Chunk& ck);           // staging, the scalar split of a latency call: ev[0]
     void stage_witness(Lane& ln, const Chunk& ck);          // W, a, b, c (and the commitment in between): ev[1]
@@ -336,7 +349,8 @@ class AlgorithmImpl {
     void trace_chunk(Lane& ln, const Chunk& ck);            // GSC_TRACE_HOST
 
     // gnark proof.WriteTo: Ar | Bs | Krs compressed, u32be nbCommitments, commitments, CommitmentPok
-    void serialize(const uint8_t* o, uint8_t flags, uint32_t status, const uint8_t* commitment_xy, const uint8_t* pok_xy, ProofResult& res) const;
+    // released = false: the self-check did not accept the statement's points (status 3, no bytes)
+    void serialize(const uint8_t* o, uint8_t flags, uint32_t status, const uint8_t* commitment_xy, const uint8_t* pok_xy, ProofResult& res, bool released = true) const;
 };
 
 }  // namespace gsc

@@ -4,6 +4,7 @@
 // libraries/prover/impl/provers.go:148-157, :216-226.
 #include "engine_impl.hpp"
 #include "glv.hpp"
+#include "prove_check_kernels.hpp"
 #include <chrono>
 #include <cstdio>
 #include <cstring>
@@ -465,6 +466,11 @@ void AlgorithmImpl::stage_assembly(Lane& ln, Chunk& ck) {
     launch_fin_combine(ln.d_sumB2.p, ln.d_sumK.p, ln.d_sumZ.p, rt.eval ? ln.d_sumC.p : nullptr, ln.d_tmp.p, B, ln.d_out.p, ln.d_flags.p, ln.stream);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipEventRecord(ln.ev[4], ln.stream));
+    if (ck.corrupt) {      // TEST HOOK: behind the last writer of the proof's points, in front of the check and the download
+        launch_prove_corrupt(ln.d_out.p, ln.d_cpts.p, B, ck.n, (uint32_t)ck.corrupt, (int)((ck.corrupt >> 32) & 0xFF), (int)((ck.corrupt >> 40) & 0xFF), ln.stream);
+        HIP_CHECK(hipGetLastError());
+    }
+    const std::unique_ptr<ProveCheckPass> pass = ck.check ? check_enqueue(ln, ck) : nullptr;
     HIP_CHECK(hipMemcpyAsync(ln.h_out.p, ln.d_out.p, 256 * B, hipMemcpyDeviceToHost, ln.stream));
     HIP_CHECK(hipMemcpyAsync(ln.h_flags.p, ln.d_flags.p, (B + 3) / 4 * 4, hipMemcpyDeviceToHost, ln.stream));
     HIP_CHECK(hipMemcpyAsync(ln.h_status.p, ln.d_status.p, B * 4, hipMemcpyDeviceToHost, ln.stream));
@@ -476,7 +482,28 @@ void AlgorithmImpl::stage_assembly(Lane& ln, Chunk& ck) {
     if (!rt.latency) { HIP_CHECK(hipMemcpyAsync(ln.h_clk(), ln.d_clk.p, (cfg.trace_host ? 44 : 32) * 8, hipMemcpyDeviceToHost, ln.stream)); HIP_CHECK(hipMemsetAsync(ln.d_clk.p, 0, 32 * 8, ln.stream)); }
     ck.t_enqueued = std::chrono::steady_clock::now();
     HIP_CHECK(hipStreamSynchronize(ln.stream));
+    if (pass) {
+        ck.verdict = pass->finish(ln.h_status.p, ln.h_flags.p); ck.check_fell_back = pass->fell_back();
+        // a chunk that is proved again (prove_chunk) is counted when it comes through here for the last time; what counts is what would have been released
+        if (!ln.h_fsync()[1] && !ln.h_wsflag()) {
+            size_t checked = 0, refused = 0;
+            for (size_t i = 0; i < ck.n; i++) if (ln.h_status.p[i] == 0xFFFFFFFFu && !ln.h_flags.p[i]) { checked++; refused += !ck.verdict[i]; }
+            pass->count(checked, refused);
+        }
+    }
     ck.t_done = std::chrono::steady_clock::now();
+}
+
+std::unique_ptr<ProveCheckPass> AlgorithmImpl::check_enqueue(Lane& ln, const Chunk& ck) {
+    // the public signals as the caller's verifier builds them: the host's own ciphertext and the request, never the witness
+    std::vector<uint8_t> sig(144 * ck.n);
+    for (size_t i = 0; i < ck.n; i++) {
+        const ProofRequest& q = ck.reqs[i]; uint8_t* o = sig.data() + 144 * i;
+        memcpy(o, q.ciphertext, 64); memcpy(o + 64, q.nonce, 12);
+        for (int b = 0; b < 4; b++) o[76 + b] = (uint8_t)(q.counter >> (8 * (cipher == CHACHA20 ? b : 3 - b)));      // little-endian for ChaCha20, big-endian for AES (verifiers.go)
+        memcpy(o + 80, q.plaintext, 64);
+    }
+    return std::make_unique<ProveCheckPass>(ck.check, ProveCheckInput{ln.d_out.p, ln.d_cpts.p, ln.d_status.p, ln.d_flags.p, ck.B, ck.n, sig.data()}, ln.stream);
 }
 
 void AlgorithmImpl::stage_stat(Lane& ln, const Chunk& ck) {
@@ -541,6 +568,8 @@ void AlgorithmImpl::prove_chunk(Lane& ln, const ProofRequest* reqs, size_t n, Pr
         if (k) { call.skip_resident = true; ck.rt = chunk_route(n, cfg, route_facts(), call); }
     }
     ln.small_active = ck.rt.small;
+    ck.check = check_now();      // the key loaded now checks this chunk, whatever is loaded while it runs
+    if (corrupt) ck.corrupt = corrupt->exchange(0);
     stage_upload(ln, ck); fail_after(1);
     stage_witness(ln, ck); fail_after(2);
     stage_early_sums(ln, ck); fail_after(3);
@@ -552,24 +581,27 @@ void AlgorithmImpl::prove_chunk(Lane& ln, const ProofRequest* reqs, size_t n, Pr
         if (!warned.exchange(true)) fprintf(stderr, "libprove: the resident witness kernel could not hold the device (shared with another process?); solving level by level\n");
         const uint32_t pen = few_penalty.load();
         few_skip.store(pen); few_penalty.store(pen < 4096 ? pen * 2 : 4096);
+        if (ck.corrupt) corrupt->store(ck.corrupt);      // (the chunk is proved again: the armed change is for the attempt that counts)
         return prove_chunk(ln, reqs, n, results, dbg, false, allow_small);
     }
     if (ln.h_wsflag()) {      // a value did not fit the byte plane it was predicted for: the whole chunk again with the generic solver (results never depend on predictions)
         small_fallbacks++;
+        if (ck.corrupt) corrupt->store(ck.corrupt);
         return prove_chunk(ln, reqs, n, results, dbg, allow_few_solver, false);
     }
     if (ck.rt.resident) few_penalty.store(16);
     stage_stat(ln, ck);
     const uint8_t* const h_cpts = ln.h_cpts.p;
     for (size_t i = 0; i < n; i++)
-        serialize(ln.h_out.p + 256 * i, ln.h_flags.p[i], ln.h_status.p[i], has_commitment ? h_cpts + 64 * i : nullptr, has_commitment ? h_cpts + 64 * B + 64 * i : nullptr, results[i]);
+        serialize(ln.h_out.p + 256 * i, ln.h_flags.p[i], ln.h_status.p[i], has_commitment ? h_cpts + 64 * i : nullptr, has_commitment ? h_cpts + 64 * B + 64 * i : nullptr, results[i], !ck.check || ck.verdict[i] != 0);
     if (cfg.trace_host) trace_chunk(ln, ck);
 }
 
-void AlgorithmImpl::serialize(const uint8_t* o, uint8_t flags, uint32_t status, const uint8_t* commitment_xy, const uint8_t* pok_xy, ProofResult& res) const {
+void AlgorithmImpl::serialize(const uint8_t* o, uint8_t flags, uint32_t status, const uint8_t* commitment_xy, const uint8_t* pok_xy, ProofResult& res, bool released) const {
     res.proof_len = 0; res.status = 0;
     if (status != 0xFFFFFFFFu) { res.status = 1; return; }
     if (flags) { res.status = 2; return; }
+    if (!released) { res.status = 3; return; }
     uint8_t* p = res.proof;
     auto g1 = [&](const uint8_t* xy, uint8_t* dst) {
         uint8_t y[32]; le_limbs_to_be(xy, dst); le_limbs_to_be(xy + 32, y);

@@ -155,6 +155,15 @@ DEVNOINL bool sqrt2(const e2& a, e2& out) {
 }
 
 // ---- gnark-crypto compressed points, as strict as libverify's g1_decode / g2_decode ----
+// canonical value as eight little-endian 32-bit words -> Montgomery limbs; false when >= p
+DEVFN bool fp_from_words(const fe& w, e1& out) {
+    constexpr uint32_t P[8] = {0xd87cfd47u, 0x3c208c16u, 0x6871ca8du, 0x97816a91u, 0x8181585du, 0xb85045b6u, 0xe131a029u, 0x30644e72u};
+    bool lt = false, decided = false;
+    for (int i = 7; i >= 0; i--) if (!decided && w.l[i] != P[i]) { lt = w.l[i] < P[i]; decided = true; }
+    if (!lt) return false;
+    out = F::to_mont(F::unpack(w));
+    return true;
+}
 // big-endian 32 bytes (top two bits cleared when `mask`) -> canonical limbs; false when >= p
 DEVFN bool fp_from_be(const uint8_t* b, bool mask, e1& out) {
     fe w;
@@ -165,13 +174,11 @@ DEVFN bool fp_from_be(const uint8_t* b, bool mask, e1& out) {
         if (mask && i == 7) b0 &= 0x3F;
         w.l[i] = (b0 << 24) | ((uint32_t)q[1] << 16) | ((uint32_t)q[2] << 8) | q[3];
     }
-    constexpr uint32_t P[8] = {0xd87cfd47u, 0x3c208c16u, 0x6871ca8du, 0x97816a91u, 0x8181585du, 0xb85045b6u, 0xe131a029u, 0x30644e72u};
-    bool lt = false, decided = false;
-    for (int i = 7; i >= 0; i--) if (!decided && w.l[i] != P[i]) { lt = w.l[i] < P[i]; decided = true; }
-    if (!lt) return false;
-    out = F::to_mont(F::unpack(w));
-    return true;
+    return fp_from_words(w, out);
 }
+// the limbs fp_from_words gives for the value of a: a decoded point is then the same words whichever encoding it came in (a square root's
+// limbs are one of several images of its value)
+DEVFN e1 canon1(const e1& a) { return F::to_mont(F::unpack(F::pack(F::from_mont(a)))); }
 // 0: finite point, 1: infinity, -1: rejected
 DEVFN int decode_g1(const uint8_t* b, VP1& p) {
     const uint8_t flag = b[0] & 0xC0;
@@ -186,7 +193,7 @@ DEVFN int decode_g1(const uint8_t* b, VP1& p) {
     if (!fp_from_be(b, true, x)) return -1;
     if (!sqrt1(red(F::add(F::mul(F::sqr(x), x), three1())), y)) return -1;
     if ((flag == 0xC0) != lex_large1(y)) y = neg1(y);
-    p.x = x; p.y = y; p.inf = 0;
+    p.x = x; p.y = canon1(y); p.inf = 0;
     return 0;
 }
 DEVFN int decode_g2_curve(const uint8_t* b, VP2& p) {      // without the subgroup test
@@ -202,7 +209,7 @@ DEVFN int decode_g2_curve(const uint8_t* b, VP2& p) {      // without the subgro
     if (!fp_from_be(b, true, x.a1) || !fp_from_be(b + 32, false, x.a0)) return -1;
     if (!sqrt2(add2(mul2(sqr2(x), x), twist_b()), y)) return -1;
     if ((flag == 0xC0) != lex_large2(y)) y = neg2(y);
-    p.x = x; p.y = y; p.inf = 0;
+    p.x = x; p.y = e2{canon1(y.a0), canon1(y.a1)}; p.inf = 0;
     return 0;
 }
 // [r] Q == O: the plain test libverify uses (double-and-add over the bits of r, exact XYZZ formulas)
@@ -541,16 +548,11 @@ struct KeyDev {
 };
 struct ProofDev { VP1 A, C, L, D, pok; VP2 B; int32_t ok; };
 constexpr int kProofSlot = 196;
-// strict decoding of A, B (with the subgroup test), C (and D, PoK) and L = K0 + sum of window entries (+ c K[npub+1] + D)
-DEVFN void prep_one(const KeyDev& k, const uint8_t* proof, const uint8_t* win, ProofDev& out) {
-    out.ok = 0;
-    if (!k.fits) return;
-    if (decode_g1(proof, out.A) < 0 || decode_g2(proof + 32, out.B) < 0 || decode_g1(proof + 96, out.C) < 0) return;
-    // the proof of knowledge follows the commitments; libverify decodes it (and refuses a bad encoding) even without a commitment
-    if (decode_g1(proof + (k.has_commitment ? 164 : 132), out.pok) < 0) return;
+// What follows the decode of a proof's points, whichever form they came in (prep_one, prep_affine_one): L = K0 + sum of window entries
+// (+ c K[npub+1] + D with the challenge c of the decoded D)
+DEVFN void prep_finish(const KeyDev& k, const uint8_t* win, ProofDev& out) {
     G1X acc = lsum(k.k0, k.table, win, kWindows);
     if (k.has_commitment) {
-        if (decode_g1(proof + 132, out.D) < 0) return;
         uint8_t c[32];
         commitment_challenge(out.D, c);
         for (int j = 0; j < kCommitWindows; j++) acc = g1_madd(acc, k.ctable[256 * j + c[j]]);
@@ -558,6 +560,59 @@ DEVFN void prep_one(const KeyDev& k, const uint8_t* proof, const uint8_t* win, P
     }
     out.L = g1_affine(acc);
     out.ok = 1;
+}
+// strict decoding of A, B (with the subgroup test), C (and D, PoK), then prep_finish
+DEVFN void prep_one(const KeyDev& k, const uint8_t* proof, const uint8_t* win, ProofDev& out) {
+    out.ok = 0;
+    if (!k.fits) return;
+    if (decode_g1(proof, out.A) < 0 || decode_g2(proof + 32, out.B) < 0 || decode_g1(proof + 96, out.C) < 0) return;
+    // the proof of knowledge follows the commitments; libverify decodes it (and refuses a bad encoding) even without a commitment
+    if (decode_g1(proof + (k.has_commitment ? 164 : 132), out.pok) < 0) return;
+    if (k.has_commitment && decode_g1(proof + 132, out.D) < 0) return;
+    prep_finish(k, win, out);
+}
+// ---- the prover's own output, before it is compressed (k_prove_check.hip) ----
+// A finite affine point as the prover leaves it: canonical coordinates (< p) that satisfy the curve equation exactly, no square root.  Such a
+// point is what decode_g1 / decode_g2_curve return for its compressed encoding (the encoding keeps x and the sign of y, and the curve has one
+// y of that sign for x), and a point off the curve is not: its encoding decodes to another point or to none.  So accepting these points is
+// accepting the bytes serialisation will write.
+DEVFN bool affine_g1(const fe& xw, const fe& yw, VP1& p) {
+    p.x = F::zero(); p.y = F::zero(); p.inf = 1;
+    e1 x, y;
+    if (!fp_from_words(xw, x) || !fp_from_words(yw, y)) return false;
+    if (!eq1(F::sqr(y), red(F::add(F::mul(F::sqr(x), x), three1())))) return false;
+    p.x = x; p.y = y; p.inf = 0;
+    return true;
+}
+DEVFN bool affine_g2_curve(const fe& x0, const fe& x1, const fe& y0, const fe& y1, VP2& p) {      // without the subgroup test
+    p.x = F2::zero(); p.y = F2::zero(); p.inf = 1;
+    e2 x, y;
+    if (!fp_from_words(x0, x.a0) || !fp_from_words(x1, x.a1) || !fp_from_words(y0, y.a0) || !fp_from_words(y1, y.a1)) return false;
+    if (!eq2(sqr2(y), add2(mul2(sqr2(x), x), twist_b()))) return false;
+    p.x = x; p.y = y; p.inf = 0;
+    return true;
+}
+DEVFN fe words_le(const uint8_t* b) { fe w;      // eight little-endian words (the layout of Lane::d_out)
+#pragma unroll
+    for (int i = 0; i < 8; i++) w.l[i] = (uint32_t)b[4 * i] | ((uint32_t)b[4 * i + 1] << 8) | ((uint32_t)b[4 * i + 2] << 16) | ((uint32_t)b[4 * i + 3] << 24);
+    return w; }
+DEVFN fe words_be(const uint8_t* b) { fe w;      // 32 big-endian bytes (the layout points_to_affine_be leaves)
+#pragma unroll
+    for (int i = 0; i < 8; i++) { const uint8_t* q = b + 28 - 4 * i; w.l[i] = ((uint32_t)q[0] << 24) | ((uint32_t)q[1] << 16) | ((uint32_t)q[2] << 8) | q[3]; }
+    return w; }
+// prep_one's twin on the prover's buffers.  abc: 256 bytes, eight canonical little-endian words per coordinate: A.x A.y | B.x.a0 B.x.a1 B.y.a0
+// B.y.a1 | C.x C.y.  d_be, pok_be: X | Y as 64 big-endian bytes each (read only for a key with a commitment; without one the proof of
+// knowledge is the point at infinity, as the proof bytes say).  The caller has excluded the statements whose infinity flags are set.
+DEVFN void prep_affine_one(const KeyDev& k, const uint8_t* abc, const uint8_t* d_be, const uint8_t* pok_be, const uint8_t* win, ProofDev& out) {
+    out.ok = 0;
+    if (!k.fits) return;
+    if (!affine_g1(words_le(abc), words_le(abc + 32), out.A)) return;
+    if (!affine_g2_curve(words_le(abc + 64), words_le(abc + 96), words_le(abc + 128), words_le(abc + 160), out.B) || !g2_in_subgroup(out.B)) return;
+    if (!affine_g1(words_le(abc + 192), words_le(abc + 224), out.C)) return;
+    if (k.has_commitment) {
+        if (!affine_g1(words_be(pok_be), words_be(pok_be + 32), out.pok) || !affine_g1(words_be(d_be), words_be(d_be + 32), out.D)) return;
+    } else { out.pok.x = F::zero(); out.pok.y = F::zero(); out.pok.inf = 1; }
+    prep_finish(k, win, out);
 }
 DEVFN VP1 neg_p(const VP1& p) { VP1 r = p; r.y = neg1(p.y); return r; }
 // pass 0 (keys with a commitment): e(D, ped_gsn) e(PoK, ped_g) == 1; pass 1: e(A, B) e(-alpha, beta) e(-L, gamma) e(-C, delta) == 1.

@@ -5,6 +5,8 @@
 // (GSC_DEVICE, or the first of GSC_DEVICES); calls on the same key are serialised, and nothing here synchronises the device.
 // Routing: a call of at most GSC_VERIFY_FEW_MAX items takes the few-proof kernels (k_verify_few.hip: 8 lanes per proof), larger
 // calls the per-thread ones; gsc_verify_last_path reports which.
+// The last section is the prover's self-check (prove_check.hpp): the same key object on an engine replica's device, fed by k_check_prep from a
+// lane's output buffers on the lane's stream.
 #include "../../include/libprove.h"
 #include "json.hpp"
 #include "verify_common.hpp"
@@ -13,6 +15,9 @@
 #include "verify_claims_kernels.hpp"
 #include "verify_kernels.hpp"
 #include "verify_few_kernels.hpp"
+#include "prove_check.hpp"
+#include "prove_check_kernels.hpp"
+#include <algorithm>
 #include <atomic>
 #include <cerrno>
 #include <cstdio>
@@ -62,14 +67,18 @@ int verify_device() {
     return 0;
 }
 
+thread_local size_t* devbuf_tally = nullptr;      // build_key points this at the key's byte count: what its buffers take of device memory
 template <class T> struct DevBuf {
     T* p = nullptr;
-    void alloc(size_t n) { ck(hipMalloc(&p, n * sizeof(T) + 1), "hipMalloc"); }
-    ~DevBuf() { if (p) (void)hipFree(p); }
+    size_t* tally = nullptr; size_t held = 0;      // the count this buffer is part of while it lives
+    void alloc(size_t n) { ck(hipMalloc(&p, n * sizeof(T) + 1), "hipMalloc"); tally = devbuf_tally; held = n * sizeof(T) + 1; if (tally) *tally += held; }
+    ~DevBuf() { if (p) { (void)hipFree(p); if (tally) *tally -= held; } }
 };
 
 struct GpuKey {
     int device = 0, algo = 0;
+    size_t cap = 0;                      // proofs per device pass: what the chunk buffers below hold (kChunk for a verifier's key)
+    size_t bytes = 0;                    // device memory of the key's own buffers (those allocated later included)
     hipStream_t stream = nullptr;
     bool has_commitment = false, fits = false;
     size_t few_max = 0;                  // GSC_VERIFY_FEW_MAX as it stood when the key loaded
@@ -97,11 +106,14 @@ struct GpuKey {
     DevBuf<uint8_t> cflag;
     ClaimBufs claim_bufs() {
         if (!cparts.p) {
-            cparts.alloc(kChunk); cterms.alloc(kChunk * kBatchSums); crho.alloc(kChunk * 5); cfixed.alloc(kChunk * kBatchFixed);
-            cpf.alloc(kChunk * kBatchFixed); cflag.alloc(kChunk);
+            devbuf_tally = &bytes;
+            struct Untally { ~Untally() { devbuf_tally = nullptr; } } untally;
+            cparts.alloc(cap); cterms.alloc(cap * kBatchSums); crho.alloc(cap * 5); cfixed.alloc(cap * kBatchFixed);
+            cpf.alloc(cap * kBatchFixed); cflag.alloc(cap);
         }
         return ClaimBufs{cparts.p, cterms.p, crho.p, cfixed.p, cpf.p, cflag.p};
     }
+    size_t few_cap() const { return std::min(cap, kFewChunk); }      // proofs the few-proof lines buffer holds
     ~GpuKey() { if (stream) { (void)hipStreamSynchronize(stream); (void)hipStreamDestroy(stream); } }
 };
 
@@ -111,11 +123,15 @@ std::shared_ptr<GpuKey>* const g_keys = new std::shared_ptr<GpuKey>[3];
 bool g_dir_tried = false;
 const char* kFiles[3] = {"vk.chacha20", "vk.aes128", "vk.aes256"};
 
-std::shared_ptr<GpuKey> build_key(int algo, const uint8_t* b, size_t n) {
+// the key on `device` with chunk buffers for `cap` proofs per pass (a verifier's key: verify_device(), kChunk; a prover replica's check context:
+// the replica's device and its largest lane)
+std::shared_ptr<GpuKey> build_key(int algo, const uint8_t* b, size_t n, int device, size_t cap) {
     V::VkLayout lay; std::string err;
     if (!V::parse_vk_layout(b, n, lay, &err)) { printf("%s\n", err.c_str()); return nullptr; }
     auto k = std::make_shared<GpuKey>();
-    k->device = verify_device();
+    devbuf_tally = &k->bytes;
+    struct Untally { ~Untally() { devbuf_tally = nullptr; } } untally;
+    k->device = device; k->cap = cap;
     k->few_max = few_max_setting();
     k->algo = algo;
     ck(hipSetDevice(k->device), "hipSetDevice");
@@ -170,11 +186,11 @@ std::shared_ptr<GpuKey> build_key(int algo, const uint8_t* b, size_t n) {
         ck(hipStreamSynchronize(s), "key tables");
     }
     ck(hipStreamSynchronize(s), "key lines");
-    k->proofs.alloc(kChunk * kProofSlot); k->win.alloc(kChunk * V::kWindows); k->pre.alloc(kChunk); k->verdict.alloc(kChunk); k->pd.alloc(kChunk);
-    const size_t nblk = batch_blocks(kChunk);
-    k->rnd.alloc(kChunk * kRandWords); k->ra.alloc(kChunk); k->fixed.alloc(kBatchFixed); k->bok.alloc(kChunk); k->bflag.alloc(1);
-    k->part.alloc(nblk * kBatchSums); k->rpart.alloc(nblk * 4); k->f.alloc(kChunk + kBatchFixed);
-    if (k->few_max) k->few_lines.alloc(kFewChunk * kLineSteps);
+    k->proofs.alloc(cap * kProofSlot); k->win.alloc(cap * V::kWindows); k->pre.alloc(cap); k->verdict.alloc(cap); k->pd.alloc(cap);
+    const size_t nblk = batch_blocks(cap);
+    k->rnd.alloc(cap * kRandWords); k->ra.alloc(cap); k->fixed.alloc(kBatchFixed); k->bok.alloc(cap); k->bflag.alloc(1);
+    k->part.alloc(nblk * kBatchSums); k->rpart.alloc(nblk * 4); k->f.alloc(cap + kBatchFixed);
+    if (k->few_max) k->few_lines.alloc(k->few_cap() * kLineSteps);
     return k;
 }
 
@@ -185,7 +201,7 @@ void load_dir_once() {      // like libverify: keys from GSC_VK_DIR on first use
     for (int a = 0; a < 3; a++) if (!g_keys[a]) {
         std::ifstream f(std::string(dir) + "/" + kFiles[a], std::ios::binary); if (!f) continue;
         std::vector<uint8_t> buf((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
-        try { g_keys[a] = build_key(a, buf.data(), buf.size()); } catch (const std::exception& e) { printf("%s\n", e.what()); }
+        try { g_keys[a] = build_key(a, buf.data(), buf.size(), verify_device(), kChunk); } catch (const std::exception& e) { printf("%s\n", e.what()); }
     }
 }
 std::shared_ptr<GpuKey> key_for(int algo) { std::lock_guard<std::mutex> l(g_mu); load_dir_once(); return g_keys[algo]; }
@@ -215,15 +231,19 @@ bool route_few(GpuKey& k, size_t n) {
     const int mode = g_path_mode.load();
     const bool few = mode ? mode == kPathFew : n <= k.few_max;
     k.last_path = few ? kPathFew : kPathThread;
-    if (few && !k.few_lines.p) k.few_lines.alloc(kFewChunk * kLineSteps);
+    if (few && !k.few_lines.p) {
+        devbuf_tally = &k.bytes;
+        struct Untally { ~Untally() { devbuf_tally = nullptr; } } untally;
+        k.few_lines.alloc(k.few_cap() * kLineSteps);
+    }
     return few;
 }
-// verdicts of the m proofs in k.pd into k.verdict, one pairing check per proof on the call's path
-void launch_pairings(GpuKey& k, bool few, size_t m) {
+// verdicts of the m proofs in k.pd into k.verdict, one pairing check per proof on the call's path, on stream s
+void launch_pairings(GpuKey& k, bool few, size_t m, hipStream_t s) {
     if (few) {
-        launch_verify_few_lines(k.pd.p, m, k.few_lines.p, k.stream);
-        launch_verify_few_pairing(k.kd, k.pd.p, k.few_lines.p, k.verdict.p, nullptr, m, k.stream);
-    } else launch_verify_pairing(k.kd, k.pd.p, k.verdict.p, nullptr, m, k.stream);
+        launch_verify_few_lines(k.pd.p, m, k.few_lines.p, s);
+        launch_verify_few_pairing(k.kd, k.pd.p, k.few_lines.p, k.verdict.p, nullptr, m, s);
+    } else launch_verify_pairing(k.kd, k.pd.p, k.verdict.p, nullptr, m, s);
     ck(hipGetLastError(), "k_verify_pairing");
 }
 
@@ -240,7 +260,7 @@ long long run_verify(GpuKey& k, const uint8_t* proofs, const uint32_t* lens, con
         if (!k.fits) { memset(verdicts + off, 0, m); continue; }
         prep_chunk(k, proofs, lens, signals, off, m, win, pre);
         hipStream_t s = k.stream;
-        launch_pairings(k, few, m);
+        launch_pairings(k, few, m, k.stream);
         ck(hipMemcpyAsync(verdicts + off, k.verdict.p, m, hipMemcpyDeviceToHost, s), "copy");
         ck(hipStreamSynchronize(s), "verify");
         for (size_t i = 0; i < m; i++) accepted += verdicts[off + i];
@@ -322,7 +342,7 @@ long long run_verify_batched(GpuKey& k, const uint8_t* proofs, const uint32_t* l
         for (size_t i = 0; i < m; i++) nok += okv[i];
         if (all) { if (!flag || nok < m) return 0; continue; }
         if (!flag) {      // some proof with ok fails: the per-proof pairings of the same ProofDev decide, as in run_verify
-            launch_pairings(k, few, m);
+            launch_pairings(k, few, m, k.stream);
             ck(hipMemcpyAsync(verdicts + off, k.verdict.p, m, hipMemcpyDeviceToHost, s), "copy");
             ck(hipStreamSynchronize(s), "verify");
             nok = 0;
@@ -417,7 +437,7 @@ extern "C" {
 int gsc_verify_init(GoUint8 algorithmID, GoSlice verifyingKey) {
     if (algorithmID > 2 || !verifyingKey.data || verifyingKey.len <= 0) return 0;
     try {
-        auto k = build_key(algorithmID, (const uint8_t*)verifyingKey.data, (size_t)verifyingKey.len);
+        auto k = build_key(algorithmID, (const uint8_t*)verifyingKey.data, (size_t)verifyingKey.len, verify_device(), kChunk);
         if (!k) return 0;
         std::lock_guard<std::mutex> l(g_mu);
         g_keys[algorithmID] = std::move(k);
@@ -614,3 +634,66 @@ long long gsc_verify_debug_pairing_impl(const uint8_t* g1, const uint8_t* g2, si
         return (long long)n;
     } catch (const std::exception& e) { printf("gsc_debug_pairing: %s\n", e.what()); return -1; }
 }
+
+// ---- the prover's self-check (prove_check.hpp): a key as above on an engine replica's device, fed from a lane's output buffers ----
+namespace gsc {
+
+struct ProveCheckCtx {
+    std::shared_ptr<GpuKey> key;
+    std::atomic<uint64_t> chunks{0}, proofs{0}, refused{0}, fallbacks{0};
+};
+
+std::shared_ptr<ProveCheckCtx> prove_check_create(int algo, const uint8_t* vk, size_t len, int device, size_t cap) {
+    auto c = std::make_shared<ProveCheckCtx>();
+    c->key = build_key(algo, vk, len, device, cap);
+    if (!c->key) return nullptr;
+    return c;
+}
+size_t prove_check_device_bytes(const ProveCheckCtx& c) { return c.key->bytes; }
+void prove_check_add_stats(const ProveCheckCtx& c, uint64_t out[4]) {
+    out[0] += c.chunks.load(); out[1] += c.proofs.load(); out[2] += c.refused.load(); out[3] += c.fallbacks.load();
+}
+
+// Everything goes on the LANE's stream s (the key's own stream is idle in a check context); the caller has made the key's device current.
+ProveCheckPass::ProveCheckPass(std::shared_ptr<ProveCheckCtx> ctx, const ProveCheckInput& in, hipStream_t s)
+    : ctx_(std::move(ctx)), lock_(ctx_->key->mu), s_(s), n_(in.n), win_(in.n * V::kWindows), verdict_(in.n, 0), rnd_(in.n * kRandWords) {
+    GpuKey& k = *ctx_->key;
+    if (!n_) return;
+    if (n_ > k.cap) throw std::runtime_error("internal: a chunk larger than the self-check's buffers");
+    if (!k.fits) return;      // the key is not one of this circuit: Verify accepts nothing under it, every verdict stays 0
+    for (size_t i = 0; i < n_; i++) V::public_windows(k.algo, in.signals + V::kSignalBytes * i, win_.data() + V::kWindows * i);
+    // the route of a verifier call of n items; the lines buffer bounds the few-proof pass
+    few_ = route_few(k, n_) && n_ <= k.few_cap();
+    draw_randomizers(rnd_.data(), n_, k.has_commitment, ctx_->chunks.load());
+    ck(hipMemcpyAsync(k.win.p, win_.data(), n_ * V::kWindows, hipMemcpyHostToDevice, s), "copy");
+    ck(hipMemcpyAsync(k.rnd.p, rnd_.data(), n_ * kRandWords * sizeof(uint32_t), hipMemcpyHostToDevice, s), "copy");
+    launch_check_prep(k.kd, ProverOut{in.d_out, in.d_cpts, in.d_status, in.d_flags, in.B, n_}, k.win.p, k.pd.p, s);
+    ck(hipGetLastError(), "k_check_prep");
+    launch_verify_batch(k.kd, k.pd.p, k.rnd.p, n_, k.bufs(), few_ ? k.few_lines.p : nullptr, s);
+    ck(hipGetLastError(), "k_verify_batch");
+    ck(hipMemcpyAsync(verdict_.data(), k.bok.p, n_, hipMemcpyDeviceToHost, s), "copy");
+    ck(hipMemcpyAsync(&flag_, k.bflag.p, 1, hipMemcpyDeviceToHost, s), "copy");
+}
+// a pass that is dropped before finish() (an exception on the way) has kernels on the context's buffers: they are through before the next pass may start
+ProveCheckPass::~ProveCheckPass() { if (!finished_) (void)hipStreamSynchronize(s_); }
+
+const std::vector<uint8_t>& ProveCheckPass::finish(const uint32_t* status, const uint8_t* flags) {
+    GpuKey& k = *ctx_->key;
+    finished_ = true;
+    if (!n_ || !k.fits) return verdict_;
+    // the batch equation holds over the proofs that took part (ok): nothing more to do when those are all the prover would release
+    bool all = flag_ != 0;
+    for (size_t i = 0; all && i < n_; i++) if (status[i] == 0xFFFFFFFFu && !flags[i] && !verdict_[i]) all = false;
+    if (all) return verdict_;
+    // otherwise the per-proof pairings over the same ProofDev entries decide, as in run_verify_batched
+    fell_back_ = true;
+    launch_pairings(k, few_, n_, s_);
+    ck(hipMemcpyAsync(verdict_.data(), k.verdict.p, n_, hipMemcpyDeviceToHost, s_), "copy");
+    ck(hipStreamSynchronize(s_), "prove check");
+    return verdict_;
+}
+void ProveCheckPass::count(size_t checked, size_t refused) {
+    ctx_->chunks++; ctx_->proofs += checked; ctx_->refused += refused; if (fell_back_) ctx_->fallbacks++;
+}
+
+}  // namespace gsc

@@ -269,6 +269,32 @@ extern int gsc_debug_verify_path(int mode);
  * them and the lane-sliced final exponentiation). */
 extern long long gsc_debug_pairing_few(const uint8_t *g1_uncompressed, const uint8_t *g2_uncompressed, size_t n, uint8_t *out);
 
+/* ---- the prover's self-check (an addition; off unless asked for) ----
+ * With the check on for an algorithm, a proof leaves Prove / ProveBatch / gsc_prove_raw only if Verify (libverify.so, gsc_verify_raw) would
+ * accept the released bytes under the loaded verifying key and the public signals ct | nonce | counter | pt, which the host builds from the
+ * request and its own ciphertext.  Every chunk is decided on the device before anything is downloaded: the verifier's batch check over the
+ * chunk's points as they lie in the prover's output buffers (coordinates < p, the curve equations exactly, [r]B = infinity, then one final
+ * exponentiation), and the per-proof pairings when that fails.  A proof that fails is refused exactly as a prover error is: "{}" from Prove /
+ * ProveBatch, proof_lens[i] = 0 and a zeroed slot from gsc_prove_raw; every other proof of the chunk is released unchanged, byte for byte what
+ * the call gives with the check off.  Statements the prover refuses anyway (solver status, degenerate points) take no part.
+ *
+ * gsc_prove_check_init: verifyingKey = gnark VerifyingKey.WriteTo bytes (the decoder and the refusals of gsc_verify_init, raw points
+ * included).  Builds one check context per engine replica on that replica's device.  1 = on; 0 = the key was refused (a line on stdout; the
+ * state stays as it was); -1 = the algorithm is not initialised.  An empty slice turns the check off and frees the contexts (1).  Safe beside
+ * running Prove calls: a chunk is checked under the key that was loaded when it started, or not at all.
+ * GSC_PROVE_CHECK=1 in the environment makes InitAlgorithm do this itself with vk.chacha20 / vk.aes128 / vk.aes256 from GSC_VK_DIR; a missing
+ * or refused file makes InitAlgorithm return 0 with one line on stdout. */
+extern int gsc_prove_check_init(GoUint8 algorithmID, GoSlice verifyingKey);
+/* out: chunks checked, proofs checked, proofs refused by the check, chunks that needed the proof-by-proof pass — summed over the replicas,
+ * since the key was loaded; all 0 while the check is off.  Returns 0, -1 when the algorithm is not initialised.  gsc_describe reports
+ * check=off or check=on(<bytes of device memory of the contexts>). */
+extern int gsc_prove_check_stats(GoUint8 algorithmID, uint64_t out[4]);
+/* TEST HOOK: arms a one-shot change to statement `index` of the algorithm's next chunk, applied on the device behind the assembly and in
+ * front of the check and the download, inside that proof's own output slot.  which: 0 A, 1 B, 2 C, 3 D, 4 PoK (3, 4: AES only).  mode 0: the
+ * same point of statement (index + 1) mod n — a valid group element in the wrong equation; mode 1: bit 0 of the point's y flipped — off the
+ * curve.  An index past the chunk changes nothing.  Returns 0; -1 when hooks are off, the algorithm is not initialised or which / mode is none. */
+extern int gsc_debug_prove_corrupt(GoUint8 algorithmID, uint32_t index, int which, int mode);
+
 #ifdef __cplusplus
 }
 #endif
