@@ -317,7 +317,7 @@ std::string Algorithm::describe() const {
     std::string out = buf;
     if (impl_->quotient_eval) out += std::string(" quotient=evaluation-form") + (impl_->fuse_z_digits ? "+digits" : "") + (!impl_->fuse_z_digits || !impl_->cfg.overlap_quotient ? "" : impl_->cfg.overlap_quotient == 2 ? "+beside-wire-sets" : "+beside-wire-sets(<4096)") + "(c: " + std::to_string(impl_->mC.nbit) + " grouped + " + std::to_string(impl_->mC.nflat - impl_->mC.nbit) + " flat + " + std::to_string(impl_->mC.nwide) + " windowed)";
     else out += " quotient=coefficient-form";
-    if (impl_->quotient_eval) out += impl_->mZ.digit_bases ? " Zlive=" + std::to_string(impl_->mZ.nwide) + " Zfold=" + impl_->fold_route : " Zfold=off(" + impl_->fold_why + ")";
+    if (impl_->quotient_eval) out += impl_->mZ.digit_bases ? " Zlive=" + std::to_string(impl_->mZ.nwide) + " Zfold=dft" :" Zfold=off(" + impl_->fold_why + ")";
     if (impl_->quotient_eval) out += " Qtiles=" + std::to_string(quot_live_tiles(impl_->L, impl_->quot_live)) + "/" + std::to_string(1u << (impl_->L - (impl_->L + 1) / 2));      // tiles the last quotient kernel runs
     out += impl_->small.ok ? " witness=small-integer(" + std::to_string(impl_->small.n_levels) + " chained levels, fallbacks " + std::to_string(impl_->small_fallbacks.load()) + ")" : " witness=generic" + (impl_->small.why.empty() ? std::string() : "(" + impl_->small.why + ")");
     out += impl_->cfg.keep_secrets ? " wipe=off" : impl_->cfg.wipe_full ? " wipe=full" : " wipe=inputs";

@@ -54,8 +54,8 @@ struct EngineConfig {
                                  // bases V_i plus a flat sum over the solver's c); 0 = coefficient form for every call (six transforms, the key's own Z bases)
     int fuse_z_digits = 1;       // GSC_FUSE_Z_DIGITS: in evaluation form the last quotient kernel writes the signed digits of d itself (no scalar vector, no recoding pass); 0 = it writes d
     int quotient_fold = 1;       // GSC_QUOTIENT_FOLD: in evaluation form, the bases of the coset values that the domain's zero padding makes redundant are folded into the others at
-                                 // InitAlgorithm (k_quot_bases.hip, "the fold": n - m + 1 of the n Z bases are never walked again).  1 = by the dense sums where their init cost
-                                 // allows it (ChaCha20-V3), by three group transforms otherwise (AES-V2); 2 = by the transforms always; 0 = the sets as the key gives them.  Same bytes
+                                 // InitAlgorithm (k_quot_bases.hip, "the fold": n - m + 1 of the n Z bases are never walked again) by three group transforms; 0 = the sets as the key
+                                 // gives them; 2 = accepted as 1 (it used to choose between two routes of the fold).  Same bytes
     int quotient_live_tiles = 1; // GSC_QUOTIENT_LIVE_TILES: with folded sets, the last quotient kernel runs only the tiles that hold live table positions and the one before it stores
                                  // only what those tiles load (kernels.hpp quot_live_tiles); 0 = every tile, every element.  Same bytes
     int small_witness = 1;       // GSC_SMALL_WITNESS: circuits whose whole witness is small integers (ChaCha20-V3) are solved by the integer kernels on byte planes

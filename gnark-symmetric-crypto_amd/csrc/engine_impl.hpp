@@ -153,18 +153,12 @@ class AlgorithmImpl {
     // The fold (k_quot_bases.hip): with m constraints on a domain of n only m - 1 of the d_i are independent of c; the bases of the others went into U and V
     // (U', V': valid only as a pair — mC and mZ are both folded or neither), mZ walks m - 1 bases.  fold_why: why not, for gsc_describe.
     std::string fold_why = "GSC_QUOTIENT_FOLD=0";
-    const char* fold_route = "";      // "dense" or "dft" once the sets are folded (gsc_describe: Zfold=)
     // ... and the evaluation-form quotient computes d for the live table positions only (launch_compute_d*'s live; cfg.quotient_live_tiles).  0: for all n —
     // the sets are not folded, or the knob is off
     size_t quot_live = 0;
-    // The dense route's init cost gate: (2m - 1)(n - m + 1) scalar multiplications (ChaCha20-V3 4.3e8).  Beyond it (AES-V2: 8.5e9 and 6.6e9), and for
-    // GSC_QUOTIENT_FOLD=2 whatever the size, the same sums come from three group transforms of size n (fold_quotient_bases_dft: AES-128 3.8e6).
-    static constexpr double FOLD_MAX_SCALAR_MULS = 1e9;
-    // U' and V' (table order, m and m - 1 points) from U and V; false (and fold_why) when a folded base is the point at infinity
+    // U' and V' (table order, m and m - 1 points) from U and V; false (and fold_why) when a folded V base is the point at infinity
     bool fold_quotient_bases(const DevBuf<G1Aff>& d_U, const std::vector<uint8_t>& stU, const DevBuf<G1Aff>& d_V, const std::vector<uint8_t>& stV, const std::vector<uint32_t>& rowsZ,
                              DevBuf<G1Aff>& d_U2, std::vector<uint8_t>& stU2, DevBuf<G1Aff>& d_V2, std::vector<uint8_t>& stV2);
-    bool fold_quotient_bases_dft(const DevBuf<G1Aff>& d_U, const std::vector<uint8_t>& stU, const DevBuf<G1Aff>& d_V, const std::vector<uint8_t>& stV, const std::vector<uint32_t>& rowsZ,
-                                 DevBuf<G1Aff>& d_U2, std::vector<uint8_t>& stU2, DevBuf<G1Aff>& d_V2, std::vector<uint8_t>& stV2);
     // batch buffers: one set per lane.  A lane = a HIP stream with its own witness / polynomial / partial-sum buffers; with more than
     // one full lane big batches are cut into chunks that the lanes prove concurrently.  Measured on MI355X: for FULL
     // batches two lanes do not beat one (the MSM kernels fill the chip; chaining the heavy phases so that only the witness stage

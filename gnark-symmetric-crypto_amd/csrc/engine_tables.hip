@@ -350,63 +350,9 @@ void AlgorithmImpl::build_subset(const AffT* b, size_t ng, AffT* t, uint8_t* ok)
     HIP_CHECK(hipStreamSynchronize(stream));
 }
 
-// The fold (k_quot_bases.hip): 2m - 1 sums over the n - m + 1 dropped bases, in chunks of FOLD_COLS columns through the windowed MSM kernels —
-// a temporary table of small digits over the dropped bases, the scalar matrix of a chunk in the engine's [base][column] layout, recode,
-// gather-accumulate, reduce, Horner — then U_i and V_i added with the exact group law.  ChaCha20-V3: 4.3e8 scalar multiplications, about two Z
-// launches of work.
+// The fold (k_quot_bases.hip): U' and V' from U and V by three group transforms (launch_quot_fold_dft) — 3 n points and the weights as scratch.
 bool AlgorithmImpl::fold_quotient_bases(const DevBuf<G1Aff>& d_U, const std::vector<uint8_t>& stU, const DevBuf<G1Aff>& d_V, const std::vector<uint8_t>& stV, const std::vector<uint32_t>& rowsZ,
                                         DevBuf<G1Aff>& d_U2, std::vector<uint8_t>& stU2, DevBuf<G1Aff>& d_V2, std::vector<uint8_t>& stV2) {
-    constexpr size_t FOLD_COLS = 8192; constexpr int FOLD_C = 13;
-    const size_t m = n_constraints, nj = domain_n - m + 1, ncols = 2 * m - 1, B = FOLD_COLS;
-    const int nwin = msm_windows(FOLD_C); const size_t D = (size_t)1 << (FOLD_C - 1), noct = (nj + 7) / 8;
-    DevBuf<uint32_t> d_perm(domain_n); d_perm.upload(rowsZ.data(), domain_n, stream);
-    DevBuf<fe> pw(domain_n), node(ncols), weight(ncols), yj(nj), lam(nj);
-    launch_quot_fold_weights(dom.p, d_perm.p, L, (uint32_t)m, pw.p, node.p, weight.p, yj.p, lam.p, stream);
-    HIP_CHECK(hipGetLastError());
-    // the dropped bases: the tail of V in table order
-    DevBuf<G1Aff> table(nj * D);
-    {
-        std::vector<uint64_t> off(nj); std::vector<uint32_t> len(nj, (uint32_t)D);
-        for (size_t i = 0; i < nj; i++) off[i] = i * D;
-        build_rows<G1Aff, G1Xyzz>(d_V.p + (m - 1), nj, off, len, table.p);
-    }
-    size_t per = 0; const size_t nslices = msm_slices(nj, (size_t)nwin, WIN_SLICE, B, per), Bw = B * (size_t)nwin;
-    DevBuf<fe> scal(nj * B); DevBuf<uint4> digits((size_t)nwin * noct * B);
-    DevBuf<G1Xyzz> pa(nslices * Bw), pb((nslices + MSM_REDUCE_FANIN - 1) / MSM_REDUCE_FANIN * Bw), sj(Bw), sums((ncols + B - 1) / B * B);
-    for (size_t p0 = 0; p0 < ncols; p0 += B) {
-        launch_quot_fold_scalars(node.p, weight.p, yj.p, lam.p, (uint32_t)nj, (uint32_t)p0, (uint32_t)ncols, B, scal.p, stream);
-        launch_msm_recode(MsmRecodeArgs{scal.p, nullptr, 0, nj, B, FOLD_C, nwin, digits.p}, stream);
-        launch_msm_win<G1Aff>(MsmWinArgs{table.p, FOLD_C, nwin, nj, digits.p, B, nslices, per, pa.p}, stream);
-        {      // slices -> one sum per (window, column)
-            G1Xyzz* src = pa.p; G1Xyzz* alt = pb.p;
-            for (size_t ns = nslices;;) {
-                const size_t groups = msm_reduce_groups(ns, Bw);
-                launch_msm_reduce(src, ns, Bw, groups == 1 ? sj.p : alt, stream);
-                if (groups == 1) break;
-                std::swap(src, alt); ns = groups;
-            }
-        }
-        MsmHornerJobs jobs{}; jobs.job[0] = MsmHornerJob{sj.p, nullptr, sums.p + p0, nwin, FOLD_C}; jobs.n = 1;
-        launch_msm_horner<G1Aff>(jobs, B, stream);
-        HIP_CHECK(hipGetLastError());
-    }
-    DevBuf<uint8_t> d_stU(m), d_stV(m - 1), d_stU2(m), d_stV2(m - 1);
-    d_stU.upload(stU.data(), m, stream); d_stV.upload(stV.data(), m - 1, stream);
-    d_U2.alloc(m); d_V2.alloc(m - 1); stU2.resize(m); stV2.resize(m - 1);
-    launch_quot_fold_add(d_U.p, d_stU.p, sums.p, m, d_U2.p, d_stU2.p, stream);
-    launch_quot_fold_add(d_V.p, d_stV.p, sums.p + m, m - 1, d_V2.p, d_stV2.p, stream);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipMemcpyAsync(stU2.data(), d_stU2.p, m, hipMemcpyDeviceToHost, stream));
-    HIP_CHECK(hipMemcpyAsync(stV2.data(), d_stV2.p, m - 1, hipMemcpyDeviceToHost, stream));
-    HIP_CHECK(hipStreamSynchronize(stream));
-    if (std::count(stV2.begin(), stV2.end(), (uint8_t)0) != (ptrdiff_t)(m - 1)) { fold_why = "a folded V base is the point at infinity"; return false; }
-    fold_why.clear();
-    return true;
-}
-
-// The same U' and V' from three group transforms (launch_quot_fold_dft): no table, no scalar matrix — 3 n points and the weights as scratch.
-bool AlgorithmImpl::fold_quotient_bases_dft(const DevBuf<G1Aff>& d_U, const std::vector<uint8_t>& stU, const DevBuf<G1Aff>& d_V, const std::vector<uint8_t>& stV, const std::vector<uint32_t>& rowsZ,
-                                            DevBuf<G1Aff>& d_U2, std::vector<uint8_t>& stU2, DevBuf<G1Aff>& d_V2, std::vector<uint8_t>& stV2) {
     const size_t m = n_constraints;
     DevBuf<uint32_t> d_perm(domain_n); d_perm.upload(rowsZ.data(), domain_n, stream);
     DevBuf<uint8_t> d_stU(m), d_stV(domain_n), d_stU2(m), d_stV2(m - 1), scratch(quot_fold_dft_scratch_bytes(L, (uint32_t)m));
@@ -551,18 +497,13 @@ void AlgorithmImpl::init_key(const R1csFile& cs, const PkFile& key) {
             };
         };
         // The fold: positions m - 1 .. n - 1 of the table order leave the Z set, their bases go into U and into the live V (k_quot_bases.hip).
-        // Gated on a key without points at infinity among V (positions must not shift) and on there being something to drop.  Route: the dense sums
-        // where their init cost passes FOLD_MAX_SCALAR_MULS (ChaCha20-V3), otherwise — or always, GSC_QUOTIENT_FOLD=2 — the three transforms.
+        // Gated on a key without points at infinity among V (positions must not shift) and on there being something to drop.
         DevBuf<G1Aff> d_U2, d_V2; std::vector<uint8_t> stU2, stV2;
         size_t live = domain_n;
-        const double fold_cost = (2.0 * (double)n_constraints - 1.0) * (double)(domain_n - n_constraints + 1);
         if (cfg.quotient_fold) {
-            const bool dense = cfg.quotient_fold == 1 && fold_cost <= FOLD_MAX_SCALAR_MULS;
             if (n_constraints < 2 || domain_n - n_constraints + 1 < domain_n / 64) fold_why = "nothing to drop";
             else if (std::count(stV.begin(), stV.end(), (uint8_t)0) != (ptrdiff_t)domain_n) fold_why = "a V base is the point at infinity";
-            else timed("G1.Z fold", [&] {
-                if (dense ? fold_quotient_bases(d_U, stU, d_V, stV, rowsZ, d_U2, stU2, d_V2, stV2) : fold_quotient_bases_dft(d_U, stU, d_V, stV, rowsZ, d_U2, stU2, d_V2, stV2)) { live = n_constraints - 1; fold_route = dense ? "dense" : "dft"; }
-            });
+            else timed("G1.Z fold", [&] { if (fold_quotient_bases(d_U, stU, d_V, stV, rowsZ, d_U2, stU2, d_V2, stV2)) live = n_constraints - 1; });
         }
         const bool folded = live != domain_n;
         const std::vector<uint8_t> rawV(live * 32, 0), rawU(n_constraints * 32, 0);      // build_set only takes the point count from these

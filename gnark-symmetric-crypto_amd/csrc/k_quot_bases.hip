@@ -153,41 +153,6 @@ __global__ __launch_bounds__(64) void k_qf_weights(const fe* pw, const uint32_t*
     }
 }
 
-// scal[q * batch + b] = lambda_q weight_p / (y_q - node_p) as a canonical integer, p = p0 + b (columns beyond ncols repeat the last one):
-// the scalar matrix of the windowed MSM over the dropped bases, [base][column].  A thread inverts its QF_ROWS differences at once.
-constexpr int QF_ROWS = 16;
-__global__ __launch_bounds__(64) void k_qf_scalars(const fe* node, const fe* weight, const fe* yj, const fe* lam, uint32_t nj, uint32_t p0, uint32_t ncols, size_t batch, fe* scal) {
-    const size_t b = (size_t)blockIdx.x * 64 + threadIdx.x;
-    const uint32_t q0 = blockIdx.y * QF_ROWS, p = p0 + b < ncols ? p0 + (uint32_t)b : ncols - 1;
-    const fe e = node[p], w = weight[p];
-    fe pre[QF_ROWS], run = Fr::one();
-#pragma unroll
-    for (int k = 0; k < QF_ROWS; k++) {
-        pre[k] = run;
-        if (q0 + k < nj) run = Fr::mul(run, Fr::sub(yj[q0 + k], e));
-    }
-    fe inv = Fr::inv(run);
-#pragma unroll
-    for (int k = QF_ROWS - 1; k >= 0; k--) {
-        if (q0 + k >= nj) continue;
-        const fe one_over = Fr::mul(inv, pre[k]);
-        inv = Fr::mul(inv, Fr::sub(yj[q0 + k], e));
-        store_fe(scal + (size_t)(q0 + k) * batch + b, Fr::from_mont(Fr::mul(Fr::mul(lam[q0 + k], w), one_over)));
-    }
-}
-
-// out[i] = base[i] + sum[i] with the exact group law, affine in the table builders' layout; status 2 = the point at infinity
-__global__ __launch_bounds__(64) void k_qf_add(const Aff<Fp>* base, const uint8_t* base_status, const fe* sum, uint32_t n, Aff<Fp>* out, uint8_t* status) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    Xyzz9<Fp29f> p = G1x::load_xyzz(sum + 4 * (size_t)i);
-    if (base_status[i] != 2) p = G1x::add(p, G1x::from_aff(Aff9<Fp29f>{qb_to_fp29(base[i].x), qb_to_fp29(base[i].y)}));
-    if (p.inf) { status[i] = 2; out[i] = Aff<Fp>{Fp::zero(), Fp::zero()}; return; }
-    const Aff9<Fp29f> a = G1x::to_aff(p);
-    out[i] = Aff<Fp>{qb_from_fp29(a.x), qb_from_fp29(a.y)};
-    status[i] = 0;
-}
-
 // TEST HOOK: out[i] = a[i] + b[i] as canonical big-endian X | Y (zeros and flag 1 for the point at infinity)
 __global__ __launch_bounds__(64) void k_qf_sum_be(const fe* a, const fe* b, uint32_t n, uint8_t* out, uint8_t* flags) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -199,8 +164,9 @@ __global__ __launch_bounds__(64) void k_qf_sum_be(const fe* a, const fe* b, uint
     for (int c = 0; c < 2; c++) for (int k = 0; k < 32; k++) out[64 * (size_t)i + 32 * c + k] = (uint8_t)(xy[c].l[7 - k / 4] >> (8 * (3 - k % 4)));
 }
 
-// ---- the fold as three group transforms ----------------------------------------------------------------------------------------------------
-// The dense route above spends one scalar multiplication per (column, dropped base).  Both sums are structured in the node index:
+// ---- the sums as three group transforms ----------------------------------------------------------------------------------------------------
+// The fold needs, for every column, a sum over the dropped bases: sum_J lambda_j V_j / (y_j - x_i) for U'_i (i < m) and sum_J lambda_j V_j / (y_j - y_i)
+// for V'_i (i in I) — (2m - 1)(n - m + 1) terms taken one by one.  Both sums are structured in the node index:
 // with W_j = lambda_j V_j (j in J; the point at infinity elsewhere) and W^_k = sum_j w^(-jk) W_j (one transform of size n),
 //   x nodes (i < m):      y^n - x^n = -2 = (y - x) sum_k y^(n-1-k) x^k, hence
 //     sum_J W_j / (y_j - x_i) = -1/2 sum_k w^(ik) zeta^(n-1-k) W^_((k+1) mod n);
@@ -208,7 +174,7 @@ __global__ __launch_bounds__(64) void k_qf_sum_be(const fe* a, const fe* b, uint
 //     g^_k = sum_d g(d) w^(dk) is closed-form, g^_0 = (1 - n) / 2, g^_k = (n + 1) / 2 - k (0 < k < n), hence
 //     sum_J W_j / (y_j - y_i) = 1 / (n y_i) sum_k w^(ik) g^_k W^_k.
 // The outer sums run in the other direction: k_qb_stage's transform, read at index (-i) mod n.  U'_i = U_i - (weight_i / 2) A^[-i],
-// V'_i = V_i + (weight_i / (n y_i)) G^[-i]: the same group elements as the dense route's, hence the same affine bases.
+// V'_i = V_i + (weight_i / (n y_i)) G^[-i] (weight: mu 2^261 or nu, k_qf_weights): the group elements defined above, whichever way they are summed.
 // tests/test_quot_fold_dft_host.py checks the identities on integers.
 
 // cst[0] = w = zeta^2, cst[1] = w^-1 = w^(n-1) (Montgomery): what k_qf_powers and k_qb_twiddles take from the key's domain record
@@ -244,7 +210,7 @@ __global__ __launch_bounds__(64) void k_qfd_pointwise(const fe* What, uint32_t n
 }
 
 // Column p of the fold (k_qf_weights): p < m the node x_p, out U'_p = U_p - (weight_p / 2) Ax[-p]; p >= m the coset node of table position
-// p - m, index i = perm[p - m], out V'_(p-m) = V_(p-m) + (weight_p / (n node_p)) Gy[-i].  Affine bases and statuses as k_qf_add writes them.
+// p - m, index i = perm[p - m], out V'_(p-m) = V_(p-m) + (weight_p / (n node_p)) Gy[-i].  Affine in the table builders' layout; status 2 = the point at infinity.
 __global__ __launch_bounds__(64) void k_qfd_finish(const fe* Ax, const fe* Gy, const uint32_t* perm, uint32_t n, uint32_t m, const fe* node, const fe* weight,
                                                    const Aff<Fp>* U, const uint8_t* stU, const Aff<Fp>* V, const uint8_t* stV, Aff<Fp>* U2, uint8_t* stU2, Aff<Fp>* V2, uint8_t* stV2) {
     const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
@@ -288,6 +254,12 @@ size_t quot_fold_dft_scratch_bytes(int L, uint32_t m) {
     const size_t n = (size_t)1 << L, nj = n - m + 1;
     return (2 + n + n / 2 + 2 * (2 * (size_t)m - 1) + 2 * nj) * sizeof(fe) + 3 * n * sizeof(G1Xyzz);
 }
+// the fold's weights: pw (n elements, scratch), node and weight (2m - 1), yj and lam (n - m + 1), all Montgomery
+static void launch_quot_fold_weights(const fe* omega, const uint32_t* perm, int L, uint32_t m, fe* pw, fe* node, fe* weight, fe* yj, fe* lam, hipStream_t s) {
+    const uint32_t n = 1u << L;
+    hipLaunchKernelGGL(k_qf_powers, dim3((n + 63) / 64), dim3(64), 0, s, omega, perm, n, L, m, pw, yj);
+    hipLaunchKernelGGL(k_qf_weights, dim3((m + n + 63) / 64), dim3(64), 0, s, pw, perm, n, L, m, node, weight, yj, lam);
+}
 void launch_quot_fold_dft(int L, uint32_t m, const uint32_t* perm, const G1Aff* U, const uint8_t* stU, const G1Aff* V, const uint8_t* stV,
                           G1Aff* U2, uint8_t* stU2, G1Aff* V2, uint8_t* stV2, void* scratch, hipStream_t s, hipEvent_t weights_done) {
     const uint32_t n = 1u << L, hn = n / 2, nj = n - m + 1, ncols = 2 * m - 1, blocks = (n + 63) / 64;
@@ -314,17 +286,6 @@ void launch_g1_aff_to_be(const G1Aff* in, const uint8_t* status, size_t n, uint8
     if (n) hipLaunchKernelGGL(k_qfd_to_be, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, reinterpret_cast<const Aff<Fp>*>(in), status, (uint32_t)n, be, flags);
 }
 
-void launch_quot_fold_weights(const fe* omega, const uint32_t* perm, int L, uint32_t m, fe* pw, fe* node, fe* weight, fe* yj, fe* lam, hipStream_t s) {
-    const uint32_t n = 1u << L;
-    hipLaunchKernelGGL(k_qf_powers, dim3((n + 63) / 64), dim3(64), 0, s, omega, perm, n, L, m, pw, yj);
-    hipLaunchKernelGGL(k_qf_weights, dim3((m + n + 63) / 64), dim3(64), 0, s, pw, perm, n, L, m, node, weight, yj, lam);
-}
-void launch_quot_fold_scalars(const fe* node, const fe* weight, const fe* yj, const fe* lam, uint32_t nj, uint32_t p0, uint32_t ncols, size_t batch, fe* scal, hipStream_t s) {
-    hipLaunchKernelGGL(k_qf_scalars, dim3((unsigned)(batch / 64), (nj + QF_ROWS - 1) / QF_ROWS), dim3(64), 0, s, node, weight, yj, lam, nj, p0, ncols, batch, scal);
-}
-void launch_quot_fold_add(const G1Aff* base, const uint8_t* base_status, const G1Xyzz* sum, size_t n, G1Aff* out, uint8_t* status, hipStream_t s) {
-    if (n) hipLaunchKernelGGL(k_qf_add, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, reinterpret_cast<const Aff<Fp>*>(base), base_status, reinterpret_cast<const fe*>(sum), (uint32_t)n, reinterpret_cast<Aff<Fp>*>(out), status);
-}
 void launch_g1_sum_be(const G1Xyzz* a, const G1Xyzz* b, size_t n, uint8_t* out, uint8_t* flags, hipStream_t s) {
     if (n) hipLaunchKernelGGL(k_qf_sum_be, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, reinterpret_cast<const fe*>(a), reinterpret_cast<const fe*>(b), (uint32_t)n, out, flags);
 }

@@ -201,18 +201,11 @@ void launch_quot_bases(const G1Aff* zfile, const uint8_t* zstatus, int L, int mo
 // InitAlgorithm: the fold of the coset values that the domain's zero padding makes redundant (k_quot_bases.hip, "the fold").  With m
 // constraints the d of the table positions m - 1 .. n - 1 (perm: position -> coset index) are linear in c and in the other d; the fold's
 // 2m - 1 columns are the nodes x_p (p < m, base U_p) and the coset points of the positions p - m (base V at that position).
-// weights: pw (n elements, scratch), node and weight (2m - 1), yj and lam (n - m + 1), all Montgomery.
-void launch_quot_fold_weights(const fe* omega, const uint32_t* perm, int L, uint32_t m, fe* pw, fe* node, fe* weight, fe* yj, fe* lam, hipStream_t s);
-// scal[q * batch + b] = the canonical scalar of dropped base q in column p0 + b (columns beyond ncols repeat the last): launch_msm_recode's layout, mont = 0
-void launch_quot_fold_scalars(const fe* node, const fe* weight, const fe* yj, const fe* lam, uint32_t nj, uint32_t p0, uint32_t ncols, size_t batch, fe* scal, hipStream_t s);
-// out[i] = base[i] + sum[i] (exact group law; base_status[i] = 2: base i is the point at infinity), affine, status[i] = 2 for the point at infinity
-void launch_quot_fold_add(const G1Aff* base, const uint8_t* base_status, const G1Xyzz* sum, size_t n, G1Aff* out, uint8_t* status, hipStream_t s);
-// The same fold as three group transforms of size n = 2^L instead of (2m - 1)(n - m + 1) scalar multiplications (k_quot_bases.hip, "the fold as three
-// group transforms"): about 3 (n/2) L + 3n + 2m of them.  perm (device, n entries): table position -> coset index; U (m bases), V (n bases, table order)
-// with statuses (2: the point at infinity), all on the device.  Out: U' (m) and V' (m - 1, table order), affine, status 2 for the point at infinity — the
-// same group elements as the dense route's.  2 <= m <= n, 2 <= L <= 17; w = zeta^2 is derived from L, nothing of a key is needed.  scratch:
-// quot_fold_dft_scratch_bytes(L, m) bytes of device memory, free again once the stream has passed.  weights_done (optional): recorded behind the
-// weight kernels, before the transforms.
+// Their sums over the dropped bases come from three group transforms of size n = 2^L (k_quot_bases.hip, "the sums as three group transforms"): about
+// 3 (n/2) L + 3n + 2m scalar multiplications.  perm (device, n entries): table position -> coset index; U (m bases), V (n bases, table order)
+// with statuses (2: the point at infinity), all on the device.  Out: U' (m) and V' (m - 1, table order), affine, status 2 for the point at infinity.
+// 2 <= m <= n, 2 <= L <= 17; w = zeta^2 is derived from L, nothing of a key is needed.  scratch: quot_fold_dft_scratch_bytes(L, m) bytes of device
+// memory, free again once the stream has passed.  weights_done (optional): recorded behind the weight kernels, before the transforms.
 size_t quot_fold_dft_scratch_bytes(int L, uint32_t m);
 void launch_quot_fold_dft(int L, uint32_t m, const uint32_t* perm, const G1Aff* U, const uint8_t* stU, const G1Aff* V, const uint8_t* stV,
                           G1Aff* U2, uint8_t* stU2, G1Aff* V2, uint8_t* stV2, void* scratch, hipStream_t s, hipEvent_t weights_done = nullptr);

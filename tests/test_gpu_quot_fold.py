@@ -1,5 +1,6 @@
 """The quotient fold on the device (k_quot_bases.hip): GSC_QUOTIENT_FOLD=1 drops the n - m + 1 = 9 152 Z bases that the
-domain's zero padding makes redundant and folds them into U and the live V; the sums, hence the proof bytes, must not change.
+domain's zero padding makes redundant and folds them into U and the live V — by the three group transforms of launch_quot_fold_dft, the
+fold's only route — and the sums, hence the proof bytes, must not change.
 
 Two prover processes on the golden ChaCha20 key, fold on and off, small tables (c = 8), (r, s) fixed; each proves the same 64 statements and
 evaluates the quotient sum of 64 columns of caller-supplied a, b with entries +-1 on every row < m (gsc_debug_z_sum): proofs never multiply

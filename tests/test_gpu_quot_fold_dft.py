@@ -5,9 +5,12 @@ U', V' come from the DENSE formulas on the exponents (quot_fold_model.fold_dense
 byte with their infinity flags.  L = 4 and 6 are the smallest domains at which the index negation, the (k + 1) mod n wrap, g^_0 and the
 bit-reversed loads of the second pass can go wrong; every m at which a set is empty or a single element is there.
 
-Then whole provers in child processes: ChaCha20-V3 by the dense sums (GSC_QUOTIENT_FOLD=1) and by the transforms (=2) must build the same
-sets, and AES-128 — whose dense fold is 20 x too expensive, so that it was never folded before — folded by the transforms against unfolded:
-the same proof bytes, accepted by libverify, and the same quotient sums for inputs whose every c_i is +-1."""
+Then whole provers in child processes: ChaCha20-V3's transforms must build the sets that the engine's dense sums built before they were retired
+(digests of 64 proofs and of the +-1 quotient sums, recorded from that route: tests/golden/quot_fold_chacha20_dense.json), GSC_QUOTIENT_FOLD=2
+still means folded, and AES-128 folded against unfolded: the same proof bytes, accepted by libverify, and the same quotient sums for inputs
+whose every c_i is +-1."""
+import hashlib
+import json
 import os
 import random
 import subprocess
@@ -165,12 +168,36 @@ def _same_outputs(a, b, proof_len):
     assert len({a["pts"][64 * k:64 * k + 64] for k in range(64)}) == 64      # 64 different columns, 64 different points
 
 
-def test_chacha20_dense_and_transform_routes_build_the_same_sets(tmp_path):
-    runs = _children(tmp_path, 0, ("1", "2"), 23617)
-    dense, dft = runs["1"], runs["2"]
-    for r, route in ((dense, "dense"), (dft, "dft")):
-        assert " Z=32768 " in r["describe"] and "Zlive=23616 " in r["describe"] and "Zfold=%s " % route in r["describe"], r["describe"]
-    _same_outputs(dense, dft, 164)
+def _field(describe, key):
+    return [w for w in describe.split() if w.startswith(key + "=")][0].split("=", 1)[1]
+
+
+@pytest.fixture(scope="module")
+def chacha_runs(tmp_path_factory):
+    return _children(tmp_path_factory.mktemp("fold_dft_chacha"), 0, (None, "2"), 23617)
+
+
+def test_chacha20_transforms_build_the_sets_the_dense_sums_built(chacha_runs):
+    """tests/golden/quot_fold_chacha20_dense.json: digests of what this very child gave when the sets were folded term by term (the retired dense
+    route, GSC_QUOTIENT_FOLD=1 at the commit the file names; it agreed there, byte for byte, with the transforms)."""
+    want = json.loads(golden_bytes("quot_fold_chacha20_dense.json"))
+    run = chacha_runs[None]
+    assert " Z=32768 " in run["describe"] and "Zlive=23616 " in run["describe"] and "Zfold=dft " in run["describe"], run["describe"]
+    assert (want["proofs"], want["proof_bytes"], want["rows"]) == (N, 164, 23617)
+    proofs = [run["proofs"][196 * k:196 * k + 164] for k in range(N)]
+    assert hashlib.sha256(b"".join(proofs)).hexdigest() == want["sha256_proofs"]
+    assert hashlib.sha256(run["pts"] + run["flags"]).hexdigest() == want["sha256_points_flags"]
+    assert len(set(proofs)) == N
+    assert run["flags"] == bytes(64)                                       # no column sums to the point at infinity
+    assert len({run["pts"][64 * k:64 * k + 64] for k in range(64)}) == 64      # 64 different columns, 64 different points
+
+
+def test_chacha20_knob_value_2_still_means_folded(chacha_runs):
+    # (2 used to choose the transforms over the dense sums: hosts that set it keep initialising, and get the default)
+    default, two = chacha_runs[None], chacha_runs["2"]
+    for key in ("Z", "Zlive", "Zfold", "Qtiles"):
+        assert _field(two["describe"], key) == _field(default["describe"], key), (key, two["describe"])
+    assert _field(two["describe"], "Zfold") == "dft"
 
 
 @pytest.fixture(scope="module")
@@ -179,10 +206,6 @@ def aes_runs(aes_keys, tmp_path_factory):
     assert os.path.exists(pk_path)
     # (no latency layouts: these children prove one batch of 64 and share the device with the session's own algorithms)
     return _children(tmp_path_factory.mktemp("fold_dft_aes"), 1, (None, "0"), 8192, pk_path, {"GSC_FEW_Z_GB": "0", "GSC_FEW_WIDE": "0"})
-
-
-def _field(describe, key):
-    return [w for w in describe.split() if w.startswith(key + "=")][0].split("=", 1)[1]
 
 
 def test_aes128_is_folded_by_default_and_says_so(aes_runs):

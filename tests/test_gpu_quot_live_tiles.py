@@ -105,7 +105,7 @@ def test_the_knob_changes_what_is_launched_and_says_so(chacha):
     runs, _ = chacha
     on, off = runs["1"], runs["0"]
     for r in (on, off):
-        assert _field(r["describe"], "Z") == "32768" and _field(r["describe"], "Zlive") == "23616" and _field(r["describe"], "Zfold") == "dense", r["describe"]
+        assert _field(r["describe"], "Z") == "32768" and _field(r["describe"], "Zlive") == "23616" and _field(r["describe"], "Zfold") == "dft", r["describe"]
     assert _field(on["describe"], "Qtiles") == "93/128", on["describe"]
     assert _field(off["describe"], "Qtiles") == "128/128", off["describe"]
 
