@@ -25,7 +25,8 @@ EXPORTS = ["enforce_binding", "InitAlgorithm", "Free", "Prove", "ProveBatch", "g
            "gsc_verify_raw_batched", "gsc_verify_all", "VerifyAll", "gsc_debug_verify_randomizers",
            "gsc_verify_json", "gsc_verify_last_path", "gsc_debug_verify_path", "gsc_debug_pairing_few",
            "gsc_verify_claims", "VerifyClaims",
-           "gsc_prove_check_init", "gsc_prove_check_stats", "gsc_debug_prove_corrupt"]
+           "gsc_prove_check_init", "gsc_prove_check_stats", "gsc_debug_prove_corrupt",
+           "gsc_release_algorithm", "gsc_replace_algorithm", "gsc_memory_info", "gsc_key_generation"]
 
 
 class GoSlice(C.Structure):
@@ -117,6 +118,14 @@ def lib():
         L.gsc_prove_check_stats.argtypes = [C.c_ubyte, C.POINTER(C.c_uint64)]
         L.gsc_debug_prove_corrupt.restype = C.c_int
         L.gsc_debug_prove_corrupt.argtypes = [C.c_ubyte, C.c_uint32, C.c_int, C.c_int]
+        L.gsc_release_algorithm.restype = C.c_ubyte
+        L.gsc_release_algorithm.argtypes = [C.c_ubyte]
+        L.gsc_replace_algorithm.restype = C.c_int
+        L.gsc_replace_algorithm.argtypes = [C.c_ubyte, GoSlice, GoSlice, GoSlice]
+        L.gsc_memory_info.restype = C.c_int
+        L.gsc_memory_info.argtypes = [C.c_int, C.POINTER(C.c_uint64)]
+        L.gsc_key_generation.restype = C.c_uint64
+        L.gsc_key_generation.argtypes = [C.c_ubyte]
         L.enforce_binding()
         _lib = L
     return _lib
@@ -132,6 +141,41 @@ def init_algorithm(algorithm_id: int, proving_key: bytes, r1cs: bytes) -> bool:
     s1, k1 = _slice(proving_key)
     s2, k2 = _slice(r1cs)
     return bool(lib().InitAlgorithm(algorithm_id, s1, s2))
+
+
+def release_algorithm(algorithm_id: int) -> bool:
+    """gsc_release_algorithm: takes the algorithm out, waits for the calls in flight and frees the engine with all its device memory.
+    False: it was not initialised."""
+    return bool(lib().gsc_release_algorithm(algorithm_id))
+
+
+def replace_algorithm(algorithm_id: int, proving_key: bytes, r1cs: bytes, verifying_key: bytes = b"") -> int:
+    """gsc_replace_algorithm: a new engine from (proving_key, r1cs) built beside the serving one, swapped in, the old one drained and freed.
+    1 swapped; 0 refused (a line on stdout; the old key keeps serving); -1 the algorithm is not initialised.  verifying_key: the self-check of
+    the new engine is on under it (b"": off, or as GSC_PROVE_CHECK says)."""
+    s1, k1 = _slice(proving_key)
+    s2, k2 = _slice(r1cs)
+    s3, k3 = _slice(verifying_key) if verifying_key else (GoSlice(None, 0, 0), None)
+    return int(lib().gsc_replace_algorithm(algorithm_id, s1, s2, s3))
+
+
+def memory_info(device: int = 0):
+    """gsc_memory_info: {"free", "total", "provers", "verifiers"} in bytes for one device; None for a device that does not exist."""
+    out = (C.c_uint64 * 4)()
+    if lib().gsc_memory_info(device, out) != 0:
+        return None
+    return dict(zip(("free", "total", "provers", "verifiers"), (int(v) for v in out)))
+
+
+def key_generation(algorithm_id: int) -> int:
+    """gsc_key_generation: 0 not initialised, 1 after InitAlgorithm, +1 per successful replace_algorithm."""
+    return int(lib().gsc_key_generation(algorithm_id))
+
+
+def key_id(algorithm_id: int):
+    """The key= field of gsc_describe (first 16 hex digits of SHA-256 of the proving key's bytes); None when not initialised."""
+    d = describe(algorithm_id)
+    return d.split(" key=")[1].split()[0] if " key=" in d else None
 
 
 def _take(ret: ProveReturn) -> bytes:

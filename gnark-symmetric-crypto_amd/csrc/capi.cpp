@@ -7,6 +7,7 @@
 #include "../../include/libprove.h"
 #include "engine.hpp"
 #include "dispatch.hpp"
+#include "registry.hpp"
 #include "glv.hpp"
 #include "host_ciphers.hpp"
 #include "json.hpp"
@@ -31,79 +32,14 @@ namespace {
 
 const char* kAlgorithmNames[3] = {"chacha20", "aes-128-ctr", "aes-256-ctr"};   // prove_impl.go:21-25
 
-// Micro-batching: concurrent single-proof Prove() callers (the reference is called from many goroutines / FFI threads:
-// libraries/core_test.go:44-111) are gathered into ONE device batch instead of running one proof each, back to back.
-// Worker threads — one per (device, lane) of the algorithm's engine — drain the queue; WHEN a worker takes HOW MANY callers is
-// csrc/dispatch.hpp's BatchScheduler (tested on CPU with a stub engine): a lone caller on an idle device goes at once; while every
-// device has a batch on it the callers that arrive form the next one; the callers of a batch that has just completed are waited for
-// as long as they keep coming back (GSC_LINGER_US, default 300 us, sets the windows; 0 = never wait on an idle device); a burst is
-// shared out over the free devices and every share goes out as one device batch to the least-loaded engine replica.
-class Batcher {
-  public:
-    explicit Batcher(Algorithm* a) : algo_(a), sched_(a->devices() ? a->devices() : 1, a->max_batch(), linger_from_env()) {
-        // one worker per (device, lane): a second batch per device is started when enough callers are queued for it (dispatch.hpp)
-        const size_t nw = (a->lanes() ? a->lanes() : 1) * (a->devices() ? a->devices() : 1);
-        for (size_t i = 0; i < nw; i++) workers_.emplace_back([this] { run(); });
-    }
-    ~Batcher() { { std::lock_guard<std::mutex> l(mu_); stop_ = true; } sched_.cv.notify_all(); for (auto& w : workers_) if (w.joinable()) w.join(); }
-    // blocks until the proof is done; throws std::runtime_error if the device batch failed
-    void submit(const ProofRequest& req, ProofResult& out) {
-        Item it{&req, &out, false, std::string(), &it};
-        { std::unique_lock<std::mutex> l(mu_); q_.push_back(&it); sched_.arrived(); done_cv_.wait(l, [&] { return it.done; }); }
-        if (!it.error.empty()) throw std::runtime_error(it.error);
-    }
-    // A small call of several statements (ProveBatch / gsc_prove_raw with up to SMALL_CALL statements): its statements queue like single
-    // callers, so concurrent small calls share device batches whatever entry point they came through.
-    static constexpr size_t SMALL_CALL = 32;
-    void submit_many(const ProofRequest* reqs, size_t n, ProofResult* out) {
-        std::vector<Item> items(n);
-        {
-            std::unique_lock<std::mutex> l(mu_);
-            for (size_t i = 0; i < n; i++) { items[i] = Item{&reqs[i], &out[i], false, std::string(), items.data()}; q_.push_back(&items[i]); }
-            sched_.arrived(n);
-            done_cv_.wait(l, [&] { for (const Item& it : items) if (!it.done) return false; return true; });
-        }
-        for (const Item& it : items) if (!it.error.empty()) throw std::runtime_error(it.error);
-    }
-  private:
-    struct Item { const ProofRequest* req; ProofResult* res; bool done; std::string error; const void* call; };      // call: the same for all statements of one submit_many
-    static int linger_from_env() { const char* e = getenv("GSC_LINGER_US"); return e && *e ? atoi(e) : 300; }
-    void run() {
-        for (;;) {
-            std::vector<Item*> take;
-            {
-                std::unique_lock<std::mutex> l(mu_);
-                const size_t want = sched_.wait_for_batch(l, [&] { return q_.size(); }, stop_);
-                if (!want) return;                         // stopped, nothing queued
-                while (!q_.empty() && take.size() < want) { take.push_back(q_.front()); q_.pop_front(); }
-                sched_.started(take.size());
-            }
-            // Whatever happens below — a device error, an allocation failure, anything thrown — the callers parked on done_cv_ are released
-            // and the scheduler hears of the completion: nobody is left waiting on a batch that died.
-            std::string err; std::vector<ProofResult> res;
-            try {
-                std::vector<ProofRequest> reqs(take.size()); res.resize(take.size());
-                for (size_t i = 0; i < take.size(); i++) reqs[i] = *take[i]->req;
-                algo_->prove_batch(reqs.data(), reqs.size(), res.data(), nullptr, true);      // whole: one device batch on ONE replica (plan_shares)
-            } catch (const std::exception& e) { err = e.what(); if (err.empty()) err = "proving failed"; }
-            catch (...) { err = "proving failed (unknown error)"; }
-            {
-                std::lock_guard<std::mutex> l(mu_);
-                for (size_t i = 0; i < take.size(); i++) { if (err.empty() && i < res.size()) *take[i]->res = res[i]; take[i]->error = err; take[i]->done = true; }
-                size_t calls = 0; const void* prev = nullptr;      // (the statements of a call are queued back to back)
-                for (Item* it : take) { if (it->call != prev) calls++; prev = it->call; }
-                sched_.completed(take.size(), calls);
-            }
-            done_cv_.notify_all();
-        }
-    }
-    Algorithm* algo_; BatchScheduler sched_; bool stop_ = false;
-    std::mutex mu_; std::condition_variable done_cv_; std::deque<Item*> q_; std::vector<std::thread> workers_;
-};
-
-std::mutex g_mu;
-std::unique_ptr<Algorithm> g_algo[3];
-std::unique_ptr<Batcher> g_batcher[3];     // declared after g_algo: destroyed first
+// The algorithms (registry.hpp): an engine and the micro-batcher in front of it per id.  Every entry point takes ONE snapshot
+// when it enters and is served by it until it returns, whatever gsc_release_algorithm / gsc_replace_algorithm do meanwhile.
+using ServedAlgo = Served<Algorithm>;
+using Snapshot = Registry<ServedAlgo>::Ref;
+Registry<ServedAlgo> g_reg;
+Snapshot snapshot(int cipher) { return g_reg.snapshot((size_t)cipher); }
+Algorithm* algo_of(const Snapshot& s) { return s ? s->algo.get() : nullptr; }
+std::mutex g_mu;      // the fixed randomness below
 bool g_fixed_rand = false; uint8_t g_r[32], g_s[32], g_mask[32];   // little-endian canonical; written under g_mu, read by fill_randomness under g_mu
 DebugVectors g_debug;
 // The gsc_debug_* entry points and gsc_set_deterministic_randomness exist for the parity tests only: fixing (r, s, mask) removes
@@ -251,20 +187,23 @@ void fill_randomness(ProofRequest& q) {
     random_fr_le(q.r); random_fr_le(q.s); random_fr_le(q.mask);
 }
 
-Algorithm* lookup(int cipher) { std::lock_guard<std::mutex> l(g_mu); return g_algo[cipher].get(); }
-Batcher* batcher(int cipher) { std::lock_guard<std::mutex> l(g_mu); return g_batcher[cipher].get(); }
-
 std::string success_json(const ProofResult& r, const uint8_t ct[64]) {   // OutputParams, prove_impl.go:45-52
     return "{\"proof\":{\"proofJson\":\"" + base64_encode(r.proof, r.proof_len) + "\"},\"publicSignals\":\"" + base64_encode(ct, 64) + "\"}";
 }
 
+// What one call holds of the algorithms: at most one snapshot per cipher, taken when the call first needs the cipher and kept until the call
+// returns — a ProveBatch call is served, from parsing to its last result, by the engines it found.
+struct CallSnapshots {
+    Snapshot held[3]; bool taken[3] = {false, false, false};
+    const Snapshot& of(int cipher) { if (!taken[cipher]) { held[cipher] = snapshot(cipher); taken[cipher] = true; } return held[cipher]; }
+};
 // parses + validates one request; throws GoPanic
 struct Prepared { int cipher; ProofRequest req; };
-Prepared prepare(const JsonValue& v) {
+Prepared prepare(const JsonValue& v, CallSnapshots& snaps) {
     Decoded d = decode_params(v);
     const int cipher = find_cipher(d.cipher);
     if (cipher < 0) panic_string("could not find prover for" + d.cipher);                       // prove_impl.go:141 (sic: no space)
-    if (!lookup(cipher)) panic_string("proving params are not initialized for cipher: " + d.cipher);   // :124-126
+    if (!snaps.of(cipher)) panic_string("proving params are not initialized for cipher: " + d.cipher);   // :124-126
     Prepared p{cipher, make_request(cipher, d)};
     fill_randomness(p.req);
     return p;
@@ -281,10 +220,12 @@ std::string prove_one_json(const char* data, size_t len, DebugVectors* dbg) {
     try {
         JsonValue root;
         try { root = json_parse(data, len); } catch (const JsonSyntaxError& e) { throw GoPanic{"{\"Offset\":" + std::to_string(e.offset) + "}"}; }
-        Prepared p = prepare(root);
+        CallSnapshots snaps;
+        Prepared p = prepare(root, snaps);
+        const Snapshot& served = snaps.of(p.cipher);
         ProofResult res;
-        if (dbg) lookup(p.cipher)->prove_batch(&p.req, 1, &res, dbg);      // test hook: straight to the device, keeps the intermediates
-        else batcher(p.cipher)->submit(p.req, res);                       // shares a device batch with concurrent callers
+        if (dbg) served->algo->prove_batch(&p.req, 1, &res, dbg);          // test hook: straight to the device, keeps the intermediates
+        else served->batcher->submit(p.req, res);                         // shares a device batch with concurrent callers
         if (res.status) throw GoPanic{"{}"};     // gnark solver / prover error: no exported fields
         return success_json(res, p.req.ciphertext);
     } catch (const GoPanic& g) {
@@ -294,6 +235,45 @@ std::string prove_one_json(const char* data, size_t len, DebugVectors* dbg) {
         printf("%s\n", e.what());
         return json_quote(e.what());
     }
+}
+
+// A complete engine for `id` with its micro-batcher, from the environment as it stands now; throws std::runtime_error with a printable line.
+// vk == nullptr (InitAlgorithm): the self-check as GSC_PROVE_CHECK says.  vk given (gsc_replace_algorithm): non-empty, the check is on under that key
+// or there is no engine; empty, as GSC_PROVE_CHECK says.  outgoing: the engine this one will replace (its device bytes count as free for the widths).
+std::unique_ptr<ServedAlgo> build_served(GoUint8 id, GoSlice provingKey, GoSlice r1cs, const GoSlice* vk, const ServedAlgo* outgoing) {
+    if (!provingKey.data || provingKey.len <= 0 || !r1cs.data || r1cs.len <= 0) throw std::runtime_error("error reading proving key: EOF");
+    EngineConfig cfg = config_from_env();
+    if (outgoing) {
+        const std::vector<int> devs = cfg.devices.empty() ? std::vector<int>{cfg.device} : cfg.devices;
+        const auto old = outgoing->algo->replica_bytes();
+        for (size_t i = 0; i < devs.size(); i++) cfg.outgoing_bytes.push_back(i < old.size() && old[i].first == devs[i] ? old[i].second : 0);
+    }
+    std::unique_ptr<Algorithm> algo(new Algorithm((Cipher)id, (const uint8_t*)provingKey.data, (size_t)provingKey.len, (const uint8_t*)r1cs.data, (size_t)r1cs.len, cfg));
+    if (vk && vk->data && vk->len > 0) {
+        if (!algo->prove_check_init((const uint8_t*)vk->data, (size_t)vk->len)) throw std::runtime_error("gsc_replace_algorithm: the verifying key was refused");
+    } else if (cfg.prove_check) {      // GSC_PROVE_CHECK=1: the self-check under the verifying key of GSC_VK_DIR, or no algorithm at all
+        static const char* const files[3] = {"vk.chacha20", "vk.aes128", "vk.aes256"};
+        const std::string path = cfg.vk_dir + "/" + files[id];
+        std::vector<uint8_t> key;
+        if (FILE* f = cfg.vk_dir.empty() ? nullptr : fopen(path.c_str(), "rb")) {
+            uint8_t buf[4096]; size_t got;
+            while ((got = fread(buf, 1, sizeof buf, f)) > 0) key.insert(key.end(), buf, buf + got);
+            fclose(f);
+        }
+        if (key.empty()) throw std::runtime_error("GSC_PROVE_CHECK=1: cannot read " + (cfg.vk_dir.empty() ? std::string("a verifying key: GSC_VK_DIR is not set") : path));
+        if (!algo->prove_check_init(key.data(), key.size())) throw std::runtime_error("GSC_PROVE_CHECK=1: " + path + " refused");
+    }
+    uint8_t digest[32]; sha256_digest((const uint8_t*)provingKey.data, (size_t)provingKey.len, digest);
+    char hex[17]; for (int i = 0; i < 8; i++) snprintf(hex + 2 * i, 3, "%02x", digest[i]);
+    return std::unique_ptr<ServedAlgo>(new ServedAlgo(std::move(algo), hex));
+}
+// An engine that has left the registry and is idle, about to be freed: its lanes are at their idle image after every call, and
+// this holds them against it once more.  The line below must never appear.
+void retire(ServedAlgo& s, const char* who) {
+    try {
+        const size_t off = s.algo->scrub_before_free();
+        if (off) printf("%s: %zu bytes of the outgoing engine's secret regions were off the idle image; every region was wiped before the free\n", who, off);
+    } catch (const std::exception& e) { printf("%s: the outgoing engine could not be scanned: %s\n", who, e.what()); }
 }
 
 }  // namespace
@@ -308,31 +288,41 @@ void enforce_binding(void) {}
 
 GoUint8 InitAlgorithm(GoUint8 algorithmID, GoSlice provingKey, GoSlice r1cs) {
     if (algorithmID > 2) return 0;                               // unknown id -> false (prove_impl.go:113)
-    std::lock_guard<std::mutex> l(g_mu);
-    if (g_algo[algorithmID]) return 1;                           // already initialised (prove_impl.go:74-76)
     try {
-        if (!provingKey.data || provingKey.len <= 0 || !r1cs.data || r1cs.len <= 0) throw std::runtime_error("error reading proving key: EOF");
-        const EngineConfig cfg = config_from_env();
-        std::unique_ptr<Algorithm> algo(new Algorithm((Cipher)algorithmID, (const uint8_t*)provingKey.data, (size_t)provingKey.len, (const uint8_t*)r1cs.data, (size_t)r1cs.len, cfg));
-        if (cfg.prove_check) {      // GSC_PROVE_CHECK=1: the self-check under the verifying key of GSC_VK_DIR, or no algorithm at all
-            static const char* const files[3] = {"vk.chacha20", "vk.aes128", "vk.aes256"};
-            const std::string path = cfg.vk_dir + "/" + files[algorithmID];
-            std::vector<uint8_t> vk;
-            if (FILE* f = cfg.vk_dir.empty() ? nullptr : fopen(path.c_str(), "rb")) {
-                uint8_t buf[4096]; size_t got;
-                while ((got = fread(buf, 1, sizeof buf, f)) > 0) vk.insert(vk.end(), buf, buf + got);
-                fclose(f);
-            }
-            if (vk.empty()) throw std::runtime_error("GSC_PROVE_CHECK=1: cannot read " + (cfg.vk_dir.empty() ? std::string("a verifying key: GSC_VK_DIR is not set") : path));
-            if (!algo->prove_check_init(vk.data(), vk.size())) throw std::runtime_error("GSC_PROVE_CHECK=1: " + path + " refused");
-        }
-        g_algo[algorithmID] = std::move(algo);
-        g_batcher[algorithmID].reset(new Batcher(g_algo[algorithmID].get()));
+        // already initialised: 1, the new key is dropped (prove_impl.go:74-76).  Otherwise the build — outside the registry's mutex: callers of the
+        // other algorithms go on meanwhile; a second InitAlgorithm of this id waits for it and then finds the id initialised
+        g_reg.init(algorithmID, [&] { return build_served(algorithmID, provingKey, r1cs, nullptr, nullptr); });
         return 1;
     } catch (const std::exception& e) {
         printf("%s\n", e.what());                                 // fmt.Println(err) in the reference
         return 0;
     }
+}
+
+GoUint8 gsc_release_algorithm(GoUint8 algorithmID) {
+    if (algorithmID > 2) return 0;
+    return g_reg.release(algorithmID, [](ServedAlgo& s) { retire(s, "gsc_release_algorithm"); }) ? 1 : 0;
+}
+
+int gsc_replace_algorithm(GoUint8 algorithmID, GoSlice provingKey, GoSlice r1cs, GoSlice verifyingKey) {
+    if (algorithmID > 2) return -1;
+    try {
+        return g_reg.replace(algorithmID, [&](const ServedAlgo& serving) { return build_served(algorithmID, provingKey, r1cs, &verifyingKey, &serving); },
+                             [](ServedAlgo& s) { retire(s, "gsc_replace_algorithm"); });
+    } catch (const std::exception& e) {
+        // the old engine has served throughout and keeps serving; the attempt's device memory went back as the exception unwound
+        std::string msg = e.what();
+        if (msg.find("out of memory") != std::string::npos) msg += ": the new engine does not fit beside the serving one — gsc_release_algorithm first, then InitAlgorithm";
+        printf("%s\n", msg.c_str());
+        return 0;
+    }
+}
+
+uint64_t gsc_key_generation(GoUint8 algorithmID) { return algorithmID > 2 ? 0 : g_reg.generation(algorithmID); }
+
+int gsc_memory_info(int device, uint64_t out[4]) {
+    if (!out) return -1;
+    try { return device_memory_info(device, out) ? 0 : -1; } catch (const std::exception& e) { printf("gsc_memory_info: %s\n", e.what()); return -1; }
 }
 
 void Free(void* pointer) { free(pointer); }
@@ -351,8 +341,9 @@ struct Prove_return ProveBatch(GoSlice params) {
         const size_t n = root.items.size();
         std::vector<std::string> results(n);
         std::vector<Prepared> ok; std::vector<size_t> where;
+        CallSnapshots snaps;      // one per cipher present, from prepare to the last result
         for (size_t i = 0; i < n; i++) {
-            try { ok.push_back(prepare(root.items[i])); where.push_back(i); }
+            try { ok.push_back(prepare(root.items[i], snaps)); where.push_back(i); }
             catch (const GoPanic& g) { results[i] = g.json; }
         }
         // one device batch per algorithm; the algorithms have their own streams and buffers, so their batches run concurrently
@@ -364,9 +355,9 @@ struct Prove_return ProveBatch(GoSlice params) {
                 for (size_t k = 0; k < ok.size(); k++) if (ok[k].cipher == c) { reqs.push_back(ok[k].req); idx.push_back(where[k]); }
                 if (reqs.empty()) return;
                 std::vector<ProofResult> res(reqs.size());
-                Batcher* b = reqs.size() <= Batcher::SMALL_CALL ? batcher(c) : nullptr;
-                if (b) { if (Algorithm* al = lookup((GoUint8)c)) al->forget_thread_stat(); b->submit_many(reqs.data(), reqs.size(), res.data()); }      // a small group shares device batches with concurrent callers
-                else lookup(c)->prove_batch(reqs.data(), reqs.size(), res.data());
+                ServedAlgo& served = *snaps.held[c];      // taken by prepare: a cipher is present only with an engine
+                if (reqs.size() <= Batcher<Algorithm>::SMALL_CALL) { served.algo->forget_thread_stat(); served.batcher->submit_many(reqs.data(), reqs.size(), res.data()); }      // a small group shares device batches with concurrent callers
+                else served.algo->prove_batch(reqs.data(), reqs.size(), res.data());
                 for (size_t k = 0; k < reqs.size(); k++) results[idx[k]] = res[k].status ? std::string("{}") : success_json(res[k], reqs[k].ciphertext);
             } catch (...) { std::lock_guard<std::mutex> g(err_mu); if (!err) err = std::current_exception(); }
         };
@@ -388,7 +379,7 @@ struct Prove_return ProveBatch(GoSlice params) {
 
 long long gsc_prove_raw(GoUint8 cipher, const uint8_t* inputs, size_t n, uint8_t* proofs, uint32_t* proof_lens, uint8_t* ciphertexts) {
     if (cipher > 2) return -1;
-    Algorithm* a = lookup(cipher);
+    const Snapshot snap = snapshot(cipher); Algorithm* a = algo_of(snap);
     if (!a) return -1;
     try {
         static const bool trace = getenv("GSC_TRACE_HOST") != nullptr;      // read once
@@ -404,8 +395,7 @@ long long gsc_prove_raw(GoUint8 cipher, const uint8_t* inputs, size_t n, uint8_t
             fill_randomness(q);
         }
         const auto t1 = std::chrono::steady_clock::now();
-        Batcher* b = n && n <= Batcher::SMALL_CALL ? batcher(cipher) : nullptr;
-        if (b) { a->forget_thread_stat(); b->submit_many(reqs.data(), n, res.data()); }      // a small call shares device batches with concurrent callers
+        if (n && n <= Batcher<Algorithm>::SMALL_CALL) { a->forget_thread_stat(); snap->batcher->submit_many(reqs.data(), n, res.data()); }      // a small call shares device batches with concurrent callers
         else a->prove_batch(reqs.data(), n, res.data());
         const auto t2 = std::chrono::steady_clock::now();
         if (trace) fprintf(stderr, "gsc_prove_raw: prepare %.2f ms, prove_batch %.2f ms\n", std::chrono::duration<double, std::milli>(t1 - t0).count(), std::chrono::duration<double, std::milli>(t2 - t1).count());
@@ -422,7 +412,7 @@ long long gsc_prove_raw(GoUint8 cipher, const uint8_t* inputs, size_t n, uint8_t
 
 int gsc_prove_check_init(GoUint8 algorithmID, GoSlice verifyingKey) {
     if (algorithmID > 2) return -1;
-    Algorithm* a = lookup(algorithmID);
+    const Snapshot snap = snapshot(algorithmID); Algorithm* a = algo_of(snap);
     if (!a) return -1;
     try {
         if (!verifyingKey.data || verifyingKey.len <= 0) { a->prove_check_off(); return 1; }
@@ -431,14 +421,14 @@ int gsc_prove_check_init(GoUint8 algorithmID, GoSlice verifyingKey) {
 }
 int gsc_prove_check_stats(GoUint8 algorithmID, uint64_t out[4]) {
     if (algorithmID > 2 || !out) return -1;
-    Algorithm* a = lookup(algorithmID);
+    const Snapshot snap = snapshot(algorithmID); Algorithm* a = algo_of(snap);
     if (!a) return -1;
     a->prove_check_stats(out);
     return 0;
 }
 int gsc_debug_prove_corrupt(GoUint8 algorithmID, uint32_t index, int which, int mode) {
     if (hooks_refused("gsc_debug_prove_corrupt") || algorithmID > 2) return -1;
-    Algorithm* a = lookup(algorithmID);
+    const Snapshot snap = snapshot(algorithmID); Algorithm* a = algo_of(snap);
     if (!a) return -1;
     return a->debug_prove_corrupt(index, which, mode) ? 0 : -1;
 }
@@ -545,7 +535,7 @@ int gsc_debug_glv_split(const uint8_t* k, uint8_t* out) {
 }
 long long gsc_debug_compute_h(GoUint8 algorithmID, const uint8_t* abc_be, size_t m, uint8_t* h_out, size_t cap) {
     if (hooks_refused("gsc_debug_compute_h") || algorithmID > 2) return -1;
-    Algorithm* a = lookup(algorithmID); if (!a) return -1;
+    const Snapshot snap = snapshot(algorithmID); Algorithm* a = algo_of(snap); if (!a) return -1;
     if (!h_out) return (long long)a->domain_size();
     if (cap < a->domain_size() * 64 * 32) return -1;
     try { a->debug_compute_h(abc_be, m, h_out); return (long long)a->domain_size(); }
@@ -554,12 +544,12 @@ long long gsc_debug_compute_h(GoUint8 algorithmID, const uint8_t* abc_be, size_t
 
 long long gsc_debug_secret_residue(GoUint8 algorithmID) {
     if (hooks_refused("gsc_debug_secret_residue") || algorithmID > 2) return -1;
-    Algorithm* a = lookup(algorithmID); if (!a) return -1;
+    const Snapshot snap = snapshot(algorithmID); Algorithm* a = algo_of(snap); if (!a) return -1;
     try { return (long long)a->debug_secret_residue(); } catch (const std::exception& e) { fprintf(stderr, "gsc_debug_secret_residue: %s\n", e.what()); return -1; }
 }
 long long gsc_debug_secret_scan(GoUint8 algorithmID, char* out, size_t cap) {
     if (hooks_refused("gsc_debug_secret_scan") || algorithmID > 2) return -1;
-    Algorithm* a = lookup(algorithmID); if (!a) return -1;
+    const Snapshot snap = snapshot(algorithmID); Algorithm* a = algo_of(snap); if (!a) return -1;
     try {
         std::string report;
         const long long total = (long long)a->debug_secret_scan(report);
@@ -574,7 +564,7 @@ int gsc_debug_wipe(uint64_t bytes, int fill, const uint64_t* desc, size_t ndesc,
 }
 long long gsc_debug_compute_d(GoUint8 algorithmID, const uint8_t* ab_be, size_t m, uint8_t* d_out, size_t cap) {
     if (hooks_refused("gsc_debug_compute_d") || algorithmID > 2) return -1;
-    Algorithm* a = lookup(algorithmID); if (!a) return -1;
+    const Snapshot snap = snapshot(algorithmID); Algorithm* a = algo_of(snap); if (!a) return -1;
     if (!d_out) return (long long)a->domain_size();
     if (cap < a->domain_size() * 64 * 32) return -1;
     try { a->debug_compute_d(ab_be, m, d_out); return (long long)a->domain_size(); }
@@ -582,7 +572,7 @@ long long gsc_debug_compute_d(GoUint8 algorithmID, const uint8_t* ab_be, size_t 
 }
 int gsc_debug_z_sum(GoUint8 algorithmID, const uint8_t* abc_be, size_t m, uint8_t* out, uint8_t* flags) {
     if (hooks_refused("gsc_debug_z_sum") || algorithmID > 2 || !abc_be || !out || !flags) return -1;
-    Algorithm* a = lookup(algorithmID); if (!a) return -1;
+    const Snapshot snap = snapshot(algorithmID); Algorithm* a = algo_of(snap); if (!a) return -1;
     try { a->debug_z_sum(abc_be, m, out, flags); return 0; }
     catch (const std::exception& e) { printf("%s\n", e.what()); return -1; }
 }
@@ -596,13 +586,13 @@ int gsc_debug_quot_fold_dft(int L, uint32_t m, const uint32_t* perm, const uint8
 
 size_t gsc_describe(GoUint8 algorithmID, char* out, size_t cap) {
     if (algorithmID > 2 || !cap) return 0;
-    Algorithm* a = lookup(algorithmID);
-    std::string s = a ? a->describe() : std::string("not initialised");
+    const Snapshot snap = snapshot(algorithmID); Algorithm* a = algo_of(snap);
+    std::string s = a ? a->describe() + " key=" + snap->key_id + " gen=" + std::to_string(snap.generation()) : std::string("not initialised");
     size_t n = s.size() < cap - 1 ? s.size() : cap - 1; memcpy(out, s.data(), n); out[n] = 0; return n;
 }
 int gsc_last_dominant_kernel(GoUint8 algorithmID, char* name, size_t cap, float* ms, size_t* statements, size_t* columns, size_t* nbases) {
     if (algorithmID > 2) return -1;
-    Algorithm* a = lookup(algorithmID); if (!a) return -1;
+    const Snapshot snap = snapshot(algorithmID); Algorithm* a = algo_of(snap); if (!a) return -1;
     const KernelStat st = a->last_kernel_stat();
     if (name && cap) { const size_t n = strlen(st.name) < cap - 1 ? strlen(st.name) : cap - 1; memcpy(name, st.name, n); name[n] = 0; }
     if (ms) *ms = st.ms;
@@ -613,7 +603,7 @@ int gsc_last_dominant_kernel(GoUint8 algorithmID, char* name, size_t cap, float*
 }
 int gsc_last_kernel_clock(GoUint8 algorithmID, float* clock_mhz, int* windows) {
     if (algorithmID > 2) return -1;
-    Algorithm* a = lookup(algorithmID); if (!a) return -1;
+    const Snapshot snap = snapshot(algorithmID); Algorithm* a = algo_of(snap); if (!a) return -1;
     const KernelStat st = a->last_kernel_stat();
     if (clock_mhz) *clock_mhz = st.clock_mhz;
     if (windows) *windows = st.nwin;
@@ -621,7 +611,7 @@ int gsc_last_kernel_clock(GoUint8 algorithmID, float* clock_mhz, int* windows) {
 }
 int gsc_last_stage_ms(GoUint8 algorithmID, float out[4]) {
     if (algorithmID > 2) return -1;
-    Algorithm* a = lookup(algorithmID); if (!a) return -1;
+    const Snapshot snap = snapshot(algorithmID); Algorithm* a = algo_of(snap); if (!a) return -1;
     const KernelStat st = a->last_kernel_stat();
     for (int i = 0; i < 4; i++) out[i] = st.stage_ms[i];
     return 0;

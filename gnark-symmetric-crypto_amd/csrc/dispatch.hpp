@@ -1,6 +1,6 @@
 // Which engine replica (one per device of GSC_DEVICES) serves a call, and when a batcher worker takes how many of the queued
 // single-proof callers.  Host-only policy code with no HIP in it: tests/test_dispatch_policy.py compiles it with g++ against a stub
-// engine and checks the spread on CPU; engine.hip (Algorithm::prove_batch) and capi.cpp (Batcher) are the users.
+// engine and checks the spread on CPU; engine.hip (Algorithm::prove_batch) and registry.hpp (Batcher) are the users.
 //
 // The reference's unit of work is ONE statement per Prove call, from any number of concurrent FFI threads
 // (libraries/prover/libprove.go:30-47; concurrent callers: libraries/core_test.go:44-111), so small calls must reach every GPU of the
@@ -84,7 +84,7 @@ inline size_t batcher_take(size_t queued, size_t free_devices, size_t max_batch)
 //   * a device is free, several callers are queued and nothing is known about them (a burst out of nowhere): the classic linger window, once;
 //   * otherwise (a lone caller, an idle device): go.
 // linger_us = 0 switches both waits off; waiting for a busy device is scheduling, not lingering, and stays.
-// The class holds only the bookkeeping; the queue, its mutex and the items are the user's (capi.cpp Batcher, tests/native/dispatch_check.cpp).
+// The class holds only the bookkeeping; the queue, its mutex and the items are the user's (registry.hpp Batcher, tests/native/dispatch_check.cpp).
 class BatchScheduler {
   public:
     using Clock = std::chrono::steady_clock;

@@ -264,7 +264,7 @@ Algorithm::Algorithm(Cipher cipher, const uint8_t* pk, size_t pk_len, const uint
     // every replica decodes the key and builds its own tables on its device; the builds run side by side
     std::exception_ptr err; std::mutex err_mu; std::vector<std::thread> th;
     auto make = [&](size_t i) {
-        try { EngineConfig c = cfg; c.device = devs[i]; impls_[i].reset(new AlgorithmImpl(cipher, pk, pk_len, r1cs, r1cs_len, c)); }
+        try { EngineConfig c = cfg; c.device = devs[i]; c.reclaim_bytes = i < cfg.outgoing_bytes.size() ? cfg.outgoing_bytes[i] : 0; impls_[i].reset(new AlgorithmImpl(cipher, pk, pk_len, r1cs, r1cs_len, c)); }
         catch (...) { std::lock_guard<std::mutex> g(err_mu); if (!err) err = std::current_exception(); }
     };
     for (size_t i = 1; i < devs.size(); i++) th.emplace_back(make, i);
@@ -424,6 +424,33 @@ size_t Algorithm::debug_secret_scan(std::string& report) {
     bool first = true;
     for (int r = 0; r < WR_COUNT; r++) if (wipe_region_public(r)) { report += (first ? "" : ",") + std::string(wipe_region_name(r)); first = false; }
     return n;
+}
+size_t Algorithm::scrub_before_free() {
+    std::string report; size_t registered = 0, allocated = 0, lane_base = 0, n = 0;
+    for (auto& i : impls_) { n += i->secret_scan(lane_base, report, registered, allocated); lane_base += i->lanes.size(); }
+    if (!n) return 0;
+    for (auto& i : impls_) {
+        HIP_CHECK(hipSetDevice(i->cfg.device));
+        for (auto& ln : i->lanes) { i->wipe_whole(*ln, ln->stream); HIP_CHECK(hipStreamSynchronize(ln->stream)); }
+    }
+    return n;
+}
+std::vector<std::pair<int, size_t>> Algorithm::replica_bytes() const {
+    std::vector<std::pair<int, size_t>> out;
+    for (auto& i : impls_) { size_t b = i->held_bytes(); if (auto c = i->check_now()) b += prove_check_device_bytes(*c); out.emplace_back(i->cfg.device, b); }
+    return out;
+}
+bool device_memory_info(int device, uint64_t out[4]) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev || device >= 64) return false;
+    // (hipMemGetInfo answers for the calling thread's current device: set for the query, put back behind it)
+    int was = 0; if (hipGetDevice(&was) != hipSuccess) return false;
+    size_t free_b = 0, total_b = 0;
+    const bool ok = hipSetDevice(device) == hipSuccess && hipMemGetInfo(&free_b, &total_b) == hipSuccess;
+    (void)hipSetDevice(was);
+    if (!ok) return false;
+    out[0] = free_b; out[1] = total_b; out[2] = prover_bytes_on(device).load(); out[3] = verifier_device_bytes(device);
+    return true;
 }
 void Algorithm::forget_thread_stat() const { if (t_call_owner == this) t_call_owner = nullptr; }
 void Algorithm::prove_batch(const ProofRequest* reqs, size_t n, ProofResult* results, DebugVectors* debug_first, bool whole) {

@@ -10,6 +10,7 @@
 #include <cstddef>
 #include <memory>
 #include <string>
+#include <utility>
 #include <vector>
 
 namespace gsc {
@@ -79,6 +80,10 @@ struct EngineConfig {
     int wipe_grid = 0;           // GSC_WIPE_GRID (test hooks only): workgroups of the wipe launched beside the Z sum (0 = WIPE_GRID_BESIDE), for the measurements of DESIGN.md §5
     int fail_after_stage = 0;    // GSC_FAIL_AFTER_STAGE=k (test hooks only): prove_chunk throws on the host after enqueuing stage k (1 upload, 2 witness, 3 early sums, 4 quotient, 5 msms); nothing faults on the device
     bool few_test_abort = false; // GSC_FEW_TEST_ABORT: the resident witness kernel's barrier never fills (exercises the give-up path)
+    // Not from the environment (gsc_replace_algorithm): device bytes of the engine this one replaces, per replica (Algorithm::replica_bytes of the
+    // outgoing engine, 0 for a replica on another device).  The width chooser counts them as free: the new engine gets the widths a fresh
+    // InitAlgorithm would choose once the old engine is gone.  reclaim_bytes: this replica's share (set by Algorithm's constructor).
+    std::vector<size_t> outgoing_bytes; size_t reclaim_bytes = 0;
 };
 // Every knob is read HERE, once per InitAlgorithm / gsc_setup call — never on the proving path (getenv there would race with a
 // host that calls setenv from another thread, and would let code inside the host flip diagnostics mid-flight).
@@ -132,6 +137,11 @@ class Algorithm {
     // TEST HOOK: bytes off the idle image in EVERY secret region of every lane over its whole allocation, all replicas (after draining the lanes);
     // report: "lane<i>.<name>=<bytes>" for the regions that are not clean, then "registered=<bytes> allocated=<bytes> public=<names>"
     size_t debug_secret_scan(std::string& report);
+    // Before an idle engine is freed (gsc_release_algorithm / gsc_replace_algorithm, after the drain): the same scan, and when it counts anything
+    // every secret region of every lane is wiped over its whole allocation, as the exception path of a call does.  Returns the count: 0, always.
+    size_t scrub_before_free();
+    // {device, bytes this engine holds there} per replica: key tables, lane buffers (alloc_lane's tally) and the self-check context
+    std::vector<std::pair<int, size_t>> replica_bytes() const;
     // The self-check (include/libprove.h gsc_prove_check_init): one context per replica under the gnark VerifyingKey.WriteTo bytes; false (the
     // state stays as it was) for a key the verifier would refuse.  Chunks enqueued from then on are checked under this key.  Throws on a HIP error.
     bool prove_check_init(const uint8_t* vk, size_t len);
@@ -145,6 +155,12 @@ class Algorithm {
     std::unique_ptr<class ReplicaPicker> picker_;            // dispatch.hpp: least-loaded replica for calls that are not split
     mutable std::atomic<size_t> last_replica_{0};            // the replica whose chunk finished last (last_kernel_stat)
 };
+
+// gsc_memory_info: device memory free and in all (hipMemGetInfo), the bytes the live prover replicas on `device` hold (key tables and lane buffers:
+// counted when a replica is complete, given back when it is destroyed) and the bytes of verifier keys and self-check contexts there
+// (verify_gpu.cpp's tally).  false: no such device / HIP error.
+bool device_memory_info(int device, uint64_t out[4]);
+size_t verifier_device_bytes(int device);      // verify_gpu.cpp
 
 // TEST HOOK: the fold of the redundant quotient bases by three group transforms (launch_quot_fold_dft) on caller-supplied bases; no key, no algorithm.
 // n = 2^L, 2 <= m <= n; perm: n entries, table position -> coset index (nullptr: the identity); u (m points) and v (n points, table order): 64 B canonical

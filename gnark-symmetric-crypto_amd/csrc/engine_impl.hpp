@@ -88,6 +88,19 @@ struct MsmSet {                     // one fixed-base MSM of the proving key (ke
 struct FewSolverChain { std::mutex m; hipEvent_t last = nullptr; };
 FewSolverChain& few_solver_chain(int device);      // one per device, never destroyed (lanes may outlive static destructors): engine_prove.hip
 
+// The engines' streams come from a process-wide pool and go back to it, drained, when an engine goes: the HIP runtime binds a stream to one of
+// its hardware queues when the stream is created, and a queue keeps the scratch memory its kernels needed for the life of the process.  An
+// engine built after a release on NEW streams lands on other queues, and the process grows by their scratch (measured once per queue: 632 MiB at
+// the next init, 250 MiB at its first call) — on the streams of the engine before it, it does not.  A stream is pooled under
+// (device, kind, role): kind = its priority level or STREAM_PLAIN (hipStreamCreate), role = what it does in the engine (STREAM_ROLE_INIT, or
+// 3 * lane + 0 / 1 / 2 for a lane's main / side / third stream), so that a queue sees the kernels it has seen.  Pooled streams are never destroyed.
+constexpr int STREAM_PLAIN = 1 << 30, STREAM_ROLE_INIT = -1;
+hipStream_t stream_take(int device, int kind, int role);            // the device is current; throws on a HIP error
+void stream_give(int device, int kind, int role, hipStream_t s);    // waits for the stream's work first
+
+// bytes the complete prover replicas on a device hold (AlgorithmImpl::accounted; gsc_memory_info): engine_tables.hip
+std::atomic<size_t>& prover_bytes_on(int device);
+
 class AlgorithmImpl {
   public:
     Cipher cipher; EngineConfig cfg;
@@ -207,7 +220,8 @@ class AlgorithmImpl {
         std::vector<ScratchNeed> need_at;
         bool wipe_a_pending = false;    // phase A of the chunk being proved is enqueued: phase B waits for it
         ~Lane() { if (ev_few) { for (int d = 0; d < 64; d++) { FewSolverChain& c = few_solver_chain(d); std::lock_guard<std::mutex> lk(c.m); if (c.last == ev_few) c.last = nullptr; } (void)hipEventDestroy(ev_few); }
-                  for (auto& e : ev) if (e) (void)hipEventDestroy(e); if (ev_ws) (void)hipEventDestroy(ev_ws); if (ev_wa) (void)hipEventDestroy(ev_wa); if (ev_wa_done) (void)hipEventDestroy(ev_wa_done); if (ev_ab) (void)hipEventDestroy(ev_ab); if (ev_fs) (void)hipEventDestroy(ev_fs); if (ev_b2) (void)hipEventDestroy(ev_b2); if (ev_s2) (void)hipEventDestroy(ev_s2); if (side2) (void)hipStreamDestroy(side2); if (side) (void)hipStreamDestroy(side); if (stream) (void)hipStreamDestroy(stream); }
+                  for (auto& e : ev) if (e) (void)hipEventDestroy(e); if (ev_ws) (void)hipEventDestroy(ev_ws); if (ev_wa) (void)hipEventDestroy(ev_wa); if (ev_wa_done) (void)hipEventDestroy(ev_wa_done); if (ev_ab) (void)hipEventDestroy(ev_ab); if (ev_fs) (void)hipEventDestroy(ev_fs); if (ev_b2) (void)hipEventDestroy(ev_b2); if (ev_s2) (void)hipEventDestroy(ev_s2); if (side2) stream_give(device, kind[2], 3 * index + 2, side2); if (side) stream_give(device, kind[1], 3 * index + 1, side); if (stream) stream_give(device, kind[0], 3 * index, stream); }
+        int device = 0, index = 0, kind[3] = {STREAM_PLAIN, STREAM_PLAIN, STREAM_PLAIN};      // where the three streams go back to (stream_give)
     };
     std::vector<std::unique_ptr<Lane>> lanes;
     size_t cap = 0;                     // proofs per full lane = the largest chunk
@@ -215,7 +229,10 @@ class AlgorithmImpl {
     static constexpr size_t SMALL_LANE_CAP = 1024;     // with full lanes larger than this; half of it otherwise (alloc in engine_tables.hip)
 
     AlgorithmImpl(Cipher c, const uint8_t* pk, size_t pk_len, const uint8_t* r1cs, size_t r1cs_len, const EngineConfig& cf);
-    ~AlgorithmImpl() { lanes.clear(); if (stream) (void)hipStreamDestroy(stream); }
+    ~AlgorithmImpl() { prover_bytes_on(cfg.device) -= accounted; lanes.clear(); if (stream) stream_give(cfg.device, STREAM_PLAIN, STREAM_ROLE_INIT, stream); }
+    // device bytes of the key tables and of every lane (alloc_lane's tally); accounted: what the constructor added to prover_bytes_on(device)
+    size_t held_bytes() const { size_t b = table_bytes; for (auto& ln : lanes) b += ln->allocated; return b; }
+    size_t accounted = 0;
 
     std::unique_ptr<SolverProgram> init_program(const R1csFile& cs);
 

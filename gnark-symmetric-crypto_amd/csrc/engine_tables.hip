@@ -6,6 +6,8 @@
 #include <chrono>
 #include <cstdio>
 #include <cstring>
+#include <map>
+#include <tuple>
 
 namespace gsc {
 
@@ -30,10 +32,10 @@ AlgorithmImpl::AlgorithmImpl(Cipher c, const uint8_t* pk, size_t pk_len, const u
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) throw std::runtime_error("no HIP device available: the GPU prover has no CPU fallback");
     HIP_CHECK(hipSetDevice(cfg.device));
-    HIP_CHECK(hipStreamCreate(&stream));
+    stream = stream_take(cfg.device, STREAM_PLAIN, STREAM_ROLE_INIT);
     // a refused key (a point off the curve or outside the subgroup, a wrong circuit) throws out of this constructor: the members free their
     // device memory as they unwind, and this gives the init stream back, so that a failed InitAlgorithm leaves nothing behind
-    struct StreamGuard { hipStream_t& s; bool armed = true; ~StreamGuard() { if (armed && s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); s = nullptr; } } } stream_guard{stream};
+    struct StreamGuard { hipStream_t& s; int device; bool armed = true; ~StreamGuard() { if (armed && s) { stream_give(device, STREAM_PLAIN, STREAM_ROLE_INIT, s); s = nullptr; } } } stream_guard{stream, cfg.device};
     { int cus = 0; if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, cfg.device) == hipSuccess && cus > 0) cu_count = cus; }
     const bool trace = cfg.trace_host;
     auto now = [] { return std::chrono::steady_clock::now(); };
@@ -74,6 +76,34 @@ AlgorithmImpl::AlgorithmImpl(Cipher c, const uint8_t* pk, size_t pk_len, const u
     if (trace) fprintf(stderr, "InitAlgorithm(%d): %zu lane(s) of %zu proofs + %d of %zu, %.0f ms\n", (int)c, nl, lane_cap, cfg.small_lanes, small_cap, ms(t3, now()));
     HIP_CHECK(hipStreamSynchronize(stream));
     stream_guard.armed = false;
+    // complete: from here to the destructor the replica's tables and lanes count as held on its device (gsc_memory_info)
+    accounted = held_bytes();
+    prover_bytes_on(cfg.device) += accounted;
+}
+
+namespace {
+struct StreamPool { std::mutex mu; std::map<std::tuple<int, int, int>, std::vector<hipStream_t>> idle; };
+StreamPool& stream_pool() { static StreamPool* const p = new StreamPool; return *p; }      // never destroyed: engines may go after the static destructors
+}  // namespace
+hipStream_t stream_take(int device, int kind, int role) {
+    {
+        StreamPool& p = stream_pool(); std::lock_guard<std::mutex> l(p.mu);
+        auto it = p.idle.find(std::make_tuple(device, kind, role));
+        if (it != p.idle.end() && !it->second.empty()) { hipStream_t s = it->second.back(); it->second.pop_back(); return s; }
+    }
+    hipStream_t s = nullptr;
+    if (kind == STREAM_PLAIN) HIP_CHECK(hipStreamCreate(&s)); else HIP_CHECK(hipStreamCreateWithPriority(&s, hipStreamDefault, kind));
+    return s;
+}
+void stream_give(int device, int kind, int role, hipStream_t s) {
+    (void)hipStreamSynchronize(s);
+    StreamPool& p = stream_pool(); std::lock_guard<std::mutex> l(p.mu);
+    p.idle[std::make_tuple(device, kind, role)].push_back(s);
+}
+
+std::atomic<size_t>& prover_bytes_on(int device) {
+    static std::atomic<size_t> held[64];
+    return held[device >= 0 && device < 64 ? device : 63];
 }
 
 std::unique_ptr<SolverProgram> AlgorithmImpl::init_program(const R1csFile& cs) {
@@ -441,7 +471,9 @@ void AlgorithmImpl::init_key(const R1csFile& cs, const PkFile& key) {
             const double nlanes = cfg.lanes > 0 ? cfg.lanes : (cs.has_commitment ? 2 : 1);
             const double lane = nlanes * (double)cfg.max_batch * ((double)n_wires * 32 + 3.0 * (double)domain_n * 32 + (double)domain_n * 2 * 20 + 1e5) * 1.15;
             const double others = (cfg.w_table_gb + (cfg.few_path ? cfg.few_z_gb + (cs.has_commitment ? 8 : 0) : 0)) * 1e9 + 8.0 * 1073741824.0;
-            const double room = (double)free_b - lane - others;
+            // (a replacement: what the outgoing engine holds on this device counts as free — the widths of a fresh InitAlgorithm once it is gone;
+            // whether both fit side by side until then is for the allocations below to find out)
+            const double room = (double)free_b + (double)cfg.reclaim_bytes - lane - others;
             if (room < budget) budget = room > 0 ? room : 0;
         }
         cfg.window_z = 4;
@@ -547,10 +579,10 @@ void AlgorithmImpl::alloc_lane(Lane& ln, size_t B) {
     if (cfg.stream_priorities && least != greatest) {
         const int code = cfg.stream_priorities == 1 ? 213 : cfg.stream_priorities;      // digits: main, side, third; 1 high, 2 normal, 3 low
         auto level = [&](int d) { return d == 1 ? greatest : d == 3 ? least : (least + greatest) / 2; };
-        HIP_CHECK(hipStreamCreateWithPriority(&ln.stream, hipStreamDefault, level(code / 100)));
-        HIP_CHECK(hipStreamCreateWithPriority(&ln.side, hipStreamDefault, level(code / 10 % 10)));
-        HIP_CHECK(hipStreamCreateWithPriority(&ln.side2, hipStreamDefault, level(code % 10)));
-    } else { HIP_CHECK(hipStreamCreate(&ln.stream)); HIP_CHECK(hipStreamCreate(&ln.side)); HIP_CHECK(hipStreamCreate(&ln.side2)); }
+        ln.kind[0] = level(code / 100); ln.kind[1] = level(code / 10 % 10); ln.kind[2] = level(code % 10);
+    }
+    ln.device = cfg.device; ln.index = (int)lanes.size() - 1;      // (the lane is the last of `lanes`: AlgorithmImpl's constructor)
+    ln.stream = stream_take(ln.device, ln.kind[0], 3 * ln.index); ln.side = stream_take(ln.device, ln.kind[1], 3 * ln.index + 1); ln.side2 = stream_take(ln.device, ln.kind[2], 3 * ln.index + 2);
     for (auto& e : ln.ev) HIP_CHECK(hipEventCreate(&e));
     HIP_CHECK(hipEventCreate(&ln.ev_ws));
     HIP_CHECK(hipEventCreateWithFlags(&ln.ev_wa, hipEventDisableTiming)); HIP_CHECK(hipEventCreateWithFlags(&ln.ev_wa_done, hipEventDisableTiming));

@@ -68,11 +68,15 @@ int verify_device() {
 }
 
 thread_local size_t* devbuf_tally = nullptr;      // build_key points this at the key's byte count: what its buffers take of device memory
+thread_local int devbuf_device = 0;               // ... and this at the key's device: the same bytes, summed per device (gsc_memory_info)
+std::atomic<size_t> g_device_bytes[64];           // what the live keys (the verifier's and the self-check contexts') hold on each device
+std::atomic<size_t>& device_bytes(int device) { return g_device_bytes[device >= 0 && device < 64 ? device : 63]; }
+struct Tallying { Tallying(size_t* t, int device) { devbuf_tally = t; devbuf_device = device; } ~Tallying() { devbuf_tally = nullptr; } };
 template <class T> struct DevBuf {
     T* p = nullptr;
-    size_t* tally = nullptr; size_t held = 0;      // the count this buffer is part of while it lives
-    void alloc(size_t n) { ck(hipMalloc(&p, n * sizeof(T) + 1), "hipMalloc"); tally = devbuf_tally; held = n * sizeof(T) + 1; if (tally) *tally += held; }
-    ~DevBuf() { if (p) { (void)hipFree(p); if (tally) *tally -= held; } }
+    size_t* tally = nullptr; size_t held = 0; int device = 0;      // the counts this buffer is part of while it lives
+    void alloc(size_t n) { ck(hipMalloc(&p, n * sizeof(T) + 1), "hipMalloc"); tally = devbuf_tally; device = devbuf_device; held = n * sizeof(T) + 1; if (tally) { *tally += held; device_bytes(device) += held; } }
+    ~DevBuf() { if (p) { (void)hipFree(p); if (tally) { *tally -= held; device_bytes(device) -= held; } } }
 };
 
 struct GpuKey {
@@ -106,8 +110,7 @@ struct GpuKey {
     DevBuf<uint8_t> cflag;
     ClaimBufs claim_bufs() {
         if (!cparts.p) {
-            devbuf_tally = &bytes;
-            struct Untally { ~Untally() { devbuf_tally = nullptr; } } untally;
+            Tallying tallying(&bytes, device);
             cparts.alloc(cap); cterms.alloc(cap * kBatchSums); crho.alloc(cap * 5); cfixed.alloc(cap * kBatchFixed);
             cpf.alloc(cap * kBatchFixed); cflag.alloc(cap);
         }
@@ -129,8 +132,7 @@ std::shared_ptr<GpuKey> build_key(int algo, const uint8_t* b, size_t n, int devi
     V::VkLayout lay; std::string err;
     if (!V::parse_vk_layout(b, n, lay, &err)) { printf("%s\n", err.c_str()); return nullptr; }
     auto k = std::make_shared<GpuKey>();
-    devbuf_tally = &k->bytes;
-    struct Untally { ~Untally() { devbuf_tally = nullptr; } } untally;
+    Tallying tallying(&k->bytes, device);
     k->device = device; k->cap = cap;
     k->few_max = few_max_setting();
     k->algo = algo;
@@ -232,8 +234,7 @@ bool route_few(GpuKey& k, size_t n) {
     const bool few = mode ? mode == kPathFew : n <= k.few_max;
     k.last_path = few ? kPathFew : kPathThread;
     if (few && !k.few_lines.p) {
-        devbuf_tally = &k.bytes;
-        struct Untally { ~Untally() { devbuf_tally = nullptr; } } untally;
+        Tallying tallying(&k.bytes, k.device);
         k.few_lines.alloc(k.few_cap() * kLineSteps);
     }
     return few;
@@ -650,6 +651,7 @@ std::shared_ptr<ProveCheckCtx> prove_check_create(int algo, const uint8_t* vk, s
     return c;
 }
 size_t prove_check_device_bytes(const ProveCheckCtx& c) { return c.key->bytes; }
+size_t verifier_device_bytes(int device) { return device_bytes(device).load(); }
 void prove_check_add_stats(const ProveCheckCtx& c, uint64_t out[4]) {
     out[0] += c.chunks.load(); out[1] += c.proofs.load(); out[2] += c.refused.load(); out[3] += c.fallbacks.load();
 }

@@ -295,6 +295,33 @@ extern int gsc_prove_check_stats(GoUint8 algorithmID, uint64_t out[4]);
  * curve.  An index past the chunk changes nothing.  Returns 0; -1 when hooks are off, the algorithm is not initialised or which / mode is none. */
 extern int gsc_debug_prove_corrupt(GoUint8 algorithmID, uint32_t index, int which, int mode);
 
+/* ---- key lifecycle (an addition): give an algorithm's tables back, or put another key in its place, without restarting the host ----
+ * A call — Prove, ProveBatch, gsc_prove_raw, every query — is served whole by the engine it found when it entered.  The calls below may run
+ * beside any number of such calls; those of one id serialise among themselves (and with InitAlgorithm of that id), and callers of the other
+ * ids are never held up.  InitAlgorithm on an initialised id still returns 1 and drops its key.
+ *
+ * gsc_release_algorithm: takes the algorithm out: from that instant Prove / ProveBatch answer "proving params are not initialized for cipher:
+ * ..." and gsc_prove_raw -1.  Then waits until every call that had entered is through (callers parked in the micro-batcher are served), checks
+ * that the idle engine's secret regions are at their idle image, and frees the engine, its lanes, its self-check contexts: all its device
+ * memory is back when the call returns, and InitAlgorithm works as in a fresh process.  1 = released; 0 = not initialised or unknown id. */
+extern GoUint8 gsc_release_algorithm(GoUint8 algorithmID);
+/* gsc_replace_algorithm: builds a complete new engine beside the serving one (all replicas of GSC_DEVICES; the environment as InitAlgorithm
+ * reads it), swaps, waits until the last call under the old key has left and frees the old engine.  1 = swapped: every call that enters from
+ * now on is served by the new key and the old key's memory is back.  0 = refused, with one line on stdout (a key that does not parse, a refused
+ * key point, a wrong circuit, a refused verifying key, device memory that does not hold both engines — release first, then InitAlgorithm): the
+ * old engine has served throughout and keeps serving, nothing of the attempt stays allocated, the generation does not move.  -1 = the id is not
+ * initialised (use InitAlgorithm).  The new engine takes the digit widths a fresh InitAlgorithm would choose once the old engine is gone.
+ * Self-check: a non-empty verifyingKey turns it on for the new engine under that key (refused key = refused replacement); an empty one leaves
+ * it off, or, with GSC_PROVE_CHECK=1, on under GSC_VK_DIR's file.  The old verifying key never checks a new key's proofs. */
+extern int gsc_replace_algorithm(GoUint8 algorithmID, GoSlice provingKey, GoSlice r1cs, GoSlice verifyingKey);
+/* out: free and total device memory (hipMemGetInfo), bytes held on that device by the provers (key tables and lane buffers of every complete
+ * engine replica), bytes held there by verifier keys and self-check contexts.  Returns 0; -1 for a device that does not exist. */
+extern int gsc_memory_info(int device, uint64_t out[4]);
+/* 0 while not initialised; 1 after InitAlgorithm; +1 per successful gsc_replace_algorithm; 0 again after a release.  gsc_describe ends in
+ * key=<first 16 hex digits of SHA-256 of the proving key's bytes> gen=<n>.  A caller who must know which key made a proof reads the
+ * generation before and after the call: equal values name it. */
+extern uint64_t gsc_key_generation(GoUint8 algorithmID);
+
 #ifdef __cplusplus
 }
 #endif
