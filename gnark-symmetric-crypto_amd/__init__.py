@@ -26,7 +26,8 @@ EXPORTS = ["enforce_binding", "InitAlgorithm", "Free", "Prove", "ProveBatch", "g
            "gsc_verify_json", "gsc_verify_last_path", "gsc_debug_verify_path", "gsc_debug_pairing_few",
            "gsc_verify_claims", "VerifyClaims",
            "gsc_prove_check_init", "gsc_prove_check_stats", "gsc_debug_prove_corrupt",
-           "gsc_release_algorithm", "gsc_replace_algorithm", "gsc_memory_info", "gsc_key_generation"]
+           "gsc_release_algorithm", "gsc_replace_algorithm", "gsc_memory_info", "gsc_key_generation",
+           "gsc_setup_contribute", "gsc_setup_verify_contribution", "gsc_debug_scale_points"]
 
 
 class GoSlice(C.Structure):
@@ -126,6 +127,12 @@ def lib():
         L.gsc_memory_info.argtypes = [C.c_int, C.POINTER(C.c_uint64)]
         L.gsc_key_generation.restype = C.c_uint64
         L.gsc_key_generation.argtypes = [C.c_ubyte]
+        L.gsc_setup_contribute.restype = C.c_int
+        L.gsc_setup_contribute.argtypes = [GoSlice, GoSlice, C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_void_p]
+        L.gsc_setup_verify_contribution.restype = C.c_int
+        L.gsc_setup_verify_contribution.argtypes = [GoSlice, GoSlice, GoSlice, GoSlice, C.c_char_p]
+        L.gsc_debug_scale_points.restype = C.c_int
+        L.gsc_debug_scale_points.argtypes = [C.c_int, C.c_char_p, C.c_char_p, C.c_size_t, C.c_char_p, C.c_void_p, C.c_void_p]
         L.enforce_binding()
         _lib = L
     return _lib
@@ -218,6 +225,48 @@ def prove_batch_bytes(params_json: bytes) -> bytes:
     """ProveBatch on an already encoded JSON array; returns the raw JSON bytes (bench.py keeps JSON work off the timed path)."""
     s, keep = _slice(params_json)
     return _take(lib().ProveBatch(s))
+
+
+CONTRIBUTION_BYTES = 224
+
+
+def setup_contribute(pk: bytes, vk: bytes, seed: bytes = None):
+    """gsc_setup_contribute: one contribution to the second phase of the key ceremony (include/libprove.h) -> (pk', vk', record).  seed
+    (32 bytes) fixes the secrets and needs the test hooks; None = the OS CSPRNG.  Raises RuntimeError with the return code (-1 seed without
+    hooks, -2 refused keys, -3 device error; the reason is on stdout)."""
+    s1, k1 = _slice(pk)
+    s2, k2 = _slice(vk)
+    p, v, np_, nv = C.c_void_p(), C.c_void_p(), C.c_size_t(), C.c_size_t()
+    rec = C.create_string_buffer(CONTRIBUTION_BYTES)
+    rc = lib().gsc_setup_contribute(s1, s2, seed, C.byref(p), C.byref(np_), C.byref(v), C.byref(nv), rec)
+    if rc != 0:
+        raise RuntimeError("gsc_setup_contribute failed: %d (see stdout)" % rc)
+    out = C.string_at(p.value, np_.value), C.string_at(v.value, nv.value), rec.raw
+    lib().Free(p); lib().Free(v)
+    return out
+
+
+def setup_verify_contribution(pk_prev: bytes, vk_prev: bytes, pk_next: bytes, vk_next: bytes, record: bytes) -> bool:
+    """gsc_setup_verify_contribution: is (pk_next, vk_next) a contribution to (pk_prev, vk_prev) that `record` proves?  A refusal names its
+    rule on stdout.  Raises RuntimeError on a device error."""
+    if len(record) != CONTRIBUTION_BYTES:
+        return False
+    keep = [_slice(b) for b in (pk_prev, vk_prev, pk_next, vk_next)]
+    rc = lib().gsc_setup_verify_contribution(keep[0][0], keep[1][0], keep[2][0], keep[3][0], record)
+    if rc < 0:
+        raise RuntimeError("gsc_setup_verify_contribution: device error (%d)" % rc)
+    return rc == 1
+
+
+def debug_scale_points(group: int, pts: bytes, inf: bytes, scalar: int):
+    """TEST HOOK: scalar * P for raw big-endian points (64 B in G1, 128 B in G2) through k_scale_points -> (points, infinity flags)."""
+    w = 64 if group == 0 else 128
+    n = len(inf)
+    assert len(pts) == w * n
+    out, oinf = C.create_string_buffer(max(1, w * n)), C.create_string_buffer(max(1, n))
+    if lib().gsc_debug_scale_points(group, pts, inf, n, int(scalar).to_bytes(32, "big"), out, oinf) != 0:
+        raise RuntimeError("gsc_debug_scale_points failed (see stdout)")
+    return out.raw[:w * n], oinf.raw[:n]
 
 
 def prove_raw(cipher: int, records: bytes, n: int):

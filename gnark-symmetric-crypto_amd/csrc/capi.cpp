@@ -12,6 +12,7 @@
 #include "host_ciphers.hpp"
 #include "json.hpp"
 #include "setup.hpp"
+#include "phase2_gpu.hpp"
 #include <sys/random.h>
 #include <cerrno>
 #include <condition_variable>
@@ -446,6 +447,37 @@ int gsc_setup(GoSlice r1cs, const uint8_t* seed32, void** pk, size_t* pk_len, vo
         *pk = a; *pk_len = k.pk.size(); *vk = b; *vk_len = k.vk.size();
         return 0;
     } catch (const std::exception& e) { printf("%s\n", e.what()); return -1; }
+}
+
+int gsc_setup_contribute(GoSlice pk, GoSlice vk, const uint8_t* seed32, void** pk_out, size_t* pk_len, void** vk_out, size_t* vk_len, uint8_t* record) {
+    if (!pk_out || !pk_len || !vk_out || !vk_len || !record) return -2;
+    *pk_out = *vk_out = nullptr; *pk_len = *vk_len = 0; memset(record, 0, GSC_CONTRIBUTION_BYTES);
+    if (seed32 && hooks_refused("gsc_setup_contribute with a caller-supplied seed")) return -1;      // deterministic secrets: test keys only
+    if (!pk.data || pk.len <= 0 || !vk.data || vk.len <= 0) { printf("gsc_setup_contribute: empty key\n"); return -2; }
+    try {
+        Phase2Step step;
+        const int rc = phase2_contribute((const uint8_t*)pk.data, (size_t)pk.len, (const uint8_t*)vk.data, (size_t)vk.len, seed32, step);
+        if (rc) return rc;
+        void* a = malloc(step.pk.size()); void* b = malloc(step.vk.size());
+        if (!a || !b) { free(a); free(b); return -3; }
+        memcpy(a, step.pk.data(), step.pk.size()); memcpy(b, step.vk.data(), step.vk.size());
+        *pk_out = a; *pk_len = step.pk.size(); *vk_out = b; *vk_len = step.vk.size();
+        memcpy(record, step.record, GSC_CONTRIBUTION_BYTES);
+        return 0;
+    } catch (const std::exception& e) { printf("gsc_setup_contribute: %s\n", e.what()); return -3; }
+}
+int gsc_setup_verify_contribution(GoSlice pk_prev, GoSlice vk_prev, GoSlice pk_next, GoSlice vk_next, const uint8_t* record) {
+    for (const GoSlice* k : {&pk_prev, &vk_prev, &pk_next, &vk_next}) if (!k->data || k->len <= 0) { printf("gsc_setup_verify_contribution: rule 1: empty key\n"); return 0; }
+    if (!record) { printf("gsc_setup_verify_contribution: rule 4: no record\n"); return 0; }
+    try {
+        return phase2_verify((const uint8_t*)pk_prev.data, (size_t)pk_prev.len, (const uint8_t*)vk_prev.data, (size_t)vk_prev.len,
+                             (const uint8_t*)pk_next.data, (size_t)pk_next.len, (const uint8_t*)vk_next.data, (size_t)vk_next.len, record);
+    } catch (const std::exception& e) { printf("gsc_setup_verify_contribution: %s\n", e.what()); return -3; }
+}
+int gsc_debug_scale_points(int group, const uint8_t* pts, const uint8_t* inf, size_t n, const uint8_t* scalar_be32, uint8_t* out, uint8_t* out_inf) {
+    if (hooks_refused("gsc_debug_scale_points") || !scalar_be32 || (n && (!pts || !inf || !out || !out_inf))) return -1;
+    try { phase2_debug_scale(group, pts, inf, n, scalar_be32, out, out_inf); return 0; }
+    catch (const std::exception& e) { printf("%s\n", e.what()); return -1; }
 }
 
 int gsc_set_deterministic_randomness(const uint8_t* r_be32, const uint8_t* s_be32, const uint8_t* mask_be32) {

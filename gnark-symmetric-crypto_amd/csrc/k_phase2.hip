@@ -1,0 +1,128 @@
+// Key ceremony, second phase (gsc_setup_contribute / gsc_setup_verify_contribution): the device side.
+//   k_scale_points<P>   one thread per point: out = k P for ONE scalar k shared by every thread.  k is toxic waste (x, 1/x or the Schnorr
+//                       nonce of a contribution), so the ladder takes the same steps whatever its bits are: every step is one doubling and
+//                       one exact addition of P that is always computed (madd<true>: it handles acc = infinity and acc = +-P), and the bit
+//                       only selects, limb by limb, which of the two values goes on.  k is read from memory word by word (uniform loads);
+//                       there is no private array indexed by a runtime value.  One inversion per thread makes the result affine.
+//   k_points_be<P>      decoded points -> raw big-endian bytes
+//   k_phase2_rlc, _sum  the verifier's two random combinations sum rho_i P_i, sum rho_i P'_i over Z and K: the batched verifier's 128-bit
+//                       scalar multiplication (verify_batch_dev.hpp g1_mul) and block sum (block_sum.hpp), then one block per sum.
+// Points are the verifier's decoded images (verify_dev.hpp VP1 / VP2), as k_verify_key_points leaves them.
+#include "phase2_kernels.hpp"
+#include "block_sum.hpp"
+
+namespace gsc {
+using namespace vfy;
+
+namespace {
+
+constexpr int kThreads = 64;
+
+template <class P> struct GroupOfPoint;
+template <> struct GroupOfPoint<VP1> { using F = bn254::Fp29f; using C = bn254::G1x; };
+template <> struct GroupOfPoint<VP2> { using F = bn254::Fp2x; using C = bn254::G2x; };
+
+// m all ones: a, m zero: b
+DEVFN fe9 pick(uint32_t m, const fe9& a, const fe9& b) {
+    fe9 r;
+#pragma unroll
+    for (int i = 0; i < 9; i++) r.l[i] = (int32_t)(((uint32_t)a.l[i] & m) | ((uint32_t)b.l[i] & ~m));
+    return r;
+}
+DEVFN fe9x2 pick(uint32_t m, const fe9x2& a, const fe9x2& b) { return fe9x2{pick(m, a.a0, b.a0), pick(m, a.a1, b.a1)}; }
+template <class F> DEVFN bn254::Xyzz9<F> pick(uint32_t m, const bn254::Xyzz9<F>& a, const bn254::Xyzz9<F>& b) {
+    bn254::Xyzz9<F> r;
+    r.x = pick(m, a.x, b.x); r.y = pick(m, a.y, b.y); r.zz = pick(m, a.zz, b.zz); r.zzz = pick(m, a.zzz, b.zzz);
+    r.inf = (((uint32_t)a.inf & m) | ((uint32_t)b.inf & ~m)) != 0;
+    return r;
+}
+
+DEVFN VP1 affine_of(const bn254::Xyzz9<bn254::Fp29f>& p) { return g1_affine(p); }
+DEVFN VP2 affine_of(const bn254::Xyzz9<bn254::Fp2x>& p) {
+    VP2 r;
+    if (p.inf || F2::is_zero(p.zz)) { r.x = F2::zero(); r.y = F2::zero(); r.inf = 1; return r; }
+    const auto a = bn254::G2x::to_aff(p);
+    r.x = red2(a.x); r.y = red2(a.y); r.inf = 0;
+    return r;
+}
+
+template <class P>
+__global__ __launch_bounds__(kThreads) void k_scale_points(const P* in, size_t n, const uint32_t* k, P* out) {
+    using G = GroupOfPoint<P>;
+    using C = typename G::C;
+    const size_t i = blockIdx.x * (size_t)kThreads + threadIdx.x;
+    if (i >= n) return;
+    const P p = in[i];
+    if (p.inf) { out[i] = p; return; }      // which points of a key are infinity is public
+    const bn254::Aff9<typename G::F> a{p.x, p.y};
+    bn254::Xyzz9<typename G::F> acc = C::infinity();
+    for (int b = 253; b >= 0; b--) {        // k < r < 2^254
+        acc = C::dbl(acc);
+        const bn254::Xyzz9<typename G::F> sum = C::template madd<true>(acc, a);
+        const uint32_t m = 0u - ((k[b >> 5] >> (b & 31)) & 1u);
+        acc = pick(m, sum, acc);
+    }
+    out[i] = affine_of(acc);
+}
+
+DEVFN void be32_of(const e1& v, uint8_t* o) {
+    const fe w = F::pack(F::from_mont(v));
+    for (int j = 0; j < 8; j++) for (int b = 0; b < 4; b++) o[4 * j + b] = (uint8_t)(w.l[7 - j] >> (24 - 8 * b));
+}
+DEVFN void point_be(const VP1& p, uint8_t* o) { be32_of(p.x, o); be32_of(p.y, o + 32); }
+DEVFN void point_be(const VP2& p, uint8_t* o) { be32_of(p.x.a1, o); be32_of(p.x.a0, o + 32); be32_of(p.y.a1, o + 64); be32_of(p.y.a0, o + 96); }
+
+template <class P>
+__global__ __launch_bounds__(kThreads) void k_points_be(const P* p, size_t n, uint8_t* out, uint8_t* inf) {
+    constexpr size_t W = sizeof(P) == sizeof(VP1) ? 64 : 128;
+    const size_t i = blockIdx.x * (size_t)kThreads + threadIdx.x;
+    if (i >= n) return;
+    const P v = p[i];
+    inf[i] = v.inf ? 1 : 0;
+    if (v.inf) { for (size_t j = 0; j < W; j++) out[W * i + j] = 0; return; }
+    point_be(v, out + W * i);
+}
+
+__global__ __launch_bounds__(kThreads) void k_phase2_rlc(const VP1* a, const VP1* b, const uint32_t* rho, size_t n, G1X* part) {
+    __shared__ G1X red[kThreads];
+    const size_t i = blockIdx.x * (size_t)kThreads + threadIdx.x;
+    const bool ok = i < n;
+    uint32_t r[4];
+    for (int w = 0; w < 4; w++) r[w] = ok ? rho[4 * i + w] : 0;
+    const G1X sa = block_sum<kThreads>(ok ? g1_mul(a[i], r, 128) : g1_inf(), red);
+    const G1X sb = block_sum<kThreads>(ok ? g1_mul(b[i], r, 128) : g1_inf(), red);
+    if (threadIdx.x == 0) { part[2 * blockIdx.x] = sa; part[2 * blockIdx.x + 1] = sb; }
+}
+// block j: sums[j] = the sum of part[2 b + j] over the nblk blocks of k_phase2_rlc
+__global__ __launch_bounds__(kThreads) void k_phase2_rlc_sum(const G1X* part, size_t nblk, VP1* sums) {
+    __shared__ G1X red[kThreads];
+    G1X acc = g1_inf();
+    for (size_t b = threadIdx.x; b < nblk; b += kThreads) acc = g1_add(acc, part[2 * b + blockIdx.x]);
+    const G1X total = block_sum<kThreads>(acc, red);
+    if (threadIdx.x == 0) sums[blockIdx.x] = g1_affine(total);
+}
+
+unsigned blocks(size_t n) { return (unsigned)((n + kThreads - 1) / kThreads); }
+
+}  // namespace
+
+void launch_scale_points(const VP1* in, size_t n, const uint32_t* k, VP1* out, hipStream_t s) {
+    if (n) hipLaunchKernelGGL(k_scale_points<VP1>, dim3(blocks(n)), dim3(kThreads), 0, s, in, n, k, out);
+}
+void launch_scale_points(const VP2* in, size_t n, const uint32_t* k, VP2* out, hipStream_t s) {
+    if (n) hipLaunchKernelGGL(k_scale_points<VP2>, dim3(blocks(n)), dim3(kThreads), 0, s, in, n, k, out);
+}
+void launch_points_be(const VP1* p, size_t n, uint8_t* out, uint8_t* inf, hipStream_t s) {
+    if (n) hipLaunchKernelGGL(k_points_be<VP1>, dim3(blocks(n)), dim3(kThreads), 0, s, p, n, out, inf);
+}
+void launch_points_be(const VP2* p, size_t n, uint8_t* out, uint8_t* inf, hipStream_t s) {
+    if (n) hipLaunchKernelGGL(k_points_be<VP2>, dim3(blocks(n)), dim3(kThreads), 0, s, p, n, out, inf);
+}
+size_t phase2_rlc_blocks(size_t n) { return blocks(n); }
+void launch_phase2_rlc(const VP1* a, const VP1* b, const uint32_t* rho, size_t n, G1X* part, VP1* sums, hipStream_t s) {
+    if (!n) return;
+    hipLaunchKernelGGL(k_phase2_rlc, dim3(blocks(n)), dim3(kThreads), 0, s, a, b, rho, n, part);
+    hipLaunchKernelGGL(k_phase2_rlc_sum, dim3(2), dim3(kThreads), 0, s, (const G1X*)part, (size_t)blocks(n), sums);
+}
+
+}  // namespace gsc

@@ -9,6 +9,7 @@
 #include "verify_batch_kernels.hpp"
 #include "verify_few_kernels.hpp"
 #include "verify_batch_dev.hpp"
+#include "block_sum.hpp"
 
 namespace gsc {
 using namespace vfy;
@@ -17,21 +18,6 @@ namespace {
 
 constexpr int kScaleThreads = 64;
 constexpr int kSumThreads = 64 * kBatchFixed;       // one wave per fixed point; waves 0..3 also reduce one total each
-
-// pairwise sums of v over the block's threads (n a power of two); every thread gets the total
-template <int N>
-__device__ G1X block_sum(G1X v, G1X* lds) {
-    const int t = threadIdx.x;
-    lds[t] = v;
-    __syncthreads();
-    for (int h = N / 2; h > 0; h >>= 1) {
-        if (t < h) lds[t] = g1_add(lds[t], lds[t + h]);
-        __syncthreads();
-    }
-    const G1X r = lds[0];
-    __syncthreads();
-    return r;
-}
 
 __global__ __launch_bounds__(kScaleThreads) void k_verify_batch_scale(const ProofDev* pd, const uint32_t* rnd, size_t n, int nsums, VP1* ra,
                                                                       uint8_t* okv, G1X* part, uint64_t* rpart) {

@@ -1,0 +1,17 @@
+// Launchers of the key ceremony's kernels (k_phase2.hip).  Types come from verify_dev.hpp.
+#pragma once
+#include <hip/hip_runtime.h>
+#include "verify_batch_dev.hpp"
+
+namespace gsc {
+// out[i] = k in[i] for decoded key points (infinity stays infinity); k: eight little-endian 32-bit words in device memory, 0 < k < r, the
+// same for every point.  The ladder does not branch on k's bits.
+void launch_scale_points(const vfy::VP1* in, size_t n, const uint32_t* k, vfy::VP1* out, hipStream_t s);
+void launch_scale_points(const vfy::VP2* in, size_t n, const uint32_t* k, vfy::VP2* out, hipStream_t s);
+// decoded points -> raw big-endian canonical bytes (G1: 64 B X | Y; G2: 128 B X.A1 | X.A0 | Y.A1 | Y.A0; zeros for infinity) and infinity flags
+void launch_points_be(const vfy::VP1* p, size_t n, uint8_t* out, uint8_t* inf, hipStream_t s);
+void launch_points_be(const vfy::VP2* p, size_t n, uint8_t* out, uint8_t* inf, hipStream_t s);
+// sums[0] = sum rho_i a[i], sums[1] = sum rho_i b[i], affine; rho: four little-endian words per point; part: 2 * phase2_rlc_blocks(n) entries
+size_t phase2_rlc_blocks(size_t n);
+void launch_phase2_rlc(const vfy::VP1* a, const vfy::VP1* b, const uint32_t* rho, size_t n, vfy::G1X* part, vfy::VP1* sums, hipStream_t s);
+}  // namespace gsc

@@ -600,6 +600,9 @@ int gsc_verify_debug_randomizers_impl(const uint8_t* seed32, int all_ones) {
     return 0;
 }
 
+// the verifier's device, for the key ceremony (phase2_gpu.cpp): GSC_DEVICE, or the first of GSC_DEVICES
+int gsc_verify_device_impl() { return verify_device(); }
+
 // gsc_debug_verify_path's body
 int gsc_verify_debug_path_impl(int mode) {
     if (mode < 0 || mode > 2) return -1;

@@ -322,6 +322,38 @@ extern int gsc_memory_info(int device, uint64_t out[4]);
  * generation before and after the call: equal values name it. */
 extern uint64_t gsc_key_generation(GoUint8 algorithmID);
 
+/* ---- key ceremony, second phase (an addition): several parties each re-randomise delta of a key pair, so that forging
+ * proofs under the final key needs every one of them to collude (or to have kept their secret).  tau, alpha, beta and gamma are NOT
+ * re-randomised: that is the first phase, which this library does not have.
+ * A contribution draws a secret x in [1, r) and makes, from (pk, vk) in gnark's layouts (points compressed or raw, as InitAlgorithm takes them),
+ * G1.Delta' = x G1.Delta and G2.Delta' = x G2.Delta in pk and vk, G1.Z'[k] = (1/x) G1.Z[k] and G1.K'[i] = (1/x) G1.K[i] in pk; every other byte
+ * of both files is copied; the rewritten points are written compressed.  The result is an ordinary key pair for InitAlgorithm,
+ * gsc_replace_algorithm, gsc_verify_init, libverify.so and gnark.
+ * The record (GSC_CONTRIBUTION_BYTES, this project's own format, NOT gnark's mpcsetup transcript): SHA-256(pk_prev) | SHA-256(pk_next) |
+ * G1.Delta' raw X | Y | T = k G1.Delta_prev raw | z = k + c x mod r, big-endian; c = the first 31 bytes, as a big-endian integer, of
+ * SHA-256("gsc-phase2-v1" | SHA-256(pk_prev) | Delta_prev raw | Delta' raw | T raw): a Schnorr proof that the contributor knows x.
+ * x and k come from the OS CSPRNG; with seed32 (TEST HOOKS only) x = SHA-256("gsc-phase2-x" | seed32) mod r, k = SHA-256("gsc-phase2-k" | seed32) mod r.
+ * Neither call needs an initialised algorithm or an R1CS; both run on GSC_DEVICE, or the first of GSC_DEVICES, and are thread-safe. */
+#define GSC_CONTRIBUTION_BYTES 224
+/* 0 on success: *pk_out / *vk_out malloc'd (release with Free), record filled.  -1: seed given without test hooks;
+ * -2: a key that does not parse / a refused point / pk and vk that disagree on delta; -3: device error.  On failure
+ * the outputs are NULL / 0, the record is zeroed, nothing stays allocated. */
+extern int gsc_setup_contribute(GoSlice pk, GoSlice vk, const uint8_t *seed32,
+                                void **pk_out, size_t *pk_len, void **vk_out, size_t *vk_len,
+                                uint8_t record[GSC_CONTRIBUTION_BYTES]);
+/* One step (prev, next, record) is accepted iff (1) both pairs parse and every point decodes as for InitAlgorithm / gsc_verify_init, neither delta
+ * at infinity; (2) outside delta, Z and K next equals prev BYTE FOR BYTE (a re-encoded key — raw for compressed — is refused); (3) pk and vk of each
+ * pair carry the same deltas; (4) the record's hashes and Delta' match the files; (5) z Delta_prev == T + c Delta'; (6) e(Delta'_1, G_2) =
+ * e(G_1, Delta'_2); (7) with fresh non-zero 128-bit rho_i from the OS CSPRNG, e(sum rho_i P'_i, Delta'_2) = e(sum rho_i P_i, Delta_prev_2) over Z and K.
+ * A wrong step is accepted with probability about 2^-128.
+ * 1 accepted, 0 refused (one line on stdout naming the first rule that failed), -3 device error. */
+extern int gsc_setup_verify_contribution(GoSlice pk_prev, GoSlice vk_prev, GoSlice pk_next, GoSlice vk_next,
+                                         const uint8_t record[GSC_CONTRIBUTION_BYTES]);
+/* TEST HOOK: out[i] = scalar * pts[i].  group 0 G1 (64 B X|Y), 1 G2 (128 B X.A1|X.A0|Y.A1|Y.A0), big-endian canonical;
+ * inf[i] != 0: infinity in, infinity out (flag in out_inf); scalar_be32 < r.  0 on success, -1 on error / hooks disabled. */
+extern int gsc_debug_scale_points(int group, const uint8_t *pts, const uint8_t *inf, size_t n,
+                                  const uint8_t *scalar_be32, uint8_t *out, uint8_t *out_inf);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,7 +3,16 @@
 gnark (reference keygen.go:341-352, :380-391, :419-430) for the R1CS files it ships.  Toxic waste comes from the OS CSPRNG.
 
   python tools/gsc_keygen.py <r1cs file> <pk out> <vk out>
-e.g. python tools/gsc_keygen.py r1cs.aes128 pk.aes128 vk.aes128      (needs a GPU: the group elements are computed there)"""
+e.g. python tools/gsc_keygen.py r1cs.aes128 pk.aes128 vk.aes128      (needs a GPU: the group elements are computed there)
+
+Key ceremony, second phase: every party re-randomises delta of the pair it was handed and passes the result
+on; anyone checks every link with the published records before the final pair is loaded.
+
+  python tools/gsc_keygen.py --contribute PK VK --out-dir D
+      writes D/<name of PK>, D/<name of VK> and D/contribution.record (224 bytes); the secret comes from the OS CSPRNG and is gone when the
+      command returns
+  python tools/gsc_keygen.py --verify-contribution PREV_PK PREV_VK NEXT_PK NEXT_VK RECORD
+      prints ACCEPTED (exit status 0) or REFUSED (exit status 1; the library's line above it names the rule that failed)"""
 import lzma
 import os
 import sys
@@ -12,13 +21,42 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
+def _read(path):
+    return lzma.open(path).read() if path.endswith(".xz") else open(path, "rb").read()
+
+
+def contribute(g, args):
+    if len(args) != 4 or args[2] != "--out-dir":
+        raise SystemExit(__doc__)
+    pk_path, vk_path, out = args[0], args[1], args[3]
+    names = [os.path.basename(p)[:-3] if p.endswith(".xz") else os.path.basename(p) for p in (pk_path, vk_path)]
+    if os.path.isdir(out) and any(os.path.abspath(os.path.join(out, n)) == os.path.abspath(p) for n, p in zip(names, (pk_path, vk_path))):
+        raise SystemExit("--out-dir holds the input keys: choose another directory")
+    pk, vk, record = g.setup_contribute(_read(pk_path), _read(vk_path))
+    os.makedirs(out, exist_ok=True)
+    for name, b in zip(names + ["contribution.record"], (pk, vk, record)):
+        open(os.path.join(out, name), "wb").write(b)
+    print("pk %d bytes, vk %d bytes, record %d bytes -> %s" % (len(pk), len(vk), len(record), out))
+
+
+def verify_contribution(g, args):
+    if len(args) != 5:
+        raise SystemExit(__doc__)
+    ok = g.setup_verify_contribution(*[_read(p) for p in args])
+    print("ACCEPTED" if ok else "REFUSED")
+    raise SystemExit(0 if ok else 1)
+
+
 def main():
+    import gsc_loader
+    if len(sys.argv) > 1 and sys.argv[1] == "--contribute":
+        return contribute(gsc_loader.load(), sys.argv[2:])
+    if len(sys.argv) > 1 and sys.argv[1] == "--verify-contribution":
+        return verify_contribution(gsc_loader.load(), sys.argv[2:])
     if len(sys.argv) != 4:
         raise SystemExit(__doc__)
-    import gsc_loader
     g = gsc_loader.load()
-    path = sys.argv[1]
-    r1cs = lzma.open(path).read() if path.endswith(".xz") else open(path, "rb").read()
+    r1cs = _read(sys.argv[1])
     pk, vk = g.setup(r1cs)
     open(sys.argv[2], "wb").write(pk)
     open(sys.argv[3], "wb").write(vk)
