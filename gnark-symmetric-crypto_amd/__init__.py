@@ -27,7 +27,8 @@ EXPORTS = ["enforce_binding", "InitAlgorithm", "Free", "Prove", "ProveBatch", "g
            "gsc_verify_claims", "VerifyClaims",
            "gsc_prove_check_init", "gsc_prove_check_stats", "gsc_debug_prove_corrupt",
            "gsc_release_algorithm", "gsc_replace_algorithm", "gsc_memory_info", "gsc_key_generation",
-           "gsc_setup_contribute", "gsc_setup_verify_contribution", "gsc_debug_scale_points"]
+           "gsc_setup_contribute", "gsc_setup_verify_contribution", "gsc_debug_scale_points",
+           "gsc_srs_verify", "gsc_debug_srs_generate", "gsc_debug_group_idft", "gsc_debug_column_sums", "gsc_setup_from_srs"]
 
 
 class GoSlice(C.Structure):
@@ -133,6 +134,16 @@ def lib():
         L.gsc_setup_verify_contribution.argtypes = [GoSlice, GoSlice, GoSlice, GoSlice, C.c_char_p]
         L.gsc_debug_scale_points.restype = C.c_int
         L.gsc_debug_scale_points.argtypes = [C.c_int, C.c_char_p, C.c_char_p, C.c_size_t, C.c_char_p, C.c_void_p, C.c_void_p]
+        L.gsc_srs_verify.restype = C.c_int
+        L.gsc_srs_verify.argtypes = [GoSlice]
+        L.gsc_debug_srs_generate.restype = C.c_int
+        L.gsc_debug_srs_generate.argtypes = [C.c_int, C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
+        L.gsc_setup_from_srs.restype = C.c_int
+        L.gsc_setup_from_srs.argtypes = [GoSlice, GoSlice, C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
+        L.gsc_debug_group_idft.restype = C.c_int
+        L.gsc_debug_group_idft.argtypes = [C.c_int, C.c_int, C.c_char_p, C.c_void_p, C.c_void_p]
+        L.gsc_debug_column_sums.restype = C.c_int
+        L.gsc_debug_column_sums.argtypes = [C.c_int, C.c_uint32, C.c_char_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_char_p, C.c_void_p, C.c_void_p]
         L.enforce_binding()
         _lib = L
     return _lib
@@ -266,6 +277,72 @@ def debug_scale_points(group: int, pts: bytes, inf: bytes, scalar: int):
     out, oinf = C.create_string_buffer(max(1, w * n)), C.create_string_buffer(max(1, n))
     if lib().gsc_debug_scale_points(group, pts, inf, n, int(scalar).to_bytes(32, "big"), out, oinf) != 0:
         raise RuntimeError("gsc_debug_scale_points failed (see stdout)")
+    return out.raw[:w * n], oinf.raw[:n]
+
+
+def srs_verify(srs: bytes) -> bool:
+    """gsc_srs_verify: is `srs` a well-formed powers file (include/libprove.h: this project's own format) whose elements are the powers they
+    claim to be?  A refusal names its rule on stdout.  Raises RuntimeError on a device error."""
+    s, keep = _slice(srs)
+    rc = lib().gsc_srs_verify(s)
+    if rc < 0:
+        raise RuntimeError("gsc_srs_verify: device error (%d)" % rc)
+    return rc == 1
+
+
+def setup_from_srs(r1cs: bytes, srs: bytes, seed: bytes = None):
+    """gsc_setup_from_srs: Groth16 Setup from a powers file -> (pk, vk) with delta = gamma = 1: FORGEABLE until at least one
+    setup_contribute.  seed (32 bytes) chooses gamma, delta, sigma, g as gsc_setup's seeded Setup does and needs the test hooks.  Raises
+    RuntimeError with the return code (-1 seed without hooks, -2 refused r1cs / file / L too small, -3 device error; the reason is on stdout)."""
+    s1, k1 = _slice(r1cs)
+    s2, k2 = _slice(srs)
+    pk, vk, npk, nvk = C.c_void_p(), C.c_void_p(), C.c_size_t(), C.c_size_t()
+    rc = lib().gsc_setup_from_srs(s1, s2, seed, C.byref(pk), C.byref(npk), C.byref(vk), C.byref(nvk))
+    if rc != 0:
+        raise RuntimeError("gsc_setup_from_srs failed: %d (see stdout)" % rc)
+    out = C.string_at(pk.value, npk.value), C.string_at(vk.value, nvk.value)
+    lib().Free(pk); lib().Free(vk)
+    return out
+
+
+def debug_srs_generate(L: int, seed: bytes) -> bytes:
+    """TEST HOOK: the powers file with N = 2^L for the tau, alpha, beta that gsc_setup derives from `seed` (32 bytes)."""
+    assert len(seed) == 32
+    p, n = C.c_void_p(), C.c_size_t()
+    if lib().gsc_debug_srs_generate(L, seed, C.byref(p), C.byref(n)) != 0:
+        raise RuntimeError("gsc_debug_srs_generate failed (see stdout)")
+    out = C.string_at(p.value, n.value)
+    lib().Free(p)
+    return out
+
+
+def debug_group_idft(group: int, L: int, pts: bytes):
+    """TEST HOOK: out[j] = (1/n) sum_k w^(-jk) pts[k] over n = 2^L raw points (64 B in G1, 128 B in G2) -> (points, infinity flags)."""
+    w, n = (64 if group == 0 else 128), 1 << L
+    assert len(pts) == w * n
+    out, oinf = C.create_string_buffer(w * n), C.create_string_buffer(n)
+    if lib().gsc_debug_group_idft(group, L, pts, out, oinf) != 0:
+        raise RuntimeError("gsc_debug_group_idft failed (see stdout)")
+    return out.raw[:w * n], oinf.raw[:n]
+
+
+def debug_column_sums(group: int, rows: bytes, columns, coeffs):
+    """TEST HOOK: the column-sum kernels on a caller's matrix.  rows: raw points; columns: one list of (row, coefficient id) per column;
+    coeffs: integers below r -> (points, infinity flags), one per column."""
+    w = 64 if group == 0 else 128
+    assert len(rows) % w == 0
+    start, trow, tco = [0], [], []
+    for col in columns:
+        for r, c in col:
+            trow.append(r); tco.append(c)
+        start.append(len(trow))
+    u32 = lambda v: (C.c_uint32 * max(1, len(v)))(*v)
+    a_start, a_row, a_co = u32(start), u32(trow), u32(tco)
+    cbe = b"".join(int(c).to_bytes(32, "big") for c in coeffs)
+    n = len(columns)
+    out, oinf = C.create_string_buffer(max(1, w * n)), C.create_string_buffer(max(1, n))
+    if lib().gsc_debug_column_sums(group, len(rows) // w, rows, n, a_start, a_row, a_co, len(coeffs), cbe, out, oinf) != 0:
+        raise RuntimeError("gsc_debug_column_sums failed (see stdout)")
     return out.raw[:w * n], oinf.raw[:n]
 
 

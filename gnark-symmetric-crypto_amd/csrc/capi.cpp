@@ -13,6 +13,7 @@
 #include "json.hpp"
 #include "setup.hpp"
 #include "phase2_gpu.hpp"
+#include "srs_gpu.hpp"
 #include <sys/random.h>
 #include <cerrno>
 #include <condition_variable>
@@ -478,6 +479,52 @@ int gsc_debug_scale_points(int group, const uint8_t* pts, const uint8_t* inf, si
     if (hooks_refused("gsc_debug_scale_points") || !scalar_be32 || (n && (!pts || !inf || !out || !out_inf))) return -1;
     try { phase2_debug_scale(group, pts, inf, n, scalar_be32, out, out_inf); return 0; }
     catch (const std::exception& e) { printf("%s\n", e.what()); return -1; }
+}
+
+int gsc_srs_verify(GoSlice srs) {
+    if (!srs.data || srs.len <= 0) { printf("gsc_srs_verify: rule 1: srs: empty file\n"); return 0; }
+    try { return srs_verify((const uint8_t*)srs.data, (size_t)srs.len); }
+    catch (const std::exception& e) { printf("gsc_srs_verify: %s\n", e.what()); return -3; }
+}
+int gsc_setup_from_srs(GoSlice r1cs, GoSlice srs, const uint8_t* seed32, void** pk, size_t* pk_len, void** vk, size_t* vk_len) {
+    if (!pk || !pk_len || !vk || !vk_len) return -2;
+    *pk = *vk = nullptr; *pk_len = *vk_len = 0;
+    if (seed32 && hooks_refused("gsc_setup_from_srs with a caller-supplied seed")) return -1;      // chosen gamma, delta, sigma: test keys only
+    if (!r1cs.data || r1cs.len <= 0 || !srs.data || srs.len <= 0) { printf("gsc_setup_from_srs: empty r1cs or powers file\n"); return -2; }
+    try {
+        SetupKeys k = setup_from_srs((const uint8_t*)r1cs.data, (size_t)r1cs.len, (const uint8_t*)srs.data, (size_t)srs.len, seed32);
+        void* a = malloc(k.pk.size()); void* b = malloc(k.vk.size());
+        if (!a || !b) { free(a); free(b); return -3; }
+        memcpy(a, k.pk.data(), k.pk.size()); memcpy(b, k.vk.data(), k.vk.size());
+        *pk = a; *pk_len = k.pk.size(); *vk = b; *vk_len = k.vk.size();
+        return 0;
+    } catch (const SrsRefused& e) { printf("gsc_setup_from_srs: %s\n", e.what()); return -2; }
+    catch (const std::exception& e) { printf("gsc_setup_from_srs: %s\n", e.what()); return -3; }
+}
+int gsc_debug_group_idft(int group, int L, const uint8_t* pts, uint8_t* out, uint8_t* out_inf) {
+    if (hooks_refused("gsc_debug_group_idft") || !pts || !out || !out_inf) return -1;
+    try { srs_debug_group_idft(group, L, pts, out, out_inf); return 0; }
+    catch (const std::exception& e) { printf("%s\n", e.what()); return -1; }
+}
+int gsc_debug_column_sums(int group, uint32_t n_rows, const uint8_t* rows, uint32_t n_cols, const uint32_t* col_start, const uint32_t* term_row, const uint32_t* term_coeff,
+                          uint32_t n_coeff, const uint8_t* coeff_be, uint8_t* out, uint8_t* out_inf) {
+    if (hooks_refused("gsc_debug_column_sums") || !col_start || (n_rows && !rows) || (n_coeff && !coeff_be) || (n_cols && (!out || !out_inf))) return -1;
+    if (col_start[n_cols] && (!term_row || !term_coeff)) return -1;
+    try { srs_debug_column_sums(group, n_rows, rows, n_cols, col_start, term_row, term_coeff, n_coeff, coeff_be, out, out_inf); return 0; }
+    catch (const std::exception& e) { printf("%s\n", e.what()); return -1; }
+}
+int gsc_debug_srs_generate(int L, const uint8_t* seed32, void** srs, size_t* len) {
+    if (!srs || !len) return -1;
+    *srs = nullptr; *len = 0;
+    if (hooks_refused("gsc_debug_srs_generate") || !seed32) return -1;
+    try {
+        const std::vector<uint8_t> f = srs_debug_generate(L, seed32, config_from_env().device);
+        void* a = malloc(f.size());
+        if (!a) return -1;
+        memcpy(a, f.data(), f.size());
+        *srs = a; *len = f.size();
+        return 0;
+    } catch (const std::exception& e) { printf("gsc_debug_srs_generate: %s\n", e.what()); return -1; }
 }
 
 int gsc_set_deterministic_randomness(const uint8_t* r_be32, const uint8_t* s_be32, const uint8_t* mask_be32) {

@@ -5,8 +5,10 @@
 //                       only selects, limb by limb, which of the two values goes on.  k is read from memory word by word (uniform loads);
 //                       there is no private array indexed by a runtime value.  One inversion per thread makes the result affine.
 //   k_points_be<P>      decoded points -> raw big-endian bytes
-//   k_phase2_rlc, _sum  the verifier's two random combinations sum rho_i P_i, sum rho_i P'_i over Z and K: the batched verifier's 128-bit
-//                       scalar multiplication (verify_batch_dev.hpp g1_mul) and block sum (block_sum.hpp), then one block per sum.
+//   k_phase2_rlc<P>, _sum<P>  a verifier's two random combinations sum rho_i a_i, sum rho_i b_i (a contribution's check: Z and K before and
+//                       after; a powers file's check, srs_gpu.cpp: a vector and itself shifted by one, in G1 and in G2): the batched
+//                       verifier's 128-bit scalar multiplication (verify_batch_dev.hpp g1_mul; the same walk over G2) and block sum
+//                       (block_sum.hpp), then one block per sum.
 // Points are the verifier's decoded images (verify_dev.hpp VP1 / VP2), as k_verify_key_points leaves them.
 #include "phase2_kernels.hpp"
 #include "block_sum.hpp"
@@ -21,6 +23,7 @@ constexpr int kThreads = 64;
 template <class P> struct GroupOfPoint;
 template <> struct GroupOfPoint<VP1> { using F = bn254::Fp29f; using C = bn254::G1x; };
 template <> struct GroupOfPoint<VP2> { using F = bn254::Fp2x; using C = bn254::G2x; };
+template <class P> using XyzzOf = bn254::Xyzz9<typename GroupOfPoint<P>::F>;      // VP1: G1X, VP2: G2X
 
 // m all ones: a, m zero: b
 DEVFN fe9 pick(uint32_t m, const fe9& a, const fe9& b) {
@@ -38,13 +41,7 @@ template <class F> DEVFN bn254::Xyzz9<F> pick(uint32_t m, const bn254::Xyzz9<F>&
 }
 
 DEVFN VP1 affine_of(const bn254::Xyzz9<bn254::Fp29f>& p) { return g1_affine(p); }
-DEVFN VP2 affine_of(const bn254::Xyzz9<bn254::Fp2x>& p) {
-    VP2 r;
-    if (p.inf || F2::is_zero(p.zz)) { r.x = F2::zero(); r.y = F2::zero(); r.inf = 1; return r; }
-    const auto a = bn254::G2x::to_aff(p);
-    r.x = red2(a.x); r.y = red2(a.y); r.inf = 0;
-    return r;
-}
+DEVFN VP2 affine_of(const bn254::Xyzz9<bn254::Fp2x>& p) { return g2_affine(p); }
 
 template <class P>
 __global__ __launch_bounds__(kThreads) void k_scale_points(const P* in, size_t n, const uint32_t* k, P* out) {
@@ -83,23 +80,40 @@ __global__ __launch_bounds__(kThreads) void k_points_be(const P* p, size_t n, ui
     point_be(v, out + W * i);
 }
 
-__global__ __launch_bounds__(kThreads) void k_phase2_rlc(const VP1* a, const VP1* b, const uint32_t* rho, size_t n, G1X* part) {
-    __shared__ G1X red[kThreads];
+// rho P over 128 bits, exact double-and-add: the batched verifier's g1_mul, and the same walk over G2
+DEVFN G1X rlc_mul(const VP1& p, const uint32_t* k) { return g1_mul(p, k, 128); }
+DEVFN G2X rlc_mul(const VP2& p, const uint32_t* k) {
+    G2X acc = bn254::G2x::infinity();
+    if (p.inf) return acc;
+    const bn254::Aff9<bn254::Fp2x> a{p.x, p.y};
+    for (int i = 127; i >= 0; i--) {
+        acc = bn254::G2x::dbl(acc);
+        if ((k[i >> 5] >> (i & 31)) & 1) acc = bn254::G2x::madd<true>(acc, a);
+    }
+    return acc;
+}
+
+template <class P>
+__global__ __launch_bounds__(kThreads) void k_phase2_rlc(const P* a, const P* b, const uint32_t* rho, size_t n, XyzzOf<P>* part) {
+    using C = typename GroupOfPoint<P>::C;
+    __shared__ XyzzOf<P> red[kThreads];
     const size_t i = blockIdx.x * (size_t)kThreads + threadIdx.x;
     const bool ok = i < n;
     uint32_t r[4];
     for (int w = 0; w < 4; w++) r[w] = ok ? rho[4 * i + w] : 0;
-    const G1X sa = block_sum<kThreads>(ok ? g1_mul(a[i], r, 128) : g1_inf(), red);
-    const G1X sb = block_sum<kThreads>(ok ? g1_mul(b[i], r, 128) : g1_inf(), red);
+    const XyzzOf<P> sa = block_sum<kThreads>(ok ? rlc_mul(a[i], r) : C::infinity(), red);
+    const XyzzOf<P> sb = block_sum<kThreads>(ok ? rlc_mul(b[i], r) : C::infinity(), red);
     if (threadIdx.x == 0) { part[2 * blockIdx.x] = sa; part[2 * blockIdx.x + 1] = sb; }
 }
 // block j: sums[j] = the sum of part[2 b + j] over the nblk blocks of k_phase2_rlc
-__global__ __launch_bounds__(kThreads) void k_phase2_rlc_sum(const G1X* part, size_t nblk, VP1* sums) {
-    __shared__ G1X red[kThreads];
-    G1X acc = g1_inf();
-    for (size_t b = threadIdx.x; b < nblk; b += kThreads) acc = g1_add(acc, part[2 * b + blockIdx.x]);
-    const G1X total = block_sum<kThreads>(acc, red);
-    if (threadIdx.x == 0) sums[blockIdx.x] = g1_affine(total);
+template <class P>
+__global__ __launch_bounds__(kThreads) void k_phase2_rlc_sum(const XyzzOf<P>* part, size_t nblk, P* sums) {
+    using C = typename GroupOfPoint<P>::C;
+    __shared__ XyzzOf<P> red[kThreads];
+    XyzzOf<P> acc = C::infinity();
+    for (size_t b = threadIdx.x; b < nblk; b += kThreads) acc = C::add(acc, part[2 * b + blockIdx.x]);
+    const XyzzOf<P> total = block_sum<kThreads>(acc, red);
+    if (threadIdx.x == 0) sums[blockIdx.x] = affine_of(total);
 }
 
 unsigned blocks(size_t n) { return (unsigned)((n + kThreads - 1) / kThreads); }
@@ -119,10 +133,12 @@ void launch_points_be(const VP2* p, size_t n, uint8_t* out, uint8_t* inf, hipStr
     if (n) hipLaunchKernelGGL(k_points_be<VP2>, dim3(blocks(n)), dim3(kThreads), 0, s, p, n, out, inf);
 }
 size_t phase2_rlc_blocks(size_t n) { return blocks(n); }
-void launch_phase2_rlc(const VP1* a, const VP1* b, const uint32_t* rho, size_t n, G1X* part, VP1* sums, hipStream_t s) {
+template <class P> static void launch_rlc_of(const P* a, const P* b, const uint32_t* rho, size_t n, XyzzOf<P>* part, P* sums, hipStream_t s) {
     if (!n) return;
-    hipLaunchKernelGGL(k_phase2_rlc, dim3(blocks(n)), dim3(kThreads), 0, s, a, b, rho, n, part);
-    hipLaunchKernelGGL(k_phase2_rlc_sum, dim3(2), dim3(kThreads), 0, s, (const G1X*)part, (size_t)blocks(n), sums);
+    hipLaunchKernelGGL(k_phase2_rlc<P>, dim3(blocks(n)), dim3(kThreads), 0, s, a, b, rho, n, part);
+    hipLaunchKernelGGL(k_phase2_rlc_sum<P>, dim3(2), dim3(kThreads), 0, s, (const XyzzOf<P>*)part, (size_t)blocks(n), sums);
 }
+void launch_phase2_rlc(const VP1* a, const VP1* b, const uint32_t* rho, size_t n, G1X* part, VP1* sums, hipStream_t s) { launch_rlc_of<VP1>(a, b, rho, n, part, sums, s); }
+void launch_phase2_rlc(const VP2* a, const VP2* b, const uint32_t* rho, size_t n, G2X* part, VP2* sums, hipStream_t s) { launch_rlc_of<VP2>(a, b, rho, n, part, sums, s); }
 
 }  // namespace gsc

@@ -14,6 +14,8 @@
 // is folded into V as well.
 #include "kernels.hpp"
 #include "bn254_fp29.hpp"
+#include "verify_dev.hpp"
+#include "group_idft.hpp"
 
 namespace gsc {
 using namespace bn254;
@@ -43,13 +45,16 @@ __device__ __forceinline__ fe qb_zeta(int L) {
 }
 
 // k * P for a canonical scalar k (8 little-endian words); exact group law throughout (init-time: clarity over speed)
-__device__ __noinline__ Xyzz9<Fp29f> qb_scalar_mul(const Xyzz9<Fp29f>& P, const fe& k) {
-    Xyzz9<Fp29f> acc = G1x::infinity();
+// F: the coordinate field (Fp29f: G1, Fp2x: G2)
+template <class F>
+__device__ __noinline__ Xyzz9<F> qb_scalar_mul(const Xyzz9<F>& P, const fe& k) {
+    using C = Curve9<F>;
+    Xyzz9<F> acc = C::infinity();
     int top = 255;
     while (top >= 0 && !((k.l[top >> 5] >> (top & 31)) & 1u)) top--;
     for (int i = top; i >= 0; i--) {
-        acc = G1x::dbl(acc);
-        if ((k.l[i >> 5] >> (i & 31)) & 1u) acc = G1x::add(acc, P);
+        acc = C::dbl(acc);
+        if ((k.l[i >> 5] >> (i & 31)) & 1u) acc = C::add(acc, P);
     }
     return acc;
 }
@@ -82,18 +87,43 @@ __global__ __launch_bounds__(64) void k_qb_load(const Aff<Fp>* zfile, const uint
 }
 
 // One decimation-in-time stage s (bit-reversed input, natural output after stage L - 1): pairs (j, j + 2^s) inside blocks of
-// 2^(s+1), twiddle w^-((j mod 2^s) << (L-1-s)).
+// 2^(s+1), twiddle w^-((j mod 2^s) << (L-1-s)).  Over either group (F: Fp29f for G1, Fp2x for G2; a point takes 4 F::WORDS elements of Y):
+// the quotient bases and the fold transform G1, the Lagrange bases of a powers file (launch_group_idft) both.
+template <class F>
 __global__ __launch_bounds__(64) void k_qb_stage(fe* Y, uint32_t half_n, int L, int s, const fe* tw) {
+    using C = Curve9<F>;
+    constexpr size_t W = 4 * F::WORDS;
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= half_n) return;
     const uint32_t half = 1u << s, lo = t & (half - 1), j = ((t >> s) << (s + 1)) + lo, e = lo << (L - 1 - s);
-    fe* pu = Y + 4 * (size_t)j; fe* pv = Y + 4 * (size_t)(j + half);
-    const Xyzz9<Fp29f> u = G1x::load_xyzz(pu);
-    Xyzz9<Fp29f> v = G1x::load_xyzz(pv);
+    fe* pu = Y + W * (size_t)j; fe* pv = Y + W * (size_t)(j + half);
+    const Xyzz9<F> u = C::load_xyzz(pu);
+    Xyzz9<F> v = C::load_xyzz(pv);
     if (e) v = qb_scalar_mul(v, tw[e]);
-    G1x::store_xyzz(pu, G1x::add(u, v));
-    v.y = Fp29::norm(Fp29::neg(v.y));
-    G1x::store_xyzz(pv, G1x::add(u, v));
+    C::store_xyzz(pu, C::add(u, v));
+    v.y = F::norm(F::neg(v.y));
+    C::store_xyzz(pv, C::add(u, v));
+}
+
+// The inputs of launch_group_idft: Y[bitrev(k)] = (1 / n) in[k] for decoded key points (verify_dev.hpp VP1 / VP2; infinity stays infinity)
+template <class P, class F>
+__global__ __launch_bounds__(64) void k_gt_load(const P* in, uint32_t n, int L, fe* Y) {
+    using C = Curve9<F>;
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    fe* dst = Y + 4 * F::WORDS * (size_t)(L ? __brev(k) >> (32 - L) : 0u);
+    const P p = in[k];
+    if (p.inf) { C::store_xyzz(dst, C::infinity()); return; }
+    const fe n_inv = Fr::from_mont(Fr::inv(Fr::from_u32(n)));
+    C::store_xyzz(dst, qb_scalar_mul(C::from_aff(Aff9<F>{p.x, p.y}), n_inv));
+}
+// ... and its outputs: natural order, affine, as decoded key points again
+__device__ __forceinline__ vfy::VP1 gt_affine(const Xyzz9<Fp29f>& p) { return vfy::g1_affine(p); }
+__device__ __forceinline__ vfy::VP2 gt_affine(const Xyzz9<Fp2x>& p) { return vfy::g2_affine(p); }
+template <class P, class F>
+__global__ __launch_bounds__(64) void k_gt_finish(const fe* Y, uint32_t n, P* out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = gt_affine(Curve9<F>::load_xyzz(Y + 4 * F::WORDS * (size_t)i));
 }
 
 // XYZZ -> affine bases in the layout the table builders take (8 x 32-bit Montgomery images); status 2 = the point at infinity
@@ -269,7 +299,7 @@ void launch_quot_fold_dft(int L, uint32_t m, const uint32_t* perm, const G1Aff* 
     launch_quot_fold_weights(cst, perm, L, m, pw, node, weight, yj, lam, s);
     if (weights_done) (void)hipEventRecord(weights_done, s);
     hipLaunchKernelGGL(k_qb_twiddles, dim3((hn + 63) / 64), dim3(64), 0, s, cst + 1, hn, tw);
-    auto transform = [&](fe* Y) { for (int st = 0; st < L; st++) hipLaunchKernelGGL(k_qb_stage, dim3((hn + 63) / 64), dim3(64), 0, s, Y, hn, L, st, tw); };
+    auto transform = [&](fe* Y) { for (int st = 0; st < L; st++) hipLaunchKernelGGL(k_qb_stage<Fp29f>, dim3((hn + 63) / 64), dim3(64), 0, s, Y, hn, L, st, tw); };
     hipLaunchKernelGGL(k_qfd_load, dim3(blocks), dim3(64), 0, s, reinterpret_cast<const Aff<Fp>*>(V), stV, perm, n, L, m, lam, What);
     transform(What);
     hipLaunchKernelGGL(k_qfd_pointwise, dim3(blocks), dim3(64), 0, s, What, n, L, 0, Ax);
@@ -290,13 +320,26 @@ void launch_g1_sum_be(const G1Xyzz* a, const G1Xyzz* b, size_t n, uint8_t* out, 
     if (n) hipLaunchKernelGGL(k_qf_sum_be, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, reinterpret_cast<const fe*>(a), reinterpret_cast<const fe*>(b), (uint32_t)n, out, flags);
 }
 
+size_t group_idft_scratch_bytes(int L, bool g2) { const size_t n = (size_t)1 << L; return (2 + n / 2) * sizeof(fe) + n * (g2 ? sizeof(G2Xyzz) : sizeof(G1Xyzz)); }
+template <class P, class F> static void group_idft(const P* in, int L, void* scratch, P* out, hipStream_t s) {
+    const uint32_t n = 1u << L, hn = n / 2;
+    fe* cst = static_cast<fe*>(scratch); fe* tw = cst + 2; fe* Y = tw + hn;
+    hipLaunchKernelGGL(k_qfd_consts, dim3(1), dim3(64), 0, s, L, cst);
+    hipLaunchKernelGGL(k_qb_twiddles, dim3((hn + 63) / 64), dim3(64), 0, s, cst + 1, hn, tw);
+    hipLaunchKernelGGL((k_gt_load<P, F>), dim3((n + 63) / 64), dim3(64), 0, s, in, n, L, Y);
+    for (int st = 0; st < L; st++) hipLaunchKernelGGL(k_qb_stage<F>, dim3((hn + 63) / 64), dim3(64), 0, s, Y, hn, L, st, tw);
+    hipLaunchKernelGGL((k_gt_finish<P, F>), dim3((n + 63) / 64), dim3(64), 0, s, (const fe*)Y, n, out);
+}
+void launch_group_idft(const vfy::VP1* in, int L, void* scratch, vfy::VP1* out, hipStream_t s) { group_idft<vfy::VP1, Fp29f>(in, L, scratch, out, s); }
+void launch_group_idft(const vfy::VP2* in, int L, void* scratch, vfy::VP2* out, hipStream_t s) { group_idft<vfy::VP2, Fp2x>(in, L, scratch, out, s); }
+
 void launch_quot_bases(const G1Aff* zfile, const uint8_t* zstatus, int L, int mode, const fe* omega_inv, const fe* n_inv,
                        fe* tw, G1Xyzz* scratch, const uint32_t* perm, G1Aff* out, uint8_t* status, hipStream_t s) {
     const uint32_t n = 1u << L, hn = n / 2;
     fe* Y = reinterpret_cast<fe*>(scratch);
     hipLaunchKernelGGL(k_qb_twiddles, dim3((hn + 63) / 64), dim3(64), 0, s, omega_inv, hn, tw);
     hipLaunchKernelGGL(k_qb_load, dim3((n + 63) / 64), dim3(64), 0, s, reinterpret_cast<const Aff<Fp>*>(zfile), zstatus, n, L, mode, omega_inv, n_inv, Y);
-    for (int st = 0; st < L; st++) hipLaunchKernelGGL(k_qb_stage, dim3((hn + 63) / 64), dim3(64), 0, s, Y, hn, L, st, tw);
+    for (int st = 0; st < L; st++) hipLaunchKernelGGL(k_qb_stage<Fp29f>, dim3((hn + 63) / 64), dim3(64), 0, s, Y, hn, L, st, tw);
     hipLaunchKernelGGL(k_qb_finish, dim3((n + 63) / 64), dim3(64), 0, s, Y, n, perm, reinterpret_cast<Aff<Fp>*>(out), status);
 }
 

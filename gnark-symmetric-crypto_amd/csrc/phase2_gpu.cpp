@@ -5,44 +5,19 @@
 // GSC_DEVICE / the first of GSC_DEVICES, so calls may run beside each other and beside proving.
 #include "phase2_gpu.hpp"
 #include "phase2.hpp"
-#include "phase2_kernels.hpp"
-#include "verify_kernels.hpp"
-#include <sys/random.h>
-#include <cerrno>
-#include <cstdio>
-#include <cstring>
-#include <stdexcept>
-#include <string>
+#include "ceremony_gpu.hpp"
 
 long long gsc_verify_debug_pairing_impl(const uint8_t* g1, const uint8_t* g2, size_t n, uint8_t* out, bool few);      // verify_gpu.cpp
-int gsc_verify_device_impl();                                                                                        // verify_gpu.cpp
 
 namespace gsc {
 using namespace vfy;
 using hostf::Fr;
 namespace P2 = phase2;
+using namespace cer;
 
 namespace {
 
-#define HIP_CHECK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) throw std::runtime_error(std::string("HIP error: ") + hipGetErrorString(e_) + " at " #expr); } while (0)
-
-struct Buf {
-    void* p = nullptr; size_t bytes = 0; bool secret = false;      // secret: zeroed before it is freed, also when an exception unwinds
-    explicit Buf(size_t n, bool is_secret = false) : bytes(n ? n : 1), secret(is_secret) { HIP_CHECK(hipMalloc(&p, bytes)); }
-    Buf(const Buf&) = delete; Buf& operator=(const Buf&) = delete;
-    ~Buf() { if (p) { if (secret) { (void)hipMemset(p, 0, bytes); (void)hipDeviceSynchronize(); } (void)hipFree(p); } }
-    template <class T> T* as() const { return static_cast<T*>(p); }
-};
-struct Stream {
-    hipStream_t s = nullptr;
-    Stream() { HIP_CHECK(hipSetDevice(gsc_verify_device_impl())); HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); }
-    Stream(const Stream&) = delete; Stream& operator=(const Stream&) = delete;
-    ~Stream() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } }
-};
-void need_device() {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) throw std::runtime_error("no HIP device available: the key ceremony computes on the GPU");
-}
+#define HIP_CHECK GSC_CER_HIP_CHECK
 
 // scalars that are toxic waste: cleared when the scope is left, normally or by an exception
 struct Secrets {
@@ -53,13 +28,6 @@ struct Secrets {
     ~Secrets() { explicit_bzero(&x, sizeof x); explicit_bzero(&x_inv, sizeof x_inv); explicit_bzero(&k, sizeof k); explicit_bzero(&t, sizeof t); explicit_bzero(words, sizeof words); }
 };
 void fr_to_le(const Fr& v, uint8_t out[32]) { hostf::U256 c = v.canon(); memcpy(out, c.w, 32); explicit_bzero(&c, sizeof c); }
-void os_random(void* out, size_t n) {      // OS CSPRNG bytes; a failure fails the call, never a fallback
-    for (size_t got = 0; got < n;) {
-        const ssize_t r = getrandom((uint8_t*)out + got, n - got, 0);
-        if (r > 0) got += (size_t)r;
-        else if (!(r < 0 && errno == EINTR)) throw std::runtime_error(std::string("getrandom failed: ") + strerror(errno));
-    }
-}
 Fr random_nonzero_fr() {      // uniform in [1, r) by rejection
     for (;;) {
         uint8_t be[32];
@@ -80,35 +48,10 @@ struct DevKey {
     VP1* p1() const { return g1.as<VP1>(); }
     VP2* p2() const { return g2.as<VP2>(); }
 };
-// false when a point is refused (st < 0)
-bool decode_slots(const std::vector<uint8_t>& s1, size_t n1, const std::vector<uint8_t>& s2, size_t n2, VP1* o1, VP2* o2, hipStream_t s) {
-    if (!(n1 + n2)) return true;
-    Buf d1(s1.size()), d2(s2.size()), st(n1 + n2);
-    if (n1) HIP_CHECK(hipMemcpyAsync(d1.p, s1.data(), s1.size(), hipMemcpyHostToDevice, s));
-    if (n2) HIP_CHECK(hipMemcpyAsync(d2.p, s2.data(), s2.size(), hipMemcpyHostToDevice, s));
-    launch_verify_key_points(d1.as<uint8_t>(), n1, d2.as<uint8_t>(), n2, o1, o2, st.as<int8_t>(), s);
-    HIP_CHECK(hipGetLastError());
-    std::vector<int8_t> hs(n1 + n2);
-    HIP_CHECK(hipMemcpyAsync(hs.data(), st.p, hs.size(), hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    for (int8_t v : hs) if (v < 0) return false;
-    return true;
-}
 bool decode_file(const uint8_t* b, DevKey& k, hipStream_t s) {
     std::vector<uint8_t> s1, s2;
     P2::slots(b, k.w.g1, 32, s1); P2::slots(b, k.w.g2, 64, s2);
     return decode_slots(s1, k.n1, s2, k.n2, k.p1(), k.p2(), s);
-}
-// raw big-endian bytes (and infinity flags) of n decoded points
-template <class P> void download(const P* p, size_t n, uint8_t* out, uint8_t* inf, hipStream_t s) {
-    constexpr size_t W = sizeof(P) == sizeof(VP1) ? 64 : 128;
-    if (!n) return;
-    Buf d(W * n), di(n);
-    launch_points_be(p, n, d.as<uint8_t>(), di.as<uint8_t>(), s);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipMemcpyAsync(out, d.p, W * n, hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipMemcpyAsync(inf, di.p, n, hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
 }
 // G1.Delta (64 B) and G2.Delta (128 B) of a decoded file; false when either is the point at infinity
 bool deltas(const DevKey& k, uint8_t d1[64], uint8_t d2[128], hipStream_t s) {
@@ -125,20 +68,6 @@ void scale_one(const VP1* p, const uint8_t k_be[32], uint8_t out[64], hipStream_
     HIP_CHECK(hipGetLastError());
     uint8_t inf;
     download(o.as<VP1>(), 1, out, &inf, s);
-}
-
-// one line on stdout; the caller returns rc (a refused step: 0; a refused contribution: -2)
-int refuse(const char* who, const std::string& why, int rc = 0) { printf("%s: %s\n", who, why.c_str()); return rc; }
-
-// the generators, raw big-endian: G1 (1, 2); G2 as gnark-crypto has it
-void generators(uint8_t g1[64], uint8_t g2[128]) {
-    static const char* const hex[4] = {"198e9393920d483a7260bfb731fb5d25f1aa493335a9e71297e485b7aef312c2", "1800deef121f1e76426a00665e5c4479674322d4f75edadd46debd5cd992f6ed",
-                                       "090689d0585ff075ec9e99ad690c3395bc4b313370b38ef355acdadcd122975b", "12c85ea5db8c6deb4aab71808dcb408fe3d1e7690c43d37b4ce6cc0166fa7daa"};
-    memset(g1, 0, 64); g1[31] = 1; g1[63] = 2;
-    for (int c = 0; c < 4; c++) for (int i = 0; i < 32; i++) {
-        auto nib = [](char ch) { return ch <= '9' ? ch - '0' : ch - 'a' + 10; };
-        g2[32 * c + i] = (uint8_t)(nib(hex[c][2 * i]) << 4 | nib(hex[c][2 * i + 1]));
-    }
 }
 
 }  // namespace
@@ -237,9 +166,7 @@ int phase2_verify(const uint8_t* pk_prev, size_t pk_prev_len, const uint8_t* vk_
     const size_t n = wpp.nz + wpp.nk;
     uint8_t sums[2][64] = {{0}}, sinf[2] = {1, 1};
     if (n) {
-        std::vector<uint32_t> rho(4 * n);
-        os_random(rho.data(), 16 * n);
-        for (size_t i = 0; i < n; i++) while (!(rho[4 * i] | rho[4 * i + 1] | rho[4 * i + 2] | rho[4 * i + 3])) os_random(&rho[4 * i], 16);
+        const std::vector<uint32_t> rho = random_rho(n);
         Buf d_rho(16 * n), part(sizeof(G1X) * 2 * phase2_rlc_blocks(n)), d_sums(2 * sizeof(VP1));
         HIP_CHECK(hipMemcpyAsync(d_rho.p, rho.data(), 16 * n, hipMemcpyHostToDevice, s));
         launch_phase2_rlc(kpp.p1() + wpp.z0, kpn.p1() + wpn.z0, d_rho.as<uint32_t>(), n, part.as<G1X>(), d_sums.as<VP1>(), s);

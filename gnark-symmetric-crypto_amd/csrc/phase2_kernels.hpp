@@ -14,4 +14,7 @@ void launch_points_be(const vfy::VP2* p, size_t n, uint8_t* out, uint8_t* inf, h
 // sums[0] = sum rho_i a[i], sums[1] = sum rho_i b[i], affine; rho: four little-endian words per point; part: 2 * phase2_rlc_blocks(n) entries
 size_t phase2_rlc_blocks(size_t n);
 void launch_phase2_rlc(const vfy::VP1* a, const vfy::VP1* b, const uint32_t* rho, size_t n, vfy::G1X* part, vfy::VP1* sums, hipStream_t s);
+// the same over G2 (one kernel template, k_phase2_rlc<P>)
+using G2X = bn254::Xyzz9<bn254::Fp2x>;
+void launch_phase2_rlc(const vfy::VP2* a, const vfy::VP2* b, const uint32_t* rho, size_t n, G2X* part, vfy::VP2* sums, hipStream_t s);
 }  // namespace gsc

@@ -45,7 +45,10 @@ struct WipeOnExit {      // wipes the listed scalars when the scope is left, nor
     WipeOnExit(const WipeOnExit&) = delete; WipeOnExit& operator=(const WipeOnExit&) = delete;
     ~WipeOnExit() { for (Fr* f : frs) wipe(*f); }
 };
-// One toxic scalar: hash_to_field(seed | label) — uniform in Fr up to 2^-128; never zero.
+}  // namespace
+
+// One toxic scalar: hash_to_field(seed | label) — uniform in Fr up to 2^-128; never zero.  (Declared in setup.hpp: the powers file of
+// the test hook gsc_debug_srs_generate derives tau, alpha and beta the same way.)
 Fr toxic(const uint8_t seed[32], const char* label) {
     uint8_t msg[64], h[48]; memcpy(msg, seed, 32); memset(msg + 32, 0, 32); strncpy((char*)msg + 32, label, 31);
     expand_message_xmd_sha256(msg, 64, "gsc-test-setup", h, 48);
@@ -53,6 +56,9 @@ Fr toxic(const uint8_t seed[32], const char* label) {
     wipe_bytes(msg, sizeof msg); wipe_bytes(h, sizeof h);      // the seed and the integer that reduces to the scalar
     return t.is_zero() ? Fr::one() : t;
 }
+
+namespace {
+
 void fr_to_le(const Fr& v, uint8_t* out) { const U256 c = v.canon(); memcpy(out, c.w, 32); }
 void store_mont(const Fp& v, uint8_t* out) { memcpy(out, v.v.w, 32); }
 
@@ -87,6 +93,63 @@ void put_g2(Out& o, const uint8_t* p_le, bool inf) {      // p_le: x.a0, x.a1, y
 
 }  // namespace
 
+void setup_generators_mont(uint8_t g1m[64], uint8_t g2m[128]) {
+    Fp::init();
+    store_mont(Fp::from_u64(1), g1m); store_mont(Fp::from_u64(2), g1m + 32);
+    store_mont(fp_from_hex("1800deef121f1e76426a00665e5c4479674322d4f75edadd46debd5cd992f6ed"), g2m);
+    store_mont(fp_from_hex("198e9393920d483a7260bfb731fb5d25f1aa493335a9e71297e485b7aef312c2"), g2m + 32);
+    store_mont(fp_from_hex("12c85ea5db8c6deb4aab71808dcb408fe3d1e7690c43d37b4ce6cc0166fa7daa"), g2m + 64);
+    store_mont(fp_from_hex("090689d0585ff075ec9e99ad690c3395bc4b313370b38ef355acdadcd122975b"), g2m + 96);
+}
+
+// The one writer of the key files (App. B.1 / B.2), for both Setups: every point as canonical little-endian affine coordinates with an
+// infinity flag, in the lists' fixed order (setup.hpp SetupLists).
+SetupKeys write_setup_keys(const R1csFile& cs, size_t n, const uint8_t* p1, const uint8_t* i1, const uint8_t* p2, const uint8_t* i2) {
+    Fr::init();
+    const size_t nw = cs.n_wires(), npub = cs.n_public, ncp = cs.commit_private.size();
+    const SetupLists ls(nw, n, ncp);
+    const size_t oA = ls.oA, oB = ls.oB, oK = ls.oK, oZ = ls.oZ, oS = ls.oS, o2B = ls.o2B, o2P = ls.o2P;
+    int lg = 0; while (((size_t)1 << lg) < n) lg++;
+    Fr omega = fr_from_hex("2a3c09f0a58a7e8500e0a7eb8ef62abc402d111e41112ed49bd61b6e725b19f0");
+    for (int i = lg; i < 28; i++) omega = omega.sq();
+    const Fr omega_inv = omega.inv(), n_inv = Fr::from_u64(n).inv(), g = Fr::from_u64(5), g_inv = g.inv();
+    std::vector<uint8_t> committed(nw, 0);
+    for (uint32_t w : cs.commit_private) committed[w] = 1;
+    auto g1 = [&](Out& o, size_t idx) { put_g1(o, &p1[64 * idx], i1[idx] != 0); };
+    auto g2 = [&](Out& o, size_t idx) { put_g2(o, &p2[128 * idx], i2[idx] != 0); };
+    auto in_pkK = [&](size_t i) { return i >= npub && !committed[i] && !(cs.has_commitment && i == cs.commit_wire); };
+    // ---- pk (App. B.1)
+    SetupKeys keys; Out pk;
+    pk.u64(n); pk.fr(n_inv); pk.fr(omega); pk.fr(omega_inv); pk.fr(g); pk.fr(g_inv); pk.b.push_back(1);
+    g1(pk, 0); g1(pk, 1); g1(pk, 2);
+    size_t nA = 0, nB = 0, nK = 0;
+    for (size_t i = 0; i < nw; i++) { nA += !i1[oA + i]; nB += !i1[oB + i]; nK += in_pkK(i); }
+    pk.u32((uint32_t)nA); for (size_t i = 0; i < nw; i++) if (!i1[oA + i]) g1(pk, oA + i);
+    pk.u32((uint32_t)nB); for (size_t i = 0; i < nw; i++) if (!i1[oB + i]) g1(pk, oB + i);
+    pk.u32((uint32_t)(n - 1)); for (size_t k = 0; k + 1 < n; k++) g1(pk, oZ + k);
+    pk.u32((uint32_t)nK); for (size_t i = 0; i < nw; i++) if (in_pkK(i)) g1(pk, oK + i);
+    g2(pk, 0); g2(pk, 2);
+    pk.u32((uint32_t)nB); for (size_t i = 0; i < nw; i++) if (!i1[oB + i]) g2(pk, o2B + i);
+    pk.u64(nw); pk.u64(nw - nA); pk.u64(nw - nB);
+    for (size_t i = 0; i < nw; i++) pk.b.push_back(i1[oA + i] ? 1 : 0);
+    for (size_t i = 0; i < nw; i++) pk.b.push_back(i1[oB + i] ? 1 : 0);
+    pk.u32(cs.has_commitment ? 1u : 0u);
+    if (cs.has_commitment) {      // Pedersen: Basis_j = K_j / gamma for the committed wires, BasisExpSigma = sigma * Basis
+        pk.u32((uint32_t)ncp); for (size_t j = 0; j < ncp; j++) g1(pk, oK + cs.commit_private[j]);
+        pk.u32((uint32_t)ncp); for (size_t j = 0; j < ncp; j++) g1(pk, oS + j);
+    }
+    // ---- vk (App. B.2)
+    Out vk;
+    g1(vk, 0); g1(vk, 1); g2(vk, 0); g2(vk, 1); g1(vk, 2); g2(vk, 2);
+    vk.u32((uint32_t)(npub + (cs.has_commitment ? 1 : 0)));
+    for (size_t i = 0; i < npub; i++) g1(vk, oK + i);
+    if (cs.has_commitment) g1(vk, oK + cs.commit_wire);
+    vk.u32(cs.has_commitment ? 1u : 0u); if (cs.has_commitment) vk.u32(0);
+    vk.u32(cs.has_commitment ? 1u : 0u); if (cs.has_commitment) { g2(vk, o2P); g2(vk, o2P + 1); }
+    keys.pk.swap(pk.b); keys.vk.swap(vk.b);
+    return keys;
+}
+
 SetupKeys groth16_setup(const uint8_t* r1cs, size_t r1cs_len, const uint8_t* seed32, int device) {
     Fr::init(); Fp::init();
     const R1csFile cs = parse_r1cs(r1cs, r1cs_len);
@@ -106,7 +169,7 @@ SetupKeys groth16_setup(const uint8_t* r1cs, size_t r1cs_len, const uint8_t* see
     // domain (gnark-crypto fft.NewDomain): generator of the 2^lg-th roots from the 2^28-th root, coset shift 5
     Fr omega = fr_from_hex("2a3c09f0a58a7e8500e0a7eb8ef62abc402d111e41112ed49bd61b6e725b19f0");
     for (int i = lg; i < 28; i++) omega = omega.sq();
-    const Fr omega_inv = omega.inv(), n_inv = Fr::from_u64(n).inv(), g = Fr::from_u64(5), g_inv = g.inv(), one = Fr::one();
+    const Fr n_inv = Fr::from_u64(n).inv(), one = Fr::one();
     // Lagrange basis at tau: L_j = (tau^n - 1) / n * w^j / (tau - w^j); one batch inversion
     tn = tau; for (int i = 0; i < lg; i++) tn = tn.sq();
     zt = tn - one;
@@ -167,11 +230,7 @@ SetupKeys groth16_setup(const uint8_t* r1cs, size_t r1cs_len, const uint8_t* see
     fr_to_le(ped_g, &sc2[32 * o2P]); fr_to_le((ped_g * sigma).neg(), &sc2[32 * (o2P + 1)]);
     // ---- generator multiples on the GPU
     uint8_t g1m[64], g2m[128];
-    store_mont(Fp::from_u64(1), g1m); store_mont(Fp::from_u64(2), g1m + 32);
-    store_mont(fp_from_hex("1800deef121f1e76426a00665e5c4479674322d4f75edadd46debd5cd992f6ed"), g2m);
-    store_mont(fp_from_hex("198e9393920d483a7260bfb731fb5d25f1aa493335a9e71297e485b7aef312c2"), g2m + 32);
-    store_mont(fp_from_hex("12c85ea5db8c6deb4aab71808dcb408fe3d1e7690c43d37b4ce6cc0166fa7daa"), g2m + 64);
-    store_mont(fp_from_hex("090689d0585ff075ec9e99ad690c3395bc4b313370b38ef355acdadcd122975b"), g2m + 96);
+    setup_generators_mont(g1m, g2m);
     std::vector<uint8_t> p1(64 * n1), i1(n1), p2(128 * n2), i2(n2);
     setup_generator_muls(device, false, g1m, sc1.data(), n1, p1.data(), i1.data());
     setup_generator_muls(device, true, g2m, sc2.data(), n2, p2.data(), i2.data());
@@ -180,39 +239,7 @@ SetupKeys groth16_setup(const uint8_t* r1cs, size_t r1cs_len, const uint8_t* see
     for (SecretVec<uint8_t>* v : {&sc1, &sc2}) wipe_bytes(v->data(), v->size());
     for (SecretVec<Fr>* v : {&L, &A, &B, &C, &K}) wipe_bytes(v->data(), v->size() * sizeof(Fr));
     for (Fr* f : toxic_guard.frs) wipe(*f);
-    auto g1 = [&](Out& o, size_t idx) { put_g1(o, &p1[64 * idx], i1[idx] != 0); };
-    auto g2 = [&](Out& o, size_t idx) { put_g2(o, &p2[128 * idx], i2[idx] != 0); };
-    auto in_pkK = [&](size_t i) { return i >= npub && !committed[i] && !(cs.has_commitment && i == cs.commit_wire); };
-    // ---- pk (App. B.1)
-    SetupKeys keys; Out pk;
-    pk.u64(n); pk.fr(n_inv); pk.fr(omega); pk.fr(omega_inv); pk.fr(g); pk.fr(g_inv); pk.b.push_back(1);
-    g1(pk, 0); g1(pk, 1); g1(pk, 2);
-    size_t nA = 0, nB = 0, nK = 0;
-    for (size_t i = 0; i < nw; i++) { nA += !i1[oA + i]; nB += !i1[oB + i]; nK += in_pkK(i); }
-    pk.u32((uint32_t)nA); for (size_t i = 0; i < nw; i++) if (!i1[oA + i]) g1(pk, oA + i);
-    pk.u32((uint32_t)nB); for (size_t i = 0; i < nw; i++) if (!i1[oB + i]) g1(pk, oB + i);
-    pk.u32((uint32_t)(n - 1)); for (size_t k = 0; k + 1 < n; k++) g1(pk, oZ + k);
-    pk.u32((uint32_t)nK); for (size_t i = 0; i < nw; i++) if (in_pkK(i)) g1(pk, oK + i);
-    g2(pk, 0); g2(pk, 2);
-    pk.u32((uint32_t)nB); for (size_t i = 0; i < nw; i++) if (!i1[oB + i]) g2(pk, o2B + i);
-    pk.u64(nw); pk.u64(nw - nA); pk.u64(nw - nB);
-    for (size_t i = 0; i < nw; i++) pk.b.push_back(i1[oA + i] ? 1 : 0);
-    for (size_t i = 0; i < nw; i++) pk.b.push_back(i1[oB + i] ? 1 : 0);
-    pk.u32(cs.has_commitment ? 1u : 0u);
-    if (cs.has_commitment) {      // Pedersen: Basis_j = K_j / gamma for the committed wires, BasisExpSigma = sigma * Basis
-        pk.u32((uint32_t)ncp); for (size_t j = 0; j < ncp; j++) g1(pk, oK + cs.commit_private[j]);
-        pk.u32((uint32_t)ncp); for (size_t j = 0; j < ncp; j++) g1(pk, oS + j);
-    }
-    // ---- vk (App. B.2)
-    Out vk;
-    g1(vk, 0); g1(vk, 1); g2(vk, 0); g2(vk, 1); g1(vk, 2); g2(vk, 2);
-    vk.u32((uint32_t)(npub + (cs.has_commitment ? 1 : 0)));
-    for (size_t i = 0; i < npub; i++) g1(vk, oK + i);
-    if (cs.has_commitment) g1(vk, oK + cs.commit_wire);
-    vk.u32(cs.has_commitment ? 1u : 0u); if (cs.has_commitment) vk.u32(0);
-    vk.u32(cs.has_commitment ? 1u : 0u); if (cs.has_commitment) { g2(vk, o2P); g2(vk, o2P + 1); }
-    keys.pk.swap(pk.b); keys.vk.swap(vk.b);
-    return keys;
+    return write_setup_keys(cs, n, p1.data(), i1.data(), p2.data(), i2.data());
 }
 
 }  // namespace gsc

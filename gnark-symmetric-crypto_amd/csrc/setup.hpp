@@ -10,6 +10,7 @@
 #include <cstdint>
 #include <cstddef>
 #include <vector>
+#include "host_field.hpp"
 
 namespace gsc {
 
@@ -22,5 +23,20 @@ SetupKeys groth16_setup(const uint8_t* r1cs, size_t r1cs_len, const uint8_t* see
 // little-endian images (G1: 64 B; G2: 128 B = x.a0, x.a1, y.a0, y.a1).  out: n affine points, canonical little-endian coordinates
 // (same order); inf[i] = 1 where the scalar was zero.
 void setup_generator_muls(int device, bool g2, const uint8_t* gen_mont, const uint8_t* scalars_le, size_t n, uint8_t* out, uint8_t* inf);
+// The order of the points both Setups hand to the one writer.  G1: [alpha, beta, delta | A (nw) | B (nw) | K (nw) | Z (n-1, file order:
+// position pos holds Z_bitrev(pos)) | sigma * basis (ncp)]; G2: [beta, gamma, delta | B (nw) | pedersen g, -sigma g].  K[i] is already divided
+// by gamma (public wires, the commitment wire, committed wires) or delta (the rest).
+struct SetupLists {
+    size_t oA, oB, oK, oZ, oS, n1, o2B, o2P, n2;
+    SetupLists(size_t nw, size_t n, size_t ncp) : oA(3), oB(oA + nw), oK(oB + nw), oZ(oK + nw), oS(oZ + (n - 1)), n1(oS + ncp), o2B(3), o2P(o2B + nw), n2(o2P + 2) {}
+};
+// pk (groth16.ProvingKey.WriteTo) and vk (VerifyingKey.WriteTo) from the lists: p1 / p2 canonical little-endian affine coordinates (64 B per
+// G1 point; 128 B per G2 point: x.a0, x.a1, y.a0, y.a1), i1 / i2 != 0 for the point at infinity.  n: the domain size.
+struct R1csFile;
+SetupKeys write_setup_keys(const R1csFile& cs, size_t n, const uint8_t* p1, const uint8_t* i1, const uint8_t* p2, const uint8_t* i2);
+// the generators' images as setup_generator_muls takes them
+void setup_generators_mont(uint8_t g1m[64], uint8_t g2m[128]);
+// One toxic scalar of a seeded (TEST) Setup: hash_to_field(seed | label), never zero.  The caller wipes it.  Call Fr::init() first.
+hostf::Fr toxic(const uint8_t seed[32], const char* label);
 
 }  // namespace gsc

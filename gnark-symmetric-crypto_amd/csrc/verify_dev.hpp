@@ -273,6 +273,14 @@ DEVFN VP1 g1_affine(const G1X& p) {
     r.x = red(a.x); r.y = red(a.y); r.inf = 0;
     return r;
 }
+// the same for G2 (the key ceremony's results: k_phase2.hip, k_quot_bases.hip's transform of a powers file, k_srs_columns.hip)
+DEVFN VP2 g2_affine(const bn254::Xyzz9<bn254::Fp2x>& p) {
+    VP2 r;
+    if (p.inf || F2::is_zero(p.zz)) { r.x = F2::zero(); r.y = F2::zero(); r.inf = 1; return r; }
+    const auto a = bn254::G2x::to_aff(p);
+    r.x = red2(a.x); r.y = red2(a.y); r.inf = 0;
+    return r;
+}
 // v 2^shift Q for one table entry (v < 256)
 DEVFN VP1 g1_small_mul(const VP1& q, uint32_t v, int shift) {
     if (q.inf || v == 0) { VP1 r; r.x = F::zero(); r.y = F::zero(); r.inf = 1; return r; }

@@ -354,6 +354,52 @@ extern int gsc_setup_verify_contribution(GoSlice pk_prev, GoSlice vk_prev, GoSli
 extern int gsc_debug_scale_points(int group, const uint8_t *pts, const uint8_t *inf, size_t n,
                                   const uint8_t *scalar_be32, uint8_t *out, uint8_t *out_inf);
 
+/* ---- key ceremony, first phase: the check of a powers file (an addition).  The result of a phase-1 ceremony is a file of
+ * group elements in which nobody needs to know tau, alpha or beta.  THIS PROJECT'S OWN FORMAT, version 1 — NOT snarkjs' .ptau and NOT gnark's
+ * mpcsetup format (neither can be pinned without those tools; a converter is not part of the library):
+ *   "gscsrs01" (8 B) | u32 big-endian L | tauG1[0 .. 2N-2] | tauG2[0 .. N-1] | alphaG1[0 .. N-1] | betaG1[0 .. N-1] | betaG2        N = 2^L
+ * tauG1[i] = tau^i G1, tauG2[i] = tau^i G2, alphaG1[i] = alpha tau^i G1, betaG1[i] = beta tau^i G1, betaG2 = beta G2; every element raw (flag
+ * bits 00; G1 64 B X | Y, G2 128 B X.A1 | X.A0 | Y.A1 | Y.A0, big-endian), none compressed, none at infinity; 1 <= L <= 24; the length is
+ * the one L gives, exactly.
+ * gsc_srs_verify accepts a file iff (1) magic, L and length are right and every element is raw, finite, canonical (< p), on the curve and, in
+ * G2, in the subgroup; (2) tauG1[0] and tauG2[0] are the generators; with fresh non-zero 128-bit rho_i from the OS CSPRNG, drawn anew for each
+ * rule, (3) e(sum rho_i tauG1[i+1], G_2) = e(sum rho_i tauG1[i], tauG2[1]) over i < 2N-2; (4) e(G_1, sum rho_i tauG2[i+1]) = e(tauG1[1],
+ * sum rho_i tauG2[i]) over i < N-1; (5) and (6) rule 3's equation over alphaG1 and over betaG1, i < N-1; (7) e(betaG1[0], G_2) = e(G_1, betaG2).
+ * A wrong file is accepted with probability about 2^-128.  The check shows that the file is the powers of SOME tau, alpha, beta; it does not
+ * show who made the file or that anybody discarded those scalars: that is what a ceremony's contribution records are for, and contributions
+ * to a powers file are not part of this library yet.
+ * 1 accepted, 0 refused (one line on stdout naming the first rule that failed), -3 device error.  Needs no initialised algorithm; runs on
+ * GSC_DEVICE, or the first of GSC_DEVICES, and is thread-safe. */
+extern int gsc_srs_verify(GoSlice srs);
+/* Groth16 Setup from a powers file: an ordinary gnark pk / vk (compressed points) for the R1CS, made from the file's group elements alone — no
+ * tau, alpha or beta is known to this call.  The Lagrange bases at tau, the column sums A_i(tau), B_i(tau), K_i and the Z_k are computed in the
+ * groups, on the device.  The call first runs gsc_srs_verify's whole check on the file.  A larger file serves a smaller circuit: with
+ * L > log2 n (n: the circuit's domain size, as gsc_setup computes it) the first 2n-1 / n elements are used.
+ * seed32 == NULL (the only mode a production host reaches): gamma = delta = 1, i.e. G1.Delta, G2.Delta and G2.Gamma are the generators.
+ * A KEY WITH DELTA = 1 IS FORGEABLE BY ANYONE.  It becomes usable only after at least one gsc_setup_contribute; a deployment verifies the file
+ * (gsc_srs_verify) and every link of the chain (gsc_setup_verify_contribution).  Without a commitment (ChaCha20-V3) the key is a deterministic
+ * function of (r1cs, file).  With one (AES-V2) the Pedersen sigma and g come from the OS CSPRNG and are wiped before the call returns:
+ * WHOEVER RUNS THIS CALL HOLDS SIGMA; a distributed sigma is not part of this library.  Public committed wires are refused, as by gsc_setup.
+ * seed32 != NULL (TEST HOOKS only): gamma, delta, sigma, g = gsc_setup's seeded scalars, applied to the unscaled points, so that the result
+ * equals gsc_setup(r1cs, seed32) byte for byte when the file holds the same seed's tau, alpha, beta (gsc_debug_srs_generate).
+ * 0 on success: *pk / *vk malloc'd (release with Free).  -1: a seed given without test hooks; -2: malformed r1cs, a file that gsc_srs_verify
+ * refuses, or L < log2 n (one line on stdout); -3: device error.  On failure the outputs are NULL / 0 and nothing stays allocated. */
+extern int gsc_setup_from_srs(GoSlice r1cs, GoSlice srs, const uint8_t *seed32, void **pk, size_t *pk_len, void **vk, size_t *vk_len);
+/* TEST HOOK: the powers file for tau, alpha, beta = gsc_setup's seeded toxic(seed32, "tau" | "alpha" | "beta"), 1 <= L <= 20: whoever holds
+ * the seed holds the scalars.  0 on success: *srs malloc'd (release with Free); -1 on error / hooks disabled, outputs NULL / 0. */
+extern int gsc_debug_srs_generate(int L, const uint8_t *seed32, void **srs, size_t *len);
+/* TEST HOOK: the group transform that turns powers of tau into the Lagrange basis at tau, out[j] = (1/n) sum_k w^(-jk) pts[k] over n = 2^L raw
+ * finite points (group 0: G1, 64 B; 1: G2, 128 B), w the generator of gsc_setup's domain of size n; natural order in and out; out_inf[j] = 1
+ * (and zeros) for the point at infinity.  1 <= L <= 17.  0 on success, -1 on error / hooks disabled. */
+extern int gsc_debug_group_idft(int group, int L, const uint8_t *pts, uint8_t *out, uint8_t *out_inf);
+/* TEST HOOK: the column sums of a sparse matrix over group elements, out[w] = sum over the terms t in [col_start[w], col_start[w+1]) of
+ * coeff[term_coeff[t]] * rows[term_row[t]], with the kernel's cut of long columns into segments.  rows: n_rows raw finite points of the group;
+ * col_start: n_cols + 1 offsets; coeff_be: n_coeff scalars below r, 32 big-endian bytes each; out_inf[w] = 1 for the point at infinity (an
+ * empty column, terms that cancel).  0 on success, -1 on error (a row that is not a finite point, an index out of range) / hooks disabled. */
+extern int gsc_debug_column_sums(int group, uint32_t n_rows, const uint8_t *rows, uint32_t n_cols, const uint32_t *col_start,
+                                 const uint32_t *term_row, const uint32_t *term_coeff, uint32_t n_coeff, const uint8_t *coeff_be,
+                                 uint8_t *out, uint8_t *out_inf);
+
 #ifdef __cplusplus
 }
 #endif

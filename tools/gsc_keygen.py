@@ -12,7 +12,16 @@ on; anyone checks every link with the published records before the final pair is
       writes D/<name of PK>, D/<name of VK> and D/contribution.record (224 bytes); the secret comes from the OS CSPRNG and is gone when the
       command returns
   python tools/gsc_keygen.py --verify-contribution PREV_PK PREV_VK NEXT_PK NEXT_VK RECORD
-      prints ACCEPTED (exit status 0) or REFUSED (exit status 1; the library's line above it names the rule that failed)"""
+      prints ACCEPTED (exit status 0) or REFUSED (exit status 1; the library's line above it names the rule that failed)
+
+Key ceremony, first phase: a key whose tau, alpha and beta nobody knows starts from a powers file (this project's own
+format, include/libprove.h — not snarkjs' .ptau, not gnark's mpcsetup).
+
+  python tools/gsc_keygen.py --verify-srs SRS
+      prints ACCEPTED (exit status 0) or REFUSED (exit status 1; the library's line above it names the rule that failed)
+  python tools/gsc_keygen.py --from-srs SRS R1CS PK VK
+      checks the file, then writes a key pair with delta = gamma = 1.  SUCH A KEY IS FORGEABLE BY ANYONE: it becomes usable only after at
+      least one --contribute, and a deployment verifies the file and every link of the chain"""
 import lzma
 import os
 import sys
@@ -47,8 +56,29 @@ def verify_contribution(g, args):
     raise SystemExit(0 if ok else 1)
 
 
+def verify_srs(g, args):
+    if len(args) != 1:
+        raise SystemExit(__doc__)
+    ok = g.srs_verify(_read(args[0]))
+    print("ACCEPTED" if ok else "REFUSED")
+    raise SystemExit(0 if ok else 1)
+
+
+def from_srs(g, args):
+    if len(args) != 4:
+        raise SystemExit(__doc__)
+    pk, vk = g.setup_from_srs(_read(args[1]), _read(args[0]))
+    open(args[2], "wb").write(pk)
+    open(args[3], "wb").write(vk)
+    print("pk %d bytes, vk %d bytes; delta = 1: NOT usable before at least one --contribute" % (len(pk), len(vk)))
+
+
 def main():
     import gsc_loader
+    if len(sys.argv) > 1 and sys.argv[1] == "--verify-srs":
+        return verify_srs(gsc_loader.load(), sys.argv[2:])
+    if len(sys.argv) > 1 and sys.argv[1] == "--from-srs":
+        return from_srs(gsc_loader.load(), sys.argv[2:])
     if len(sys.argv) > 1 and sys.argv[1] == "--contribute":
         return contribute(gsc_loader.load(), sys.argv[2:])
     if len(sys.argv) > 1 and sys.argv[1] == "--verify-contribution":
