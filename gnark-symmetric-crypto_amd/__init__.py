@@ -28,11 +28,25 @@ EXPORTS = ["enforce_binding", "InitAlgorithm", "Free", "Prove", "ProveBatch", "g
            "gsc_prove_check_init", "gsc_prove_check_stats", "gsc_debug_prove_corrupt",
            "gsc_release_algorithm", "gsc_replace_algorithm", "gsc_memory_info", "gsc_key_generation",
            "gsc_setup_contribute", "gsc_setup_verify_contribution", "gsc_debug_scale_points",
-           "gsc_srs_verify", "gsc_debug_srs_generate", "gsc_debug_group_idft", "gsc_debug_column_sums", "gsc_setup_from_srs"]
+           "gsc_srs_verify", "gsc_debug_srs_generate", "gsc_debug_group_idft", "gsc_debug_column_sums", "gsc_setup_from_srs", "gsc_debug_msm"]
 
 
 class GoSlice(C.Structure):
     _fields_ = [("data", C.c_void_p), ("len", C.c_longlong), ("cap", C.c_longlong)]
+
+
+class DebugMsmArgs(C.Structure):      # struct gsc_debug_msm_args of include/libprove.h
+    _fields_ = [("group", C.c_int32), ("nbases", C.c_uint32),
+                ("points", C.c_char_p), ("kind", C.c_char_p), ("rowlen", C.c_void_p), ("rows", C.c_void_p),
+                ("n_rows", C.c_uint32), ("zero_row", C.c_uint32),
+                ("c", C.c_int32), ("cv", C.c_int32), ("mont", C.c_int32),
+                ("batch", C.c_uint32), ("nproofs", C.c_uint32), ("per_flat", C.c_uint32), ("per_win", C.c_uint32), ("digit_bases", C.c_uint32),
+                ("digit_rows", C.c_void_p), ("scalars_be", C.c_char_p),
+                ("plane", C.c_char_p), ("plane_rows", C.c_uint32), ("plane_stride", C.c_uint32),
+                ("out", C.c_void_p), ("out_inf", C.c_void_p),
+                ("flat_digits", C.c_void_p), ("flat_digits_cap", C.c_size_t), ("win_digits", C.c_void_p), ("win_digits_cap", C.c_size_t),
+                ("gok", C.c_void_p), ("gok_cap", C.c_size_t), ("group_ok", C.c_void_p), ("group_ok_cap", C.c_size_t),
+                ("info", C.c_void_p)]
 
 
 class ProveReturn(C.Structure):
@@ -142,6 +156,8 @@ def lib():
         L.gsc_setup_from_srs.argtypes = [GoSlice, GoSlice, C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
         L.gsc_debug_group_idft.restype = C.c_int
         L.gsc_debug_group_idft.argtypes = [C.c_int, C.c_int, C.c_char_p, C.c_void_p, C.c_void_p]
+        L.gsc_debug_msm.restype = C.c_int
+        L.gsc_debug_msm.argtypes = [C.POINTER(DebugMsmArgs)]
         L.gsc_debug_column_sums.restype = C.c_int
         L.gsc_debug_column_sums.argtypes = [C.c_int, C.c_uint32, C.c_char_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_char_p, C.c_void_p, C.c_void_p]
         L.enforce_binding()
@@ -344,6 +360,38 @@ def debug_column_sums(group: int, rows: bytes, columns, coeffs):
     if lib().gsc_debug_column_sums(group, len(rows) // w, rows, n, a_start, a_row, a_co, len(coeffs), cbe, out, oinf) != 0:
         raise RuntimeError("gsc_debug_column_sums failed (see stdout)")
     return out.raw[:w * n], oinf.raw[:n]
+
+
+def debug_msm(group: int, points: bytes, kind, rowlen, rows, scalars, n_rows: int, zero_row: int, c: int, cv: int = 0, mont: int = 1, batch: int = 64,
+              nproofs: int = 0, per_flat: int = 0, per_win: int = 0, digit_rows=None, plane: bytes = None, plane_rows: int = 0, plane_stride: int = 0):
+    """TEST HOOK: the MSM kernels on a caller's bases (raw points; kind 0 bit / 1 narrow of rowlen entries / 2 wide; scalar row per base) and
+    scalars (n_rows x batch integers below r, row-major); see gsc_debug_msm in include/libprove.h.  digit_rows: the rows the windowed digits
+    are laid out for when that is more than the wide bases.  -> dict: out (canonical little-endian coordinates per column), inf, flat_digits,
+    win_digits, gok, group_ok (bytes as the kernels store them) and info (64 integers)."""
+    w = 64 if group == 0 else 128
+    n = len(kind)
+    assert len(points) == w * n and len(rowlen) == n and len(rows) == n and len(scalars) == n_rows * batch
+    u32 = lambda v: (C.c_uint32 * max(1, len(v)))(*v)
+    a_len, a_rows, a_drows = u32(rowlen), u32(rows), u32(digit_rows or [])
+    sbe = b"".join(int(v).to_bytes(32, "big") for v in scalars)
+    ncols = nproofs or batch
+    nwide = sum(1 for k in kind if k == 2)
+    # capacities from upper bounds: at most 9 window octets per wide base (cv = 4: 65 windows), 65 windows at c = 4, two words per digit octet at c = 17
+    flat_cap = 16 * batch * ((n + 7) // 8 + 1 + 9 * nwide)
+    win_cap = 16 * batch * 65 * ((max(nwide, len(digit_rows or [])) + 7) // 8) * (2 if c > 16 else 1)
+    gok_cap, gr_cap = 32 * ((n + 7) // 8) + 1, (n + 7) // 8 + 1
+    out, oinf = C.create_string_buffer(w * ncols), C.create_string_buffer(ncols)
+    fd, wd, gk, gr = C.create_string_buffer(flat_cap), C.create_string_buffer(max(1, win_cap)), C.create_string_buffer(gok_cap), C.create_string_buffer(gr_cap)
+    info = (C.c_uint32 * 64)()
+    vp = lambda b: C.cast(b, C.c_void_p)
+    args = DebugMsmArgs(group, n, points, bytes(kind), vp(a_len), vp(a_rows), n_rows, zero_row, c, cv, mont, batch, nproofs, per_flat, per_win,
+                        len(digit_rows or []), vp(a_drows) if digit_rows else None, sbe, plane, plane_rows, plane_stride, vp(out), vp(oinf),
+                        vp(fd), flat_cap, vp(wd), max(1, win_cap), vp(gk), gok_cap, vp(gr), gr_cap, vp(info))
+    if lib().gsc_debug_msm(C.byref(args)) != 0:
+        raise RuntimeError("gsc_debug_msm failed (see stdout)")
+    info = list(info)
+    return {"out": out.raw[:w * ncols], "inf": oinf.raw[:ncols], "flat_digits": fd.raw[:info[48]], "win_digits": wd.raw[:info[49]],
+            "gok": gk.raw[:info[50]], "group_ok": gr.raw[:info[51]], "info": info}
 
 
 def prove_raw(cipher: int, records: bytes, n: int):

@@ -14,6 +14,7 @@
 #include "setup.hpp"
 #include "phase2_gpu.hpp"
 #include "srs_gpu.hpp"
+#include "msm_debug.hpp"
 #include <sys/random.h>
 #include <cerrno>
 #include <condition_variable>
@@ -511,6 +512,11 @@ int gsc_debug_column_sums(int group, uint32_t n_rows, const uint8_t* rows, uint3
     if (hooks_refused("gsc_debug_column_sums") || !col_start || (n_rows && !rows) || (n_coeff && !coeff_be) || (n_cols && (!out || !out_inf))) return -1;
     if (col_start[n_cols] && (!term_row || !term_coeff)) return -1;
     try { srs_debug_column_sums(group, n_rows, rows, n_cols, col_start, term_row, term_coeff, n_coeff, coeff_be, out, out_inf); return 0; }
+    catch (const std::exception& e) { printf("%s\n", e.what()); return -1; }
+}
+int gsc_debug_msm(const gsc_debug_msm_args* args) {
+    if (hooks_refused("gsc_debug_msm") || !args) return -1;
+    try { debug_msm(config_from_env().device, *args); return 0; }
     catch (const std::exception& e) { printf("%s\n", e.what()); return -1; }
 }
 int gsc_debug_srs_generate(int L, const uint8_t* seed32, void** srs, size_t* len) {

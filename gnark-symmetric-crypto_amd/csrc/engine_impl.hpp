@@ -66,6 +66,34 @@ struct KeyPoints {
 std::vector<uint8_t> decode_g1_points(const KeyPoints& pts, G1Aff* out, hipStream_t stream);
 std::vector<uint8_t> decode_g2_points(const KeyPoints& pts, G2Aff* out, hipStream_t stream);
 
+// Slice partials -> one sum per column: reduction levels over the ping-pong buffers pa (the partials) and pb until one group is left, which goes to
+// `out`.  levels (optional, the test hook gsc_debug_msm): the slices entering every level and whether it took the by-proof kernel.
+template <class XyzzT>
+inline void msm_reduce_slices(hipStream_t st, XyzzT* pa, XyzzT* pb, size_t nslices, size_t cols, XyzzT* out, std::vector<std::pair<size_t, bool>>* levels = nullptr) {
+    XyzzT* src = pa; XyzzT* alt = pb; size_t ns = nslices;
+    for (;;) {
+        const size_t groups = msm_reduce_groups(ns, cols);
+        XyzzT* dst = groups == 1 ? out : alt;
+        if (levels) levels->emplace_back(ns, msm_reduce_by_proof(ns, cols));
+        launch_msm_reduce(src, ns, cols, dst, st);
+        if (groups == 1) break;
+        XyzzT* t = src; src = dst; alt = t; ns = groups;
+    }
+}
+// the same for the first `npr` columns of every row of `stride` (latency path: nobody reads the padding proofs' columns)
+template <class XyzzT>
+inline void msm_reduce_slices_few(hipStream_t st, XyzzT* pa, XyzzT* pb, size_t nslices, size_t cols, size_t stride, size_t npr, XyzzT* out, std::vector<std::pair<size_t, bool>>* levels = nullptr) {
+    XyzzT* src = pa; XyzzT* alt = pb; size_t ns = nslices;
+    for (;;) {
+        const size_t groups = (ns + 63) / 64;
+        XyzzT* dst = groups == 1 ? out : alt;
+        if (levels) levels->emplace_back(ns, false);
+        launch_msm_reduce_few(src, ns, cols, stride, npr, dst, st);
+        if (groups == 1) break;
+        XyzzT* t = src; src = dst; alt = t; ns = groups;
+    }
+}
+
 template <class AffT>
 struct MsmSet {                     // one fixed-base MSM of the proving key (kernels.hpp, "multi-scalar multiplication")
     size_t nbases = 0;              // bases of the key in this set
@@ -273,17 +301,7 @@ class AlgorithmImpl {
 
     void alloc_lane(Lane& ln, size_t B);
 
-    // Waves of an MSM launch = slices x windows x groups of 64 proofs (windows = 1 for the flat kernel).  Slices of up to `most`
-    // bases (256: few partial sums to reduce, a tail of < 2 % at full batches; measured 64 .. 512: kernel time within 1 %, reductions -3 ms); shorter ones when that would leave fewer than ~8k waves,
-    // so that a small batch still spreads over the whole chip.
-    static size_t msm_slices(size_t nbases, size_t nwin, size_t most, size_t B, size_t& per) {
-        const size_t gw = (B / 64) * nwin, want = (8192 + gw - 1) / gw;
-        size_t n = (nbases + most - 1) / most; if (n < want) n = want;
-        n = (n + 7) & ~(size_t)7;
-        per = ((nbases + n - 1) / n + 7) & ~(size_t)7; if (!per) per = 8;
-        n = (nbases + per - 1) / per;
-        return n ? n : 1;
-    }
+    // (slices of an MSM launch: msm_slices, msm_layout.hpp)
     RouteFacts route_facts() const { return RouteFacts{small.ok, has_commitment, quotient_eval, fuse_z_digits, mZfew.nflat != 0, mA.latency_flat(), mB1.latency_flat(), mB2.latency_flat()}; }
     // one chunk of statements on its way through the stages of prove_chunk: what it is, the route it takes (decided once, read by every stage)
     struct Chunk {

@@ -24,28 +24,10 @@ bool be_is_zero(const uint8_t* a) { for (int i = 0; i < 32; i++) if (a[i]) retur
 }  // namespace
 
 template <class XyzzT>
-void AlgorithmImpl::reduce_slices(hipStream_t st, XyzzT* pa, XyzzT* pb, size_t nslices, size_t cols, XyzzT* out) {
-    XyzzT* src = pa; XyzzT* alt = pb; size_t ns = nslices;
-    for (;;) {
-        const size_t groups = msm_reduce_groups(ns, cols);
-        XyzzT* dst = groups == 1 ? out : alt;
-        launch_msm_reduce(src, ns, cols, dst, st);
-        if (groups == 1) break;
-        XyzzT* t = src; src = dst; alt = t; ns = groups;
-    }
-}
+void AlgorithmImpl::reduce_slices(hipStream_t st, XyzzT* pa, XyzzT* pb, size_t nslices, size_t cols, XyzzT* out) { msm_reduce_slices(st, pa, pb, nslices, cols, out); }
 
 template <class XyzzT>
-void AlgorithmImpl::reduce_slices_few(hipStream_t st, XyzzT* pa, XyzzT* pb, size_t nslices, size_t cols, size_t stride, size_t npr, XyzzT* out) {
-    XyzzT* src = pa; XyzzT* alt = pb; size_t ns = nslices;
-    for (;;) {
-        const size_t groups = (ns + 63) / 64;
-        XyzzT* dst = groups == 1 ? out : alt;
-        launch_msm_reduce_few(src, ns, cols, stride, npr, dst, st);
-        if (groups == 1) break;
-        XyzzT* t = src; src = dst; alt = t; ns = groups;
-    }
-}
+void AlgorithmImpl::reduce_slices_few(hipStream_t st, XyzzT* pa, XyzzT* pb, size_t nslices, size_t cols, size_t stride, size_t npr, XyzzT* out) { msm_reduce_slices_few(st, pa, pb, nslices, cols, stride, npr, out); }
 
 template <class AffT, class XyzzT>
 void AlgorithmImpl::run_msm(Lane& ln, const MsmCtx& ctx, const MsmSet<AffT>& set, const fe* scalars, bool wires, size_t B, size_t n_real, bool latency, XyzzT* pa, XyzzT* pb, XyzzT* sj, XyzzT* flat, XyzzT* sum, bool timed, bool digits_ready,
@@ -54,7 +36,7 @@ void AlgorithmImpl::run_msm(Lane& ln, const MsmCtx& ctx, const MsmSet<AffT>& set
     // the flat rows of `m` for a call with a handful of statements: lanes = octets of bases, partial sums to `out`; returns their slices
     auto flat_few = [&](const MsmSet<AffT>& m, XyzzT* out, bool stamp) -> size_t {
         if (!m.nflat) return 0;
-        const size_t nslices = ((m.nflat + 7) / 8 + 63) / 64;
+        const size_t nslices = msm_flat_few_slices(m.nflat);
         MsmFlatRecodeArgs ra{scalars, m.frows.p, m.octwin.p, m.nflat, B, m.cv, ctx.digits, m.nbit, m.group_ok.p, ctx.gok, wires ? 1 : 0, ctx.plane, ctx.plane_rows, ctx.plane_stride};
         launch_msm_recode_flat_few(ra, n_real, ctx.stream);
         MsmFlatArgs a{m.ftable.p, m.rowoff.p, m.rowlen.p, m.nflat, ctx.digits, B, nslices, 512, out, m.nbit, m.sub.p, ctx.gok, scalars, m.frows.p};
@@ -83,10 +65,8 @@ void AlgorithmImpl::run_msm(Lane& ln, const MsmCtx& ctx, const MsmSet<AffT>& set
         reduce_slices(ctx.stream, pa, pb, nslices, B, set.nwide ? flat : sum);
     }
     if (set.nwide) {
-        // a single Prove call (lanes = bases): slices of 512 bases — 8 gathers + 6 butterfly additions per wave, and at most 64 partial
-        // sums per column, which one reduction launch folds
         size_t nslices = msm_slices(set.nwide, (size_t)set.nwin, WIN_SLICE, B, per);
-        if (latency && nslices > (set.nwide + 511) / 512) { per = 512; nslices = (set.nwide + 511) / 512; }
+        if (latency) msm_slices_latency(set.nwide, nslices, per);      // a single Prove call (lanes = bases): slices of 512 bases
         const size_t Bw = B * (size_t)set.nwin;
         MsmRecodeArgs ra{scalars, set.wrows.p, wires ? 1 : 0, set.nwide, B, set.c, set.nwin, ctx.digits};
         if (!digits_ready) launch_msm_recode(ra, ctx.stream);

@@ -272,8 +272,7 @@ std::vector<uint8_t> decode_g2_points(const KeyPoints& pts, G2Aff* out, hipStrea
 template <class AffT, class XyzzT>
 void AlgorithmImpl::build_rows(const AffT* bases, size_t n, const std::vector<uint64_t>& off, const std::vector<uint32_t>& len, AffT* table) {
     const uint32_t cap = 256;
-    std::vector<MsmRowSeg> segs;
-    for (size_t i = 0; i < n; i++) for (uint32_t f = 0; f < len[i]; f += cap) segs.push_back(MsmRowSeg{(uint32_t)i, f + 1, len[i] - f < cap ? len[i] - f : cap, 0u, off[i] + f});
+    const std::vector<MsmRowSeg> segs = msm_row_segments(off, len, cap);
     if (segs.empty()) return;
     size_t chunk = ((size_t)4 << 30) / (cap * sizeof(XyzzT)); if (chunk > segs.size()) chunk = segs.size();
     DevBuf<XyzzT> scratch(chunk * cap); DevBuf<MsmRowSeg> d_segs(segs.size());
@@ -295,55 +294,31 @@ void AlgorithmImpl::build_set(MsmSet<AffT>& set, const KeyPoints& raw, size_t po
     for (size_t i = 0; i < n; i++) if (st[i] == 1) throw std::runtime_error(std::string("pk: invalid point in ") + what);
     const size_t D = (size_t)1 << (c - 1);
     const uint32_t ROW_ZERO = zero_row != 0xFFFFFFFFu ? zero_row : (uint32_t)(n_wires + 3);
-    std::vector<uint32_t> bits, narrow, wide;            // indices into the key's order; the point at infinity contributes nothing: dropped
-    std::vector<uint32_t> narrow_len;
-    for (size_t i = 0; i < n; i++) {
-        if (st[i] == 2) continue;
-        const int k = uniform || rows[i] >= cls.size() ? 255 : cls[rows[i]];
-        if (uniform || cfg.bit_groups <= 0 || k == 255 || k + cfg.row_margin_bits > NARROW_MAX_BITS) wide.push_back((uint32_t)i);
-        else if (k <= 1) bits.push_back((uint32_t)i);
-        else { narrow.push_back((uint32_t)i); const int lb = k + cfg.row_margin_bits; narrow_len.push_back(1u << (lb < 0 ? 0 : lb)); }
-    }
-    // expand_cv > 0: EVERY base becomes window octets of that digit width (the latency-path layout of the quotient bases: no Horner pass)
-    if (!uniform || expand_cv > 0) {
-        while (bits.size() % 8) { narrow.insert(narrow.begin(), bits.back()); narrow_len.insert(narrow_len.begin(), 2u); bits.pop_back(); }
-        // flat part: [bits][narrow][padding to an octet][window octets of the expanded wide wires]
-        std::vector<uint32_t> src(bits), shift, frows, len; std::vector<int32_t> octwin;
-        src.insert(src.end(), narrow.begin(), narrow.end());
-        for (uint32_t i : src) frows.push_back(rows[i]);
-        len.assign(bits.size(), 1u); len.insert(len.end(), narrow_len.begin(), narrow_len.end());
-        while (src.size() % 8) { src.push_back(src.empty() ? 0u : src[0]); frows.push_back(ROW_ZERO); len.push_back(1u); }
-        shift.assign(src.size(), 0u); octwin.assign(src.size() / 8, -1);
-        const bool expand = !wide.empty() && (expand_cv > 0 || wide.size() <= EXPAND_MAX) && n > 0;
-        if (expand) {
-            set.cv = expand_cv > 0 ? expand_cv : EXPAND_C; const int nwv = msm_windows(set.cv), octs = (nwv + 7) / 8;
-            for (uint32_t w : wide) for (int q = 0; q < 8 * octs; q++) {
-                src.push_back(w); frows.push_back(rows[w]); shift.push_back(q < nwv ? (uint32_t)(set.cv * q) : 0u); len.push_back(q < nwv ? 1u << (set.cv - 1) : 1u);
-                if (q % 8 == 0) octwin.push_back(q);
-            }
-            set.nexpanded = wide.size(); wide.clear();
+    // The layout (msm_layout.hpp); the point at infinity contributes nothing: dropped.
+    // flat part: [bits][narrow][padding to an octet][window octets of the expanded wide wires]; expand_cv > 0: EVERY base becomes window octets of that
+    // digit width (the latency-path layout of the quotient bases: no Horner pass)
+    const MsmFlatPlan plan = msm_plan_flat(msm_sort_bases(st, rows, cls, uniform, cfg.bit_groups, cfg.row_margin_bits, NARROW_MAX_BITS), rows, ROW_ZERO, uniform, expand_cv, EXPAND_MAX, EXPAND_C, msm_windows);
+    const std::vector<uint32_t>&src = plan.src, &shift = plan.shift, &frows = plan.frows, &len = plan.len, &wide = plan.wide; const std::vector<int32_t>& octwin = plan.octwin;
+    if (plan.nexpanded) { set.cv = plan.cv; set.nexpanded = plan.nexpanded; }
+    set.nflat = src.size(); set.nbit = plan.nbit;
+    if (set.nflat) {
+        DevBuf<AffT> fb(set.nflat); DevBuf<uint32_t> d_src(set.nflat), d_shift(set.nflat);
+        d_src.upload(src.data(), src.size(), stream); d_shift.upload(shift.data(), shift.size(), stream);
+        launch_shift_bases(bases.p, d_src.p, d_shift.p, set.nflat, fb.p, stream);
+        std::vector<uint64_t> off; const size_t entries = msm_row_offsets(len, off);
+        set.ftable.alloc(entries); table_bytes += set.ftable.bytes();
+        set.rowoff.alloc(set.nflat); set.rowlen.alloc(set.nflat); set.frows.alloc(set.nflat); set.octwin.alloc(octwin.size());
+        set.rowoff.upload(off.data(), set.nflat, stream); set.rowlen.upload(len.data(), set.nflat, stream);
+        set.frows.upload(frows.data(), set.nflat, stream); set.octwin.upload(octwin.data(), octwin.size(), stream);
+        build_rows<AffT, XyzzT>(fb.p, set.nflat, off, len, set.ftable.p);
+        if (set.nbit) {
+            const size_t ng = set.nbit / 8;
+            set.sub.alloc(ng * MSM_GROUP_ENTRIES); set.group_ok.alloc(ng);
+            table_bytes += set.sub.bytes();
+            build_subset<AffT, XyzzT>(fb.p, ng, set.sub.p, set.group_ok.p);
         }
-        set.nflat = src.size(); set.nbit = bits.size();
-        if (set.nflat) {
-            DevBuf<AffT> fb(set.nflat); DevBuf<uint32_t> d_src(set.nflat), d_shift(set.nflat);
-            d_src.upload(src.data(), src.size(), stream); d_shift.upload(shift.data(), shift.size(), stream);
-            launch_shift_bases(bases.p, d_src.p, d_shift.p, set.nflat, fb.p, stream);
-            std::vector<uint64_t> off(set.nflat); size_t entries = 0;
-            for (size_t i = 0; i < set.nflat; i++) { off[i] = entries; entries += len[i]; }
-            set.ftable.alloc(entries); table_bytes += set.ftable.bytes();
-            set.rowoff.alloc(set.nflat); set.rowlen.alloc(set.nflat); set.frows.alloc(set.nflat); set.octwin.alloc(octwin.size());
-            set.rowoff.upload(off.data(), set.nflat, stream); set.rowlen.upload(len.data(), set.nflat, stream);
-            set.frows.upload(frows.data(), set.nflat, stream); set.octwin.upload(octwin.data(), octwin.size(), stream);
-            build_rows<AffT, XyzzT>(fb.p, set.nflat, off, len, set.ftable.p);
-            if (set.nbit) {
-                const size_t ng = set.nbit / 8;
-                set.sub.alloc(ng * MSM_GROUP_ENTRIES); set.group_ok.alloc(ng);
-                table_bytes += set.sub.bytes();
-                build_subset<AffT, XyzzT>(fb.p, ng, set.sub.p, set.group_ok.p);
-            }
-            HIP_CHECK(hipGetLastError());
-            HIP_CHECK(hipStreamSynchronize(stream));      // fb, d_src, d_shift go out of scope
-        }
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipStreamSynchronize(stream));      // fb, d_src, d_shift go out of scope
     }
     set.nwide = wide.size();
     if (set.nwide) {      // windowed part: uniform rows

@@ -2,6 +2,7 @@
 // immediately; no launcher allocates, synchronises or copies (hipGraph-capturable, guide §6 G9).
 #pragma once
 #include "glv.hpp"
+#include "msm_layout.hpp"
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <cstddef>
@@ -225,7 +226,7 @@ void launch_g1_sum_be(const G1Xyzz* a, const G1Xyzz* b, size_t n, uint8_t* out, 
 //   flat:     small scalars (bits, ternary values, bytes — nearly every wire).  One signed 16-bit value per (base, proof), one
 //             accumulator; rows have their own length rowlen[k] at entry rowoff[k]; bit groups of eight bases share a table of signed
 //             subset sums.
-struct MsmRowSeg { uint32_t base, first, count, pad; uint64_t entry; };     // build work item: `count` multiples of base, from `first`, written at table entry `entry`
+// (MsmRowSeg, msm_layout.hpp: a build work item — `count` multiples of base, from `first`, written at table entry `entry`)
 // Builds the rows described by segs (each at most `cap` entries); scratch: nsegs * cap projective points.
 void launch_build_rows(const G1Aff* bases, const MsmRowSeg* segs, size_t nsegs, uint32_t cap, G1Aff* table, G1Xyzz* scratch, hipStream_t s);
 void launch_build_rows(const G2Aff* bases, const MsmRowSeg* segs, size_t nsegs, uint32_t cap, G2Aff* table, G2Xyzz* scratch, hipStream_t s);
@@ -304,6 +305,8 @@ struct MsmFlatRecodeArgs {
     uint4* digits;
     size_t nbit; const uint8_t* group_ok; uint8_t* gok;
     int mont;                                       // scalars are Montgomery values (wires) or canonical integers (h)
+    // mont = 0 is honoured by WINDOW octets only: everywhere else recode_flat_octet, and mul_out behind an escape, call from_mont unconditionally.  The
+    // engine only ever passes canonical scalars to all-window sets (the expanded Z layout, build_set with expand_cv > 0); gsc_debug_msm refuses the rest.
     // byte plane of the small-integer witness path (or nullptr): a scalar row r < plane_rows is read from plane[(group * plane_stride + r) * 64 + lane]
     // (0, 1, -1; WS_PLANE_WIDE = the row's 32-byte element is in `scalars` after all) instead of scalars[r * batch + p]
     const int8_t* plane = nullptr; size_t plane_rows = 0, plane_stride = 0;

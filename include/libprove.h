@@ -399,6 +399,47 @@ extern int gsc_debug_group_idft(int group, int L, const uint8_t *pts, uint8_t *o
 extern int gsc_debug_column_sums(int group, uint32_t n_rows, const uint8_t *rows, uint32_t n_cols, const uint32_t *col_start,
                                  const uint32_t *term_row, const uint32_t *term_coeff, uint32_t n_coeff, const uint8_t *coeff_be,
                                  uint8_t *out, uint8_t *out_inf);
+/* TEST HOOK: the MSM kernels alone, on a caller's bases and scalars: no key, no circuit, no witness.  The bases are laid out by the planner the
+ * engine uses for a key's sets (csrc/msm_layout.hpp) from the caller's per-base description, the tables are built, and one sum per column runs
+ * through the launch sequence of a prover's MSM: recoding, gather-accumulate (flat and windowed part), slice reductions, Horner.
+ *   group 0: G1 (64 B per point), 1: G2 (128 B, A1 before A0); points: nbases raw finite points, big-endian X | Y;
+ *   kind[k]: 0 bit, 1 narrow with rowlen[k] table entries (1 .. 32768), 2 wide; rows[k] < n_rows: the scalar row of base k; zero_row: a row of zeros
+ *   (padding slots);  c in [4, 17]: digit width of the windowed part;  cv: 0 = wide bases take the windowed kernel, 4 .. 15 = every wide base becomes
+ *   window octets of the flat part at that width;  mont: the kernels get Montgomery images (wire values, sign-normalised) or canonical integers —
+ *   canonical ones only where the engine passes them: no bit and no narrow bases;
+ *   batch: 64 or 128 columns;  nproofs: 0 = batch kernels, 1 .. 32 = latency kernels on the first nproofs columns;
+ *   per_flat / per_win: bases per slice (multiples of 8, flat at most 512), 0 = the engine's own choice (per_flat is not read by the latency kernels);
+ *   digit_bases: 0, or more than the wide bases: the windowed digits are laid out for digit_bases bases with the scalar rows digit_rows[0 .. digit_bases)
+ *   (its first entries the wide bases' own rows), of which the kernel walks the wide bases only;
+ *   scalars_be: n_rows x batch canonical values below r, 32 big-endian bytes each, [row][column];
+ *   plane (optional): byte plane [(column / 64 * plane_stride + row) * 64 + column % 64] for the rows below plane_rows <= plane_stride: 0, 1, -1, or
+ *   -128 = read the row's 32-byte scalar after all.
+ * Outputs: out / out_inf: per column (batch, or nproofs) the affine sum as canonical little-endian values (G1 x, y; G2 x.a0, x.a1, y.a0, y.a1) and 1
+ * (with zeros) for the point at infinity;  flat_digits, win_digits (16-byte words as the kernels store them), gok, group_ok: copies of the recoders'
+ * output, each with its capacity in bytes (a buffer may be NULL with capacity 0: not copied; too small a buffer is refused);
+ * info[64]: 0 nflat, 1 nbit, 2 nexpanded, 3 nwide, 4 nwin, 5 / 6 slices and bases per slice of the flat part, 7 / 8 of the windowed part,
+ * 9 reduction levels of the flat part, 10 + 2 i / 11 + 2 i slices entering level i and 1 when it took the by-proof kernel (i < 8), 26 and 27 .. 42 the
+ * same for the windowed part, 43: Horner had an addend, 44 columns returned, 45 flat octets, 46 octets per window of the windowed digits, 47 cv,
+ * 48 .. 51 bytes written to flat_digits, win_digits, gok, group_ok.
+ * 0 on success; -1 (one line on stdout) for hooks disabled, an unknown group, c / cv / batch / nproofs / per outside the above, a scalar not below r,
+ * a point that is not raw, finite and in the group, canonical scalars with bit or narrow bases, more than 2^16 bases or 2^28 table entries. */
+struct gsc_debug_msm_args {
+    int32_t group; uint32_t nbases;
+    const uint8_t *points; const uint8_t *kind; const uint32_t *rowlen; const uint32_t *rows;
+    uint32_t n_rows, zero_row;
+    int32_t c, cv, mont;
+    uint32_t batch, nproofs, per_flat, per_win, digit_bases;
+    const uint32_t *digit_rows;
+    const uint8_t *scalars_be;
+    const int8_t *plane; uint32_t plane_rows, plane_stride;
+    uint8_t *out, *out_inf;
+    uint8_t *flat_digits; size_t flat_digits_cap;
+    uint8_t *win_digits; size_t win_digits_cap;
+    uint8_t *gok; size_t gok_cap;
+    uint8_t *group_ok; size_t group_ok_cap;
+    uint32_t *info;
+};
+extern int gsc_debug_msm(const struct gsc_debug_msm_args *args);
 
 #ifdef __cplusplus
 }

@@ -21,6 +21,7 @@ arithmetic on the twist, the whole pairing by generic lines on E(Fp12); on the l
 documents.
 """
 import functools
+import itertools
 import os
 import random
 import struct
@@ -1026,3 +1027,523 @@ def native_curve_ops(exe, group, op, pts, inf, lam, n, k):
     out = subprocess.run([exe], input=struct.pack("<4i", group, op, n, k) + pts + inf + lam, capture_output=True, timeout=300, check=True).stdout
     assert len(out) == w * n + n
     return out[:w * n], out[w * n:]
+
+
+# ---------------------------------------------------------------- the MSM kernels ----------------------------------------------------------------
+# gsc_debug_msm (include/libprove.h).  Bases are P_k = b_k G with b_k chosen by the test, so the sum of column p is (sum_k s_kp b_k mod r) G: ONE
+# scalar multiplication per column whatever the number of bases, and the point at infinity exactly when that integer is 0.  The multiplication is
+# Jacobian integer arithmetic over a fixed-window table of G (test_msm_model_host.py holds it against ec_mul).  The digit layouts are modelled
+# from the text of csrc/kernels.hpp, so that a case cannot pass by silently taking a slow path.
+HALF_R = (R - 1) // 2
+MSM_FLAT_ESCAPE, MSM_GROUP_ENTRIES, MSM_FEW_PROOFS, WS_PLANE_WIDE = -32768, 3280, 32, -128
+KIND_BIT, KIND_NARROW, KIND_WIDE = 0, 1, 2
+
+
+def jac_double(w, T):
+    """2T for T = (X, Y, Z) on y^2 = x^3 + b, or None for the point at infinity"""
+    if T is None or not any(T[1]):
+        return None
+    X, Y, Z = T
+    k = lambda n: f_small(w, n)
+    XX, YY = f_mul(X, X), f_mul(Y, Y)
+    m, s = f_mul(k(3), XX), f_mul(k(4), f_mul(X, YY))
+    X3 = f_sub(f_mul(m, m), f_add(s, s))
+    return (X3, f_sub(f_mul(m, f_sub(s, X3)), f_mul(k(8), f_mul(YY, YY))), f_mul(k(2), f_mul(Y, Z)))
+
+
+def jac_madd(w, T, q):
+    """T + q for Jacobian T (or None) and affine q; equal points double, opposite points give None"""
+    if T is None:
+        return (q[0], q[1], f_small(w, 1))
+    X, Y, Z = T
+    ZZ = f_mul(Z, Z)
+    H, Rr = f_sub(f_mul(q[0], ZZ), X), f_sub(f_mul(q[1], f_mul(Z, ZZ)), Y)
+    if not any(H):
+        return jac_double(w, T) if not any(Rr) else None
+    HH = f_mul(H, H); HHH = f_mul(H, HH); V = f_mul(X, HH)
+    X3 = f_sub(f_sub(f_mul(Rr, Rr), HHH), f_add(V, V))
+    return (X3, f_sub(f_mul(Rr, f_sub(V, X3)), f_mul(Y, HHH)), f_mul(Z, H))
+
+
+def jac_to_affine(T):
+    if T is None:
+        return None
+    zi = f_inv(T[2]); zi2 = f_mul(zi, zi)
+    return (f_mul(T[0], zi2), f_mul(T[1], f_mul(zi2, zi)))
+
+
+_gen_tables = {}
+GEN_WINDOW = 8
+
+
+def _gen_table(group):
+    """table[j][d - 1] = d 2^(8 j) G, affine, for the 32 byte positions of a scalar"""
+    if group not in _gen_tables:
+        w = 1 if group == 0 else 2
+        rows, base = [], GEN[group]
+        for _ in range(256 // GEN_WINDOW):
+            row, acc = [base], (base[0], base[1], f_small(w, 1))
+            for _d in range(2, 1 << GEN_WINDOW):
+                acc = jac_madd(w, acc, base)
+                row.append(jac_to_affine(acc))
+            rows.append(row)
+            base = jac_to_affine(jac_madd(w, acc, base))      # 2^8 times the row's base
+        _gen_tables[group] = rows
+    return _gen_tables[group]
+
+
+def gen_mul(group, k):
+    """(k mod r) G as an affine point, None for the point at infinity"""
+    w, acc, k = (1 if group == 0 else 2), None, k % R
+    for j, row in enumerate(_gen_table(group)):
+        d = (k >> (GEN_WINDOW * j)) & ((1 << GEN_WINDOW) - 1)
+        if d:
+            acc = jac_madd(w, acc, row[d - 1])
+    return jac_to_affine(acc)
+
+
+def raw_point(group, p):
+    """a finite point as gsc_debug_msm takes it: big-endian X | Y, in G2 the imaginary part first"""
+    be = lambda v: int(v).to_bytes(32, "big")
+    if group == 0:
+        return be(p[0][0]) + be(p[1][0])
+    return be(p[0][1]) + be(p[0][0]) + be(p[1][1]) + be(p[1][0])
+
+
+def msm_windows(c):
+    """csrc/kernels.hpp msm_windows: the fewest windows whose top one takes the last carry: floor((r-1) / 2^(c (nwin-1))) + 1 <= 2^(c-1) - 1"""
+    nwin = 1
+    while ((R - 1) >> (c * (nwin - 1))) + 1 > (1 << (c - 1)) - 1:
+        nwin += 1
+    return nwin
+
+
+def sign_normalise(s):
+    """(|s|, negated): the representative of s in [-(r-1)/2, (r-1)/2]"""
+    return (R - s, True) if s > HALF_R else (s, False)
+
+
+def signed_digits(mag, c, n, negated):
+    """n signed c-bit digits of the magnitude mag, each in [-D, D - 1], D = 2^(c-1); for a negated scalar the digits are negated and the split
+    threshold moves by one (signed_digit_step of csrc/msm_dev.hpp)"""
+    Dh, carry, out = 1 << (c - 1), 0, []
+    for _ in range(n):
+        raw = (mag & ((1 << c) - 1)) + carry
+        mag >>= c
+        if raw >= Dh + (1 if negated else 0):
+            raw -= 1 << c; carry = 1
+        else:
+            carry = 0
+        out.append(-raw if negated else raw)
+    assert mag == 0 and carry == 0 and all(-Dh <= d < Dh for d in out)
+    return out
+
+
+def _i16x8(vals):
+    assert len(vals) == 8
+    return struct.pack("<8h", *vals)
+
+
+def win_digit_words(scalars, rows, batch, c, mont):
+    """k_recode's output: digits[(j noct + o) batch + p] = the eight digits of window j of the bases 8o .. 8o+7 (int16; at c = 17 int32, two words per
+    index); scalars[row * batch + p]; rows: the scalar row of every base the buffer is laid out for"""
+    nwin, noct = msm_windows(c), (len(rows) + 7) // 8
+    dig = {}
+    for k, row in enumerate(rows):
+        for p in range(batch):
+            s = scalars[row * batch + p]
+            mag, neg = sign_normalise(s) if mont else (s, False)
+            dig[k, p] = signed_digits(mag, c, nwin, neg)
+    out = bytearray()
+    zero = [0] * nwin
+    for j in range(nwin):
+        for o in range(noct):
+            for p in range(batch):
+                e = [dig.get((8 * o + i, p), zero)[j] for i in range(8)]
+                out += struct.pack("<8i", *e) if c > 16 else _i16x8(e)
+    return bytes(out)
+
+
+class FlatPlan:
+    """The flat layout of csrc/msm_layout.hpp, stated again: [bit groups][narrow rows][padding to an octet][window octets of the expanded wide bases].
+    Bits that do not fill an octet become narrow rows of length 2 in front of the narrow ones; padding repeats the first base on the zero row; a wide
+    base becomes ceil(nwv / 8) octets of (base, window) pairs at shift cv q, row length 2^(cv-1); slots past the nwv windows have shift 0, length 1."""
+
+    def __init__(self, bits, narrow, narrow_len, wide, rows, zero_row, uniform=False, expand_cv=0, expand_max=0, expand_c=0):
+        bits, narrow, narrow_len, wide = list(bits), list(narrow), list(narrow_len), list(wide)
+        self.src, self.shift, self.frows, self.len, self.octwin, self.nbit, self.nexpanded, self.cv, self.wide, self.nflat = [], [], [], [], [], 0, 0, 0, wide, 0
+        if uniform and expand_cv <= 0:
+            return
+        keep = len(bits) - len(bits) % 8
+        narrow, narrow_len = bits[keep:] + narrow, [2] * (len(bits) - keep) + narrow_len
+        bits = bits[:keep]
+        self.src = bits + narrow
+        self.frows = [rows[i] for i in self.src]
+        self.len = [1] * len(bits) + narrow_len
+        while len(self.src) % 8:
+            self.src.append(self.src[0]); self.frows.append(zero_row); self.len.append(1)
+        self.shift = [0] * len(self.src)
+        self.octwin = [-1] * (len(self.src) // 8)
+        self.nbit = len(bits)
+        if wide and (expand_cv > 0 or len(wide) <= expand_max):
+            self.cv = expand_cv if expand_cv > 0 else expand_c
+            nwv = msm_windows(self.cv)
+            for wb in wide:
+                for q in range(8 * ((nwv + 7) // 8)):
+                    self.src.append(wb); self.frows.append(rows[wb])
+                    self.shift.append(self.cv * q if q < nwv else 0); self.len.append(1 << (self.cv - 1) if q < nwv else 1)
+                    if q % 8 == 0:
+                        self.octwin.append(q)
+            self.nexpanded, self.wide = len(wide), []
+        self.nflat = len(self.src)
+
+
+def sort_bases(status, rows, cls, uniform, bit_groups, margin, max_bits):
+    """msm_sort_bases: what the calibration classes make of a key's bases -> (bits, narrow, narrow_len, wide)"""
+    bits, narrow, narrow_len, wide = [], [], [], []
+    for i, st in enumerate(status):
+        if st == 2:
+            continue
+        k = 255 if uniform or rows[i] >= len(cls) else cls[rows[i]]
+        if uniform or bit_groups <= 0 or k == 255 or k + margin > max_bits:
+            wide.append(i)
+        elif k <= 1:
+            bits.append(i)
+        else:
+            narrow.append(i); narrow_len.append(1 << max(0, k + margin))
+    return bits, narrow, narrow_len, wide
+
+
+def flat_digit_words(plan, scalars, batch, mont, group_ok, nproofs=0, plane=None, plane_rows=0, plane_stride=0):
+    """k_recode_flat's (nproofs = 0) or k_recode_flat_few's output -> (digits, gok).  digits[o batch + p] = eight int16; a bit group whose columns are
+    all ternary — over the wave of 64 columns, or (latency kernel) in the one column — and whose group_ok is set carries the balanced-ternary value in
+    slot 0 and gok 1, else ordinary values: the sign-normalised scalar, or MSM_FLAT_ESCAPE from 2^15 on.  Window octets carry the digits
+    octwin .. octwin + 7 of one scalar.  gok[o (batch / 64) + wave], in the latency kernel gok[o 32 + p]; what no thread writes stays zero."""
+    noct, ng, few = plan.nflat // 8, plan.nbit // 8, nproofs > 0
+    digits = [[None] * batch for _ in range(noct)]
+    gok = bytearray(ng * (MSM_FEW_PROOFS if few else batch // 64))
+    cols = range(nproofs) if few else range(batch)
+
+    def entry(row, p):      # the byte plane's entry for (row, p), or WS_PLANE_WIDE
+        if plane is None or row >= plane_rows:
+            return WS_PLANE_WIDE
+        v = plane[((p >> 6) * plane_stride + row) * 64 + (p & 63)]
+        return v - 256 if v > 127 else v
+
+    def value(row, p):      # the scalar of (row, p) as an integer mod r
+        t = entry(row, p)
+        return scalars[row * batch + p] if t == WS_PLANE_WIDE else t % R
+
+    for o in range(noct):
+        rows = plan.frows[8 * o:8 * o + 8]
+        if plan.octwin[o] >= 0:
+            for p in cols:
+                mag, neg = sign_normalise(value(rows[0], p))
+                nw = max(msm_windows(plan.cv), plan.octwin[o] + 8)
+                digits[o][p] = signed_digits(mag, plan.cv, nw, neg)[plan.octwin[o]:plan.octwin[o] + 8]
+            continue
+        assert mont, "canonical scalars reach window octets only"
+        waves = [[p] for p in cols] if few else [list(range(64 * g, 64 * g + 64)) for g in range(batch // 64)]
+        for wi, wave in enumerate(waves):
+            all_plane = plane is not None and all(entry(r, p) != WS_PLANE_WIDE for r in rows for p in wave)
+            vals = {p: [sign_normalise(value(r, p)) for r in rows] for p in wave}
+            tern = all(m <= 1 for p in wave for m, _ in vals[p])
+            if o < ng:
+                # with every entry in the plane the values are ternary by construction; otherwise the kernel tests the 32-byte elements
+                ok = (True if all_plane else tern) and group_ok[o] != 0
+                if few:
+                    gok[o * MSM_FEW_PROOFS + wave[0]] = ok
+                else:
+                    gok[o * (batch // 64) + wi] = ok
+                if ok:
+                    for p in wave:
+                        digits[o][p] = [sum((-m if n else m) * 3 ** i for i, (m, n) in enumerate(vals[p]))] + [0] * 7
+                    continue
+            for p in wave:
+                digits[o][p] = [MSM_FLAT_ESCAPE if m >= 1 << 15 else (-m if n else m) for m, n in vals[p]]
+    out = bytearray()
+    for o in range(noct):
+        for p in range(batch):
+            out += _i16x8(digits[o][p] if digits[o][p] is not None else [0] * 8)
+    return bytes(out), bytes(gok)
+
+
+def group_tabulates(bs):
+    """group_ok of a bit group: 0 when some signed subset sum of its bases, other than the empty one, is the point at infinity (k_build_subset
+    meets every such sum on its way through the table)"""
+    return 0 if any(any(ts) and sum(t * b for t, b in zip(ts, bs)) % R == 0 for ts in itertools.product((-1, 0, 1), repeat=len(bs))) else 1
+
+
+_point_cache = {}
+
+
+def base_point(group, b):
+    if (group, b) not in _point_cache:
+        _point_cache[group, b] = raw_point(group, gen_mul(group, b))
+    return _point_cache[group, b]
+
+
+class MsmCase:
+    """One call of gsc_debug_msm and everything the test holds it against.  b[k]: the discrete logarithm of base k; kind / rowlen / rows per base;
+    scalars[row * batch + p] integers below r.  expect: info-block entries the route must show."""
+
+    def __init__(self, group, name, b, kind, rows, scalars, n_rows, c, rowlen=None, cv=0, mont=1, batch=64, nproofs=0, per_flat=0, per_win=0, digit_rows=None,
+                 plane=None, plane_rows=0, plane_stride=0, expect=None):
+        self.group, self.name, self.b, self.kind, self.rows, self.scalars, self.n_rows, self.c = group, name, list(b), list(kind), list(rows), list(scalars), n_rows, c
+        self.rowlen = list(rowlen) if rowlen else [0] * len(self.b)
+        self.cv, self.mont, self.batch, self.nproofs, self.per_flat, self.per_win, self.digit_rows = cv, mont, batch, nproofs, per_flat, per_win, digit_rows
+        self.plane, self.plane_rows, self.plane_stride, self.expect = plane, plane_rows, plane_stride, dict(expect or {})
+        self.zero_row = n_rows - 1
+        assert len(self.scalars) == n_rows * batch and all(0 <= s < R for s in self.scalars) and not any(self.scalars[self.zero_row * batch:])
+        assert all(0 < x < R for x in self.b) and len(self.kind) == len(self.rows) == len(self.b)
+        idx = lambda kd: [k for k, x in enumerate(self.kind) if x == kd]
+        self.plan = FlatPlan(idx(KIND_BIT), idx(KIND_NARROW), [self.rowlen[k] for k in idx(KIND_NARROW)], idx(KIND_WIDE), self.rows, self.zero_row, False, cv)
+        self.ncols = nproofs or batch
+
+    def points(self):
+        return b"".join(base_point(self.group, x) for x in self.b)
+
+    def value(self, row, p):
+        if self.plane is not None and row < self.plane_rows:
+            v = self.plane[((p >> 6) * self.plane_stride + row) * 64 + (p & 63)]
+            v = v - 256 if v > 127 else v
+            if v != WS_PLANE_WIDE:
+                return v % R
+        return self.scalars[row * self.batch + p]
+
+    def exponents(self):
+        return [sum(self.value(r, p) * x for r, x in zip(self.rows, self.b)) % R for p in range(self.ncols)]
+
+    def expected(self):
+        """(coordinates, infinity flags) of every column, as the hook returns them"""
+        w = 1 if self.group == 0 else 2
+        pts = [gen_mul(self.group, e) for e in self.exponents()]
+        return b"".join(pack_point(w, p) for p in pts), bytes(p is None for p in pts)
+
+    def group_ok(self):
+        return bytes(group_tabulates([self.b[k] for k in self.plan.src[8 * o:8 * o + 8]]) for o in range(self.plan.nbit // 8))
+
+    def flat_model(self):
+        return flat_digit_words(self.plan, self.scalars, self.batch, self.mont, self.group_ok(), self.nproofs, self.plane, self.plane_rows, self.plane_stride)
+
+    def win_model(self):
+        rows = self.digit_rows if self.digit_rows else [self.rows[k] for k in self.plan.wide]
+        return win_digit_words(self.scalars, rows, self.batch, self.c, self.mont) if self.plan.wide else b""
+
+    def call(self, gsc):
+        return gsc.debug_msm(self.group, self.points(), self.kind, self.rowlen, self.rows, self.scalars, self.n_rows, self.zero_row, self.c, self.cv, self.mont, self.batch,
+                             self.nproofs, self.per_flat, self.per_win, self.digit_rows, self.plane, self.plane_rows, self.plane_stride)
+
+
+def windowed_patterns(c, mont, rnd, n):
+    """n scalars for a windowed base: 0, 1, r - 1, (r -+ 1) / 2; every digit D - 1 / D / D + 1 (the carry chain, the int16 minimum at c = 16, the moved
+    threshold of a negated scalar); only the top window; 2^(c j) - 1; random values.  mont = 1 scalars are sign-normalised by the kernel, so the
+    digit patterns are given as magnitudes and as their negatives."""
+    nwin, Dh = msm_windows(c), 1 << (c - 1)
+    vals = [0, 1, R - 1, HALF_R, HALF_R + 1]
+    for w in (Dh - 1, Dh, Dh + 1):
+        for bound in ((HALF_R, R - 1) if mont else (R - 1,)):
+            top = nwin - 1
+            while sum(w << (c * j) for j in range(top)) > bound:
+                top -= 1
+            v = sum(w << (c * j) for j in range(top))
+            vals += [v, R - v] if mont and v else [v]
+    top = 1 << (c * (nwin - 1))
+    vals += [top, R - top] if top < R else []
+    vals += [(1 << (c * j)) - 1 for j in (1, 2, nwin // 2, nwin - 1) if (1 << (c * j)) - 1 < R]
+    vals += [R - ((1 << (c * j)) - 1) for j in (1, nwin - 1)]
+    vals = [v % R for v in vals]
+    while len(vals) < n:
+        vals.append(rnd.randrange(R))
+    return vals
+
+
+FLAT_EDGES = (0, 1, -1, 32767, -32767, 32768, -32768, HALF_R, HALF_R + 1, 2, -2)
+
+
+def flat_patterns(rowlen, rnd, n):
+    """n scalars for a flat base with a row of rowlen entries: 0, +-1, +-rowlen (the row's last entry), +-(rowlen + 1) (beyond the row: multiplied out),
+    +-32767 (the largest value that is no escape), +-32768 and full-width values (escapes)"""
+    vals = list(FLAT_EDGES) + [rowlen, -rowlen, rowlen + 1, -rowlen - 1, rowlen - 1]
+    vals = [v % R for v in vals]
+    while len(vals) < n:
+        vals.append(rnd.choice((rnd.randrange(R), rnd.randrange(-rowlen, rowlen + 1) % R, rnd.randrange(-40000, 40000) % R)))
+    return vals
+
+
+def _matrix(cols_of_base, batch, n_extra_rows=1):
+    """scalars[row][p] from one list of per-column values per base (row k = base k), plus zero rows"""
+    out = []
+    for col in cols_of_base:
+        assert len(col) == batch
+        out += col
+    return out + [0] * (batch * n_extra_rows)
+
+
+def _rot(vals, k, batch):
+    return [vals[(p + 5 * k) % len(vals)] for p in range(batch)]
+
+
+def _b_list(rnd, n):
+    return [rnd.randrange(1, R) for _ in range(n)]
+
+
+def msm_cases(group):
+    """the case table of tests/test_gpu_msm.py; tests/test_msm_model_host.py proves its internal consistency on a CPU first"""
+    rnd = random.Random(900 + group)
+    cases = []
+
+    def windowed(name, c, nb, mont, batch=64, expect=None, b=None, cols=None, **kw):
+        b = b or _b_list(rnd, nb)
+        pats = windowed_patterns(c, mont, rnd, batch)
+        cols = cols or [_rot(pats, k, batch) for k in range(nb)]
+        cases.append(MsmCase(group, name, b, [KIND_WIDE] * nb, range(nb), _matrix(cols, batch), nb + 1, c, mont=mont, batch=batch, expect=expect, **kw))
+
+    # ---- windowed geometry: nbases 1, 7, 8, 9, 64, 65 and 8 q + 3; c = 4, 6, 15, 16, 17; both kinds of scalars ----
+    for nb, mont in ((1, 1), (7, 0), (8, 1), (9, 0), (64, 1), (65, 0)):
+        windowed("win_c6_n%d_mont%d" % (nb, mont), 6, nb, mont, per_win=8, expect={3: nb, 4: 43, 7: (nb + 7) // 8, 8: 8})
+    windowed("win_c4_n65_engine_slices", 4, 65, 1, expect={3: 65})                                  # per = 0: msm_slices
+    windowed("win_c15_n19_per8", 15, 19, 1, per_win=8, expect={7: 3, 4: 17})                        # a ragged last octet in a ragged last slice
+    windowed("win_c15_n67_per64", 15, 67, 0, per_win=64, expect={7: 2})
+    for mont in (0, 1):
+        windowed("win_c16_n9_mont%d" % mont, 16, 9, mont, per_win=8, expect={4: 16, 7: 2})          # digit -D = the int16 minimum
+        windowed("win_c17_n24_mont%d" % mont, 17, 24, mont, per_win=8, batch=128, expect={4: 15, 7: 3})   # two words per digit octet
+    windowed("win_c16_n65_batch128", 16, 65, 1, per_win=64, batch=128, expect={7: 2})
+    windowed("win_c17_n9_few5", 17, 9, 1, nproofs=5, expect={7: 1, 8: 512})
+    # ---- reductions: 8 and 9 slices (the tail branch of xcd_slice), 65 slices: two butterfly levels; by-proof then butterfly ----
+    windowed("win_c8_n64_8slices", 8, 64, 1, per_win=8, expect={7: 8, 26: 1, 27: 8, 28: 0})
+    windowed("win_c8_n72_9slices", 8, 72, 0, per_win=8, expect={7: 9, 26: 1, 27: 9, 28: 0})
+    windowed("win_c8_n520_butterfly_twice", 8, 520, 1, per_win=8, expect={4: 32, 7: 65, 26: 2, 27: 65, 28: 0, 29: 2, 30: 0})
+    windowed("win_c6_n520_by_proof", 6, 520, 1, per_win=8, expect={4: 43, 7: 65, 26: 2, 27: 65, 28: 1, 29: 3, 30: 0})
+    # ---- latency kernels: 1, 5, 32 columns; 63, 64, 65, 129 bases in one slice of 512 and cut by 64 ----
+    for nb, npr, per in ((63, 1, 0), (64, 5, 0), (65, 32, 0), (129, 5, 0), (63, 32, 64), (64, 1, 64), (65, 5, 64), (129, 32, 64)):
+        windowed("win_few_c6_n%d_p%d_per%d" % (nb, npr, per), 6, nb, (nb + npr) & 1, nproofs=npr, per_win=per,
+                 expect={7: (nb + 63) // 64 if per else 1, 8: per or 512, 44: npr})
+    windowed("win_few_c16_n65_p5", 16, 65, 1, nproofs=5, per_win=64, expect={7: 2})
+    # ---- digits laid out for more bases than are walked: recode 40, walk the first 19 ----
+    for npr in (0, 5):
+        pats = windowed_patterns(6, 1, rnd, 64)
+        cols = [_rot(pats, k, 64) for k in range(40)]
+        cases.append(MsmCase(group, "win_digit_bases_40_walk_19_p%d" % npr, _b_list(rnd, 19), [KIND_WIDE] * 19, range(19), _matrix(cols, 64), 41, 6, per_win=8, nproofs=npr,
+                             digit_rows=list(range(40)), expect={3: 19, 46: 5, 7: 3}))
+    # ---- collisions in the windowed kernel: P + P at the head of a slice (madd<false> leaves ZZ = 0: the repair), P + (-P) midway ----
+    b0 = rnd.randrange(1, R)
+    pats = windowed_patterns(6, 1, rnd, 64)
+    tail = [_rot(pats, k, 64) for k in range(2, 11)]
+    windowed("win_collision_same_base", 6, 11, 1, b=[b0, b0] + _b_list(rnd, 9), cols=[pats, pats] + tail, per_win=8)
+    windowed("win_collision_opposite_base", 6, 11, 1, b=[b0, R - b0] + _b_list(rnd, 9), cols=[pats, pats] + tail, per_win=8)
+    # a column whose sum is the point at infinity (the last base's scalar cancels the others), and the all-zero column
+    bs = _b_list(rnd, 9)
+    cols = [_rot(pats, k, 64) for k in range(8)]
+    cols.append([(-sum(cols[k][p] * bs[k] for k in range(8)) * pow(bs[8], -1, R)) % R if p % 2 else rnd.randrange(R) for p in range(64)])
+    for k in range(9):
+        cols[k][0] = 0
+    windowed("win_sum_is_infinity", 16, 9, 0, b=bs, cols=cols, per_win=8)
+
+    # ---- flat: ordinary values against rows of 1, 2, 5 and 256 entries; slices of 8 (65 of them: two butterfly levels) and the engine's own ----
+    def flat(name, kinds, lens, cols, batch=64, b=None, n_extra=1, **kw):
+        nb = len(kinds)
+        cases.append(MsmCase(group, name, b or _b_list(rnd, nb), kinds, range(nb), _matrix(cols, batch, n_extra), nb + n_extra, kw.pop("c", 6), rowlen=lens, batch=batch, **kw))
+
+    for nb, per, exp in ((1, 0, {0: 8}), (7, 8, {5: 1}), (9, 8, {5: 2, 0: 16}), (64, 8, {5: 8, 9: 1}), (65, 64, {5: 2}), (520, 8, {5: 65, 9: 2, 10: 65, 11: 0, 12: 2})):
+        lens = [(1, 2, 5, 256)[k % 4] for k in range(nb)]
+        flat("flat_narrow_n%d_per%d" % (nb, per), [KIND_NARROW] * nb, lens, [_rot(flat_patterns(lens[k], rnd, 64), k, 64) for k in range(nb)], per_flat=per, expect=exp)
+    # ---- bit groups: v = 3280 (the table's last entry), -3280, only t_7, all zero, random ternary; 7 bits (all demoted), 9 bits (one demoted) ----
+    def ternary_cols(nb, batch):
+        cols = [[rnd.choice((0, 1, R - 1)) for _ in range(batch)] for _ in range(nb)]
+        for k in range(nb):
+            cols[k][0], cols[k][1], cols[k][2], cols[k][3] = 1, R - 1, (1 if k % 8 == 7 else 0), 0
+            cols[k][4] = R - 1 if k % 8 == 7 else 0
+        return cols
+    for nb in (7, 8, 9, 16):
+        flat("bits_n%d" % nb, [KIND_BIT] * nb, None, ternary_cols(nb, 64), expect={1: nb - nb % 8, 0: (nb + 7) // 8 * 8})
+    # one wave entirely ternary; in the other a single column holds a 2 in one wire: gok = [1, 0], and still the right sums
+    cols = ternary_cols(16, 128)
+    cols[11][64 + 37] = 2
+    flat("bits_one_wave_not_ternary", [KIND_BIT] * 16, None, cols, batch=128, expect={1: 16})
+    # the colliding pair inside a bit group: its subset sums hit the point at infinity, group_ok = 0, the group is walked base by base
+    for tag, b1 in (("same", b0), ("opposite", R - b0)):
+        flat("bits_collision_%s_base" % tag, [KIND_BIT] * 16, None, ternary_cols(16, 64), b=[b0, b1] + _b_list(rnd, 14), expect={1: 16})
+    # the same pairs in narrow rows at the head of a slice, equal scalars: the ZZ = 0 repair of the flat kernel; later bases follow
+    cols = [_rot(flat_patterns(5, rnd, 64), 0, 64)] * 2 + [_rot(flat_patterns(5, rnd, 64), k, 64) for k in range(2, 11)]
+    for tag, b1 in (("same", b0), ("opposite", R - b0)):
+        flat("flat_collision_%s_base" % tag, [KIND_NARROW] * 11, [5] * 11, cols, b=[b0, b1] + _b_list(rnd, 9), per_flat=8)
+    bs = _b_list(rnd, 9)
+    cols = [_rot(flat_patterns(5, rnd, 64), k, 64) for k in range(8)]
+    cols.append([(-sum(cols[k][p] * bs[k] for k in range(8)) * pow(bs[8], -1, R)) % R if p % 2 else 3 for p in range(64)])
+    for k in range(9):
+        cols[k][0] = 0
+    flat("flat_sum_is_infinity", [KIND_NARROW] * 9, [5] * 9, cols, b=bs, per_flat=8)
+    # ---- flat latency kernels: 1, 64 and 65 octets; 1, 5, 32 columns ----
+    for noct, npr in ((1, 1), (64, 5), (65, 32)):
+        nb = 8 * noct
+        kinds = [KIND_BIT] * 16 + [KIND_NARROW] * (nb - 16) if nb > 16 else [KIND_NARROW] * nb
+        lens = [(1, 2, 5, 256)[k % 4] for k in range(nb)]
+        cols = [_rot(flat_patterns(lens[k], rnd, 64), k, 64) for k in range(nb)]
+        if nb > 16:
+            cols[:16] = ternary_cols(16, 64)
+            cols[9][3] = 5      # one column of group 1 is not ternary: its gok is 0 beside the other columns' 1
+        flat("flat_few_oct%d_p%d" % (noct, npr), kinds, lens, cols, nproofs=npr, expect={45: noct, 5: (noct + 63) // 64, 44: npr})
+    # ---- a set with every part: bit groups, narrow rows and wide bases — windowed (Horner with the flat sum as addend) or expanded ----
+    def mixed(name, nwide, batch=64, wide_vals=None, **kw):
+        c = kw.pop("c", 6)
+        kinds = [KIND_BIT] * 9 + [KIND_NARROW] * 5 + [KIND_WIDE] * nwide
+        lens = [0] * 9 + [2, 5, 256, 1, 5] + [0] * nwide
+        cols = ternary_cols(9, batch) + [_rot(flat_patterns(lens[k], rnd, batch), k, batch) for k in range(9, 14)]
+        wp = wide_vals or windowed_patterns(kw.get("cv") or c, 1, rnd, batch)
+        cols += [_rot(wp, k, batch) for k in range(nwide)]
+        flat(name, kinds, lens, cols, batch=batch, c=c, **kw)
+    mixed("mixed_horner_addend", 9, per_win=8, per_flat=8, expect={43: 1, 1: 8, 3: 9})
+    mixed("mixed_horner_addend_c16_batch128", 3, batch=128, c=16, expect={43: 1})
+    mixed("mixed_horner_addend_few", 9, nproofs=5, expect={43: 1, 44: 5})
+    # expanded wide wires: cv = 8 (32 windows: four full octets), cv = 15 (17 windows: seven padding slots whose digits must be 0)
+    edge = [R - 1, HALF_R, HALF_R + 1, 0, 1]
+    mixed("mixed_expanded_cv8", 2, cv=8, wide_vals=edge + windowed_patterns(8, 1, rnd, 64), expect={2: 2, 3: 0, 47: 8, 0: 16 + 2 * 32})
+    mixed("mixed_expanded_cv15", 2, cv=15, wide_vals=edge + windowed_patterns(15, 1, rnd, 64), expect={2: 2, 47: 15, 0: 16 + 2 * 24})
+    mixed("mixed_expanded_cv15_few", 2, cv=15, nproofs=5, wide_vals=edge + windowed_patterns(15, 1, rnd, 64), expect={2: 2, 44: 5})
+    # canonical scalars reach the flat kernels through all-window sets only (the latency layout of the quotient bases)
+    for npr in (0, 32):
+        pats = edge + windowed_patterns(8, 0, rnd, 64)
+        cases.append(MsmCase(group, "expanded_canonical_cv8_p%d" % npr, _b_list(rnd, 3), [KIND_WIDE] * 3, range(3), _matrix([_rot(pats, k, 64) for k in range(3)], 64), 4, 6, cv=8, mont=0,
+                             nproofs=npr, expect={2: 3, 0: 96, 1: 0}))
+    # ---- the byte plane: entries 0, 1, -1 and WS_PLANE_WIDE; the 32-byte rows the plane covers hold OTHER valid values ----
+    for batch, npr in ((128, 0), (64, 5)):
+        nb = 24
+        kinds = [KIND_BIT] * 16 + [KIND_NARROW] * 8
+        lens = [0] * 16 + [5] * 8
+        cols = [[rnd.randrange(R) for _ in range(batch)] for _ in range(nb)]      # what a kernel reading the wrong source would use
+        stride, prow = nb + 3, nb - 2                                             # the last two narrow rows lie outside the plane
+        plane = bytearray((batch // 64) * stride * 64)
+        for r in range(prow):
+            for p in range(batch):
+                wide_here = (r == 5 and p >= 64) or (r >= 16 and (p + r) % 3 == 0)      # group 0 of the second wave; some narrow entries
+                t = WS_PLANE_WIDE if wide_here else rnd.choice((0, 1, -1))
+                plane[((p >> 6) * stride + r) * 64 + (p & 63)] = t & 0xFF
+                if wide_here:
+                    cols[r][p] = rnd.choice((0, 1, R - 1)) if r < 16 and p % 2 else flat_patterns(5, rnd, 24)[(p + r) % 24]
+        for r in range(prow, nb):
+            cols[r] = _rot(flat_patterns(5, rnd, batch), r, batch)
+        flat("plane_batch%d_p%d" % (batch, npr), kinds, lens, cols, batch=batch, nproofs=npr, plane=bytes(plane), plane_rows=prow, plane_stride=stride, expect={1: 16})
+    names = [c.name for c in cases]
+    assert len(set(names)) == len(names)
+    return cases
+
+
+_msm_case_cache = {}
+
+
+def msm_case_table(group):
+    if group not in _msm_case_cache:
+        _msm_case_cache[group] = {c.name: c for c in msm_cases(group)}
+    return _msm_case_cache[group]
+
+
+MSM_CASE_NAMES = None
+
+
+def msm_case_names():
+    global MSM_CASE_NAMES
+    if MSM_CASE_NAMES is None:
+        MSM_CASE_NAMES = list(msm_case_table(0))
+        assert MSM_CASE_NAMES == list(msm_case_table(1))
+    return MSM_CASE_NAMES
