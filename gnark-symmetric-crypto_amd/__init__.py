@@ -28,7 +28,7 @@ EXPORTS = ["enforce_binding", "InitAlgorithm", "Free", "Prove", "ProveBatch", "g
            "gsc_prove_check_init", "gsc_prove_check_stats", "gsc_debug_prove_corrupt",
            "gsc_release_algorithm", "gsc_replace_algorithm", "gsc_memory_info", "gsc_key_generation",
            "gsc_setup_contribute", "gsc_setup_verify_contribution", "gsc_debug_scale_points",
-           "gsc_srs_verify", "gsc_debug_srs_generate", "gsc_debug_group_idft", "gsc_debug_column_sums", "gsc_setup_from_srs", "gsc_debug_msm"]
+           "gsc_srs_verify", "gsc_debug_srs_generate", "gsc_debug_group_idft", "gsc_debug_column_sums", "gsc_setup_from_srs", "gsc_debug_msm", "gsc_debug_solve"]
 
 
 class GoSlice(C.Structure):
@@ -47,6 +47,21 @@ class DebugMsmArgs(C.Structure):      # struct gsc_debug_msm_args of include/lib
                 ("flat_digits", C.c_void_p), ("flat_digits_cap", C.c_size_t), ("win_digits", C.c_void_p), ("win_digits_cap", C.c_size_t),
                 ("gok", C.c_void_p), ("gok_cap", C.c_size_t), ("group_ok", C.c_void_p), ("group_ok_cap", C.c_size_t),
                 ("info", C.c_void_p)]
+
+
+class DebugSolveArgs(C.Structure):      # struct gsc_debug_solve_args of include/libprove.h
+    _fields_ = [("n_public", C.c_uint32), ("n_secret", C.c_uint32), ("n_internal", C.c_uint32), ("n_constraints", C.c_uint32),
+                ("calldata", C.c_void_p), ("n_calldata", C.c_uint32),
+                ("blueprint", C.c_void_p), ("constraint_off", C.c_void_p), ("wire_off", C.c_void_p), ("n_instr", C.c_uint32),
+                ("bp_kind", C.c_char_p), ("bp_entries", C.c_void_p), ("bp_entries_len", C.c_void_p), ("n_blueprints", C.c_uint32),
+                ("coeff", C.c_void_p), ("n_coeff", C.c_uint32),
+                ("has_commitment", C.c_int32), ("commit_wire", C.c_uint32), ("commit_private", C.c_void_p), ("n_commit_private", C.c_uint32),
+                ("in_W", C.c_char_p), ("mask", C.c_char_p), ("commit", C.c_char_p),
+                ("batch", C.c_uint32), ("nproofs", C.c_uint32), ("workgroups", C.c_uint32), ("mode", C.c_int32),
+                ("class_w", C.c_char_p), ("class_a", C.c_char_p), ("class_b", C.c_char_p), ("class_c", C.c_char_p),
+                ("fill", C.c_uint32),
+                ("W", C.c_void_p), ("W_cap", C.c_size_t), ("A", C.c_void_p), ("A_cap", C.c_size_t), ("B", C.c_void_p), ("B_cap", C.c_size_t), ("C", C.c_void_p), ("C_cap", C.c_size_t),
+                ("status", C.c_void_p), ("flag", C.c_void_p), ("info", C.c_void_p), ("why", C.c_void_p)]
 
 
 class ProveReturn(C.Structure):
@@ -158,6 +173,8 @@ def lib():
         L.gsc_debug_group_idft.argtypes = [C.c_int, C.c_int, C.c_char_p, C.c_void_p, C.c_void_p]
         L.gsc_debug_msm.restype = C.c_int
         L.gsc_debug_msm.argtypes = [C.POINTER(DebugMsmArgs)]
+        L.gsc_debug_solve.restype = C.c_int
+        L.gsc_debug_solve.argtypes = [C.POINTER(DebugSolveArgs)]
         L.gsc_debug_column_sums.restype = C.c_int
         L.gsc_debug_column_sums.argtypes = [C.c_int, C.c_uint32, C.c_char_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_char_p, C.c_void_p, C.c_void_p]
         L.enforce_binding()
@@ -392,6 +409,37 @@ def debug_msm(group: int, points: bytes, kind, rowlen, rows, scalars, n_rows: in
     info = list(info)
     return {"out": out.raw[:w * ncols], "inf": oinf.raw[:ncols], "flat_digits": fd.raw[:info[48]], "win_digits": wd.raw[:info[49]],
             "gok": gk.raw[:info[50]], "group_ok": gr.raw[:info[51]], "info": info}
+
+
+def debug_solve(desc: dict, in_W: bytes, batch: int = 64, nproofs: int = 0, workgroups: int = 0, mode: int = 0, mask: bytes = None, commit: bytes = None,
+                classes=None, fill: int = 0xA5, caps=None):
+    """TEST HOOK: the witness solver kernels on a caller's constraint system; see gsc_debug_solve in include/libprove.h.  desc: the R1CS fields
+    (n_public, n_secret, n_internal, n_constraints, calldata, blueprint, constraint_off, wire_off, bp_kind, bp_entries (one list per blueprint),
+    coeff (Montgomery integers), has_commitment, commit_wire, commit_private); in_W / mask / commit: 32 little-endian bytes per Montgomery value,
+    [wire][column]; classes: (class_w, class_a, class_b, class_c) for mode 1; caps: byte capacities of (W, A, B, C) when not the exact need.
+    -> dict: rc, W, A, B, C (bytes as stored), status, flag, info (32 integers), why."""
+    nw, nc = desc["n_public"] + desc["n_secret"] + desc["n_internal"], desc["n_constraints"]
+    u32 = lambda v: (C.c_uint32 * max(1, len(v)))(*v)
+    vp = lambda b: C.cast(b, C.c_void_p)
+    cd, bp, co, wo = u32(desc["calldata"]), u32(desc["blueprint"]), u32(desc["constraint_off"]), u32(desc["wire_off"])
+    ents = u32([w for e in desc["bp_entries"] for w in e]); elen = u32([len(e) for e in desc["bp_entries"]])
+    coeff = b"".join(int(v).to_bytes(32, "little") for v in desc["coeff"])
+    cbuf = C.create_string_buffer(coeff, max(1, len(coeff)))
+    cpriv = u32(desc.get("commit_private") or [])
+    assert len(in_W) == 32 * batch * (desc["n_public"] + desc["n_secret"])
+    need = [32 * batch * nw] + [32 * batch * nc] * 3
+    caps = list(caps or need)
+    bufs = [C.create_string_buffer(max(1, c)) for c in caps]
+    status, flag, info, why = (C.c_uint32 * batch)(), (C.c_uint32 * 1)(), (C.c_uint32 * 32)(), C.create_string_buffer(128)
+    cls = [bytes(c) for c in classes] if classes else [None] * 4
+    args = DebugSolveArgs(desc["n_public"], desc["n_secret"], desc["n_internal"], nc, vp(cd), len(desc["calldata"]), vp(bp), vp(co), vp(wo), len(desc["blueprint"]),
+                          bytes(desc["bp_kind"]), vp(ents), vp(elen), len(desc["bp_kind"]), vp(cbuf), len(desc["coeff"]),
+                          1 if desc.get("has_commitment") else 0, desc.get("commit_wire", 0), vp(cpriv), len(desc.get("commit_private") or []),
+                          in_W, mask, commit, batch, nproofs, workgroups, mode, cls[0], cls[1], cls[2], cls[3], fill,
+                          vp(bufs[0]), caps[0], vp(bufs[1]), caps[1], vp(bufs[2]), caps[2], vp(bufs[3]), caps[3], vp(status), vp(flag), vp(info), vp(why))
+    rc = lib().gsc_debug_solve(C.byref(args))
+    return {"rc": rc, "W": bufs[0].raw[:need[0]], "A": bufs[1].raw[:need[1]], "B": bufs[2].raw[:need[2]], "C": bufs[3].raw[:need[3]],
+            "status": list(status), "flag": flag[0], "info": list(info), "why": why.value.decode("utf-8", "replace")}
 
 
 def prove_raw(cipher: int, records: bytes, n: int):

@@ -15,6 +15,7 @@
 #include "phase2_gpu.hpp"
 #include "srs_gpu.hpp"
 #include "msm_debug.hpp"
+#include "solver_debug.hpp"
 #include <sys/random.h>
 #include <cerrno>
 #include <condition_variable>
@@ -517,6 +518,11 @@ int gsc_debug_column_sums(int group, uint32_t n_rows, const uint8_t* rows, uint3
 int gsc_debug_msm(const gsc_debug_msm_args* args) {
     if (hooks_refused("gsc_debug_msm") || !args) return -1;
     try { debug_msm(config_from_env().device, *args); return 0; }
+    catch (const std::exception& e) { printf("%s\n", e.what()); return -1; }
+}
+int gsc_debug_solve(const gsc_debug_solve_args* args) {
+    if (hooks_refused("gsc_debug_solve") || !args) return -1;
+    try { return debug_solve(config_from_env().device, *args); }
     catch (const std::exception& e) { printf("%s\n", e.what()); return -1; }
 }
 int gsc_debug_srs_generate(int L, const uint8_t* seed32, void** srs, size_t* len) {

@@ -8,6 +8,7 @@
 #include "formats.hpp"
 #include "kernels.hpp"
 #include "wit_small.hpp"
+#include "solver_tables.hpp"
 #include "wipe_plan.hpp"
 #include "prove_check.hpp"
 #include <atomic>
@@ -21,26 +22,6 @@
 #include <vector>
 
 namespace gsc {
-
-#define HIP_CHECK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) throw std::runtime_error(std::string("HIP error: ") + hipGetErrorString(e_) + " at " #expr); } while (0)
-
-// alloc_lane points this at the lane's byte count for its duration: every DevBuf the thread allocates meanwhile is counted, so that the lane's
-// region table (wipe_plan.hpp) can be held against what was really allocated
-inline thread_local size_t* devbuf_tally = nullptr;
-
-template <class T>
-struct DevBuf {
-    T* p = nullptr; size_t n = 0;
-    bool secret = false;      // a temporary that holds a call's data: zeroed before it is freed, also when an exception unwinds (like setup_dev.hip's Buf)
-    DevBuf() = default;
-    explicit DevBuf(size_t count, bool is_secret = false) : secret(is_secret) { alloc(count); }
-    DevBuf(const DevBuf&) = delete; DevBuf& operator=(const DevBuf&) = delete;
-    ~DevBuf() { release(); }
-    void release() { if (p) { if (secret) { (void)hipMemset(p, 0, n * sizeof(T)); (void)hipDeviceSynchronize(); } (void)hipFree(p); p = nullptr; } }
-    void alloc(size_t count) { release(); n = count; if (count) { HIP_CHECK(hipMalloc((void**)&p, count * sizeof(T))); if (devbuf_tally) *devbuf_tally += count * sizeof(T); } }
-    void upload(const T* src, size_t count, hipStream_t s) { HIP_CHECK(hipMemcpyAsync(p, src, count * sizeof(T), hipMemcpyHostToDevice, s)); }
-    size_t bytes() const { return n * sizeof(T); }
-};
 
 // page-locked host memory: the staging buffers of a lane (uploads and downloads are then real asynchronous DMA, not driver-staged copies)
 template <class T>
@@ -109,13 +90,6 @@ struct MsmSet {                     // one fixed-base MSM of the proving key (ke
     bool latency_flat() const { return !nwide || few_wide; }       // calls with a handful of statements need no windowed kernel for this set
 };
 
-// The resident solver kernel (k_solver_few) spins at device-wide barriers, so two of them must never share the device: each could
-// hold CUs the other's missing workgroups are waiting for.  Launches are therefore chained on the device: a launch first makes its
-// stream wait for the previous one's completion event (no host blocking).  Other processes on the same device are not covered —
-// there the kernel's bounded polling gives up and the call is solved again with one launch per level (prove_chunk).
-struct FewSolverChain { std::mutex m; hipEvent_t last = nullptr; };
-FewSolverChain& few_solver_chain(int device);      // one per device, never destroyed (lanes may outlive static destructors): engine_prove.hip
-
 // The engines' streams come from a process-wide pool and go back to it, drained, when an engine goes: the HIP runtime binds a stream to one of
 // its hardware queues when the stream is created, and a queue keeps the scratch memory its kernels needed for the life of the process.  An
 // engine built after a release on NEW streams lands on other queues, and the process grows by their scratch (measured once per queue: 632 MiB at
@@ -129,11 +103,11 @@ void stream_give(int device, int kind, int role, hipStream_t s);    // waits for
 // bytes the complete prover replicas on a device hold (AlgorithmImpl::accounted; gsc_memory_info): engine_tables.hip
 std::atomic<size_t>& prover_bytes_on(int device);
 
-class AlgorithmImpl {
+// (the solver's tables — program, schedule, coefficients, the small-integer program — and the circuit's sizes: SolverTables, solver_tables.hpp)
+class AlgorithmImpl : public SolverTables {
   public:
     Cipher cipher; EngineConfig cfg;
-    size_t n_wires = 0, n_public = 0, n_inputs = 0, n_constraints = 0, domain_n = 0; int L = 0;      // n_inputs: public + secret wires (what k_assign_* writes)
-    bool has_commitment = false;
+    size_t domain_n = 0; int L = 0;
     // lanes are handed out one chunk at a time; concurrent calls (and the chunks of one call) take whichever lane is free
     std::mutex pool_mu; std::condition_variable pool_cv; std::vector<uint8_t> lane_busy;
     // a free lane that can hold n statements — the smallest such lane, so that small calls leave the full-capacity lanes to big ones
@@ -168,16 +142,7 @@ class AlgorithmImpl {
     size_t table_bytes = 0;
     std::vector<uint8_t> row_class;    // per scalar row (wire), predicted by calibrate(): 0 = always 0 or 1, 1 = also -1, else the largest bit length seen (255 = unknown)
 
-    // program
-    DevBuf<uint32_t> prog, sched, lookup_coeff; DevBuf<fe> coeff, coeff_inv;
-    DevBuf<uint32_t> few_count_ops, few_count_qoff; std::vector<uint32_t> few_count_first;
-    DevBuf<uint32_t> few_ops, few_terms, few_lstart;          // the same program laid out for k_solver_few (formats.hpp FewProgram)
-    uint32_t n_levels = 0, commit_level = 0; std::vector<uint32_t> level_width; std::vector<uint8_t> level_kind; std::vector<uint32_t> level_long; int has_div = 0;
-    // The small-integer witness path (wit_small.hpp): built after calibrate() for circuits that qualify (ChaCha20-V3); small.ok says so.
-    // small keeps the sizes and the per-row classes; the item lists live on the device.
-    SmallProgram small; std::vector<uint8_t> row_class_a, row_class_b;
-    DevBuf<uint32_t> ws_tiny, ws_parts, ws_bits, ws_twire, ws_levels, ws_rtiny, ws_rgen, ws_rtwire; DevBuf<long long> ws_tcoef, ws_rtcoef;
-    DevBuf<uint8_t> ws_cls_a, ws_cls_b, ws_cls_c;      // per constraint row: 0 = byte plane, 1 = 32-byte element
+    std::vector<uint8_t> row_class_a, row_class_b;      // the calibration classes of the rows of a and b (the small-integer path's byte planes)
     void init_small(const SolverProgram& sp);
     std::atomic<uint64_t> small_fallbacks{0};      // chunks that had to be solved again generically (gsc_describe)
     // NTT

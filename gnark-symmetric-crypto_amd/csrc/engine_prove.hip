@@ -247,52 +247,15 @@ void AlgorithmImpl::stage_upload(Lane& ln, const Chunk& ck) {
 }
 
 void AlgorithmImpl::run_levels(Lane& ln, const Chunk& ck, SolverArgs& sa, uint32_t from, uint32_t to) {
-    const bool resident = ck.rt.resident;
-    SolverFewArgs fa{few_ops.p, few_terms.p, few_lstart.p, 0, 0, coeff.p, coeff_inv.p, lookup_coeff.p, ln.d_W.p, ln.d_A.p, ln.d_B.p, ln.d_C.p, ck.B, (uint32_t)ck.n,
-                     ln.d_status.p, sa.mask, sa.commit, ln.d_fsync.p, 1u << 21, 0u, n_levels, nullptr};
-    if (cfg.few_test_abort) { fa.poll_limit = 256; fa.test_missing = 1; }      // test: the barrier never fills
-    for (uint32_t l = from; l < to; l++) {
-        sa.first_level = l; sa.n_long = level_long[l];
-        if (level_kind[l]) {
-            if (resident) launch_solver_count_few(sa, few_count_ops.p, few_count_qoff.p, few_count_first[l], level_width[l], ck.n, ln.stream);
-            else launch_solver_count_level(sa, level_width[l], ln.stream);
-        } else if (resident) {                   // a run of generic levels: one launch, device-wide barriers in between
-            uint32_t e = l + 1; while (e < to && !level_kind[e]) e++;
-            fa.from = l; fa.to = e; fa.trace = sa.trace;
-            HIP_CHECK(hipMemsetAsync(ln.d_fsync.p, 0, 4, ln.stream));
-            {
-                FewSolverChain& chain = few_solver_chain(cfg.device);
-                std::lock_guard<std::mutex> lk(chain.m);
-                if (chain.last && chain.last != ln.ev_few) HIP_CHECK(hipStreamWaitEvent(ln.stream, chain.last, 0));
-                // measured: 128 workgroups best for 1-2 statements, 256 (one per CU) beyond; never more than the device has CUs
-                // (every workgroup must be resident: one per CU by construction) — the kernel works with any grid
-                uint32_t wgs = cfg.few_workgroups ? (uint32_t)cfg.few_workgroups : (ck.n <= 2 ? 128u : 256u);
-                if (wgs > (uint32_t)cu_count) wgs = (uint32_t)cu_count;
-                launch_solver_few(fa, has_div, wgs, ln.stream);
-                HIP_CHECK(hipEventRecord(ln.ev_few, ln.stream));
-                chain.last = ln.ev_few;
-            }
-            l = e - 1;
-        } else launch_solver_level(sa, level_width[l], ln.stream);
-    }
+    SolverWalk walk;
+    walk.n = ck.n; walk.resident = ck.rt.resident; walk.workgroups = cfg.few_workgroups > 0 ? (uint32_t)cfg.few_workgroups : 0u; walk.cu_count = cu_count; walk.device = cfg.device;
+    walk.test_abort = cfg.few_test_abort != 0; walk.fsync = ln.d_fsync.p; walk.ev_few = ln.ev_few;
+    solver_run_levels(*this, sa, walk, from, to, ln.stream);
 }
 
 // Circuits whose witness is small integers (ChaCha20-V3): the integer kernels on byte planes (wit_small.hpp) instead of the level launches
 void AlgorithmImpl::solve_small(Lane& ln, const Chunk& ck) {
-    const size_t B = ck.B;
-    HIP_CHECK(hipMemsetAsync(ln.d_wsflag.p, 0, 4, ln.stream));
-    launch_wit_narrow(ln.d_W.p, B, n_inputs, ln.d_W8.p, small.rows_per_group, ln.d_wsflag.p, ln.stream);
-    launch_wit_chain(WitChainArgs{ws_tiny.p, ws_parts.p, ws_bits.p, ws_twire.p, ws_tcoef.p, ws_levels.p, small.n_levels, ln.d_W8.p, small.rows_per_group, ln.d_wsflag.p}, B / 64, 512 * (size_t)small.max_slots, ln.stream);
-    const uint32_t per_chunk = 4 * WS_IB;
-    launch_wit_rows(WitRowsArgs{ws_rtiny.p, small.n_rtiny, per_chunk, (small.n_rtiny + per_chunk - 1) / per_chunk, ws_rgen.p, small.n_rgen, ws_rtwire.p, ws_rtcoef.p, ln.d_W8.p, small.rows_per_group,
-                                ln.d_A8.p, ln.d_B8.p, ln.d_C8.p, n_constraints, ln.d_A.p, ln.d_B.p, ln.d_C.p, B, ln.d_status.p, ln.d_wsflag.p}, B / 64, ln.stream);
-    // The consumers (first transform kernel, flat recoders) read the byte planes; the 32-byte matrices only hold the rows predicted wide.
-    if (ck.dbg) {      // debug dumps want every row as a 32-byte element
-        launch_wit_expand(ln.d_W8.p, small.rows_per_group, n_wires, nullptr, ln.d_W.p, B, ln.stream);
-        launch_wit_expand(ln.d_A8.p, n_constraints, n_constraints, ws_cls_a.p, ln.d_A.p, B, ln.stream);
-        launch_wit_expand(ln.d_B8.p, n_constraints, n_constraints, ws_cls_b.p, ln.d_B.p, B, ln.stream);
-        launch_wit_expand(ln.d_C8.p, n_constraints, n_constraints, ws_cls_c.p, ln.d_C.p, B, ln.stream);
-    }
+    solver_run_small(*this, SmallBuffers{ln.d_W.p, ln.d_A.p, ln.d_B.p, ln.d_C.p, ln.d_W8.p, ln.d_A8.p, ln.d_B8.p, ln.d_C8.p, ln.d_status.p, ln.d_wsflag.p}, ck.B, ck.dbg != nullptr, ln.stream);
 }
 
 void AlgorithmImpl::dump_solver_trace(Lane& ln, const unsigned long long* d_trace) {

@@ -11,18 +11,6 @@
 
 namespace gsc {
 
-namespace {
-// Montgomery images of 0, 1, 2, -1, -2 in Fr: gnark puts these at coefficient ids 0..4 of every R1CS
-// (SURVEY.md App. A); the solver kernel short-cuts them to additions.
-const uint32_t kSmallCoeffs[5][8] = {
-    {0x00000000u, 0x00000000u, 0x00000000u, 0x00000000u, 0x00000000u, 0x00000000u, 0x00000000u, 0x00000000u},
-    {0x4ffffffbu, 0xac96341cu, 0x9f60cd29u, 0x36fc7695u, 0x7879462eu, 0x666ea36fu, 0x9a07df2fu, 0x0e0a77c1u},
-    {0x9ffffff6u, 0x592c6838u, 0x3ec19a53u, 0x6df8ed2bu, 0xf0f28c5cu, 0xccdd46deu, 0x340fbe5eu, 0x1c14ef83u},
-    {0xa0000006u, 0x974bc177u, 0xda58a367u, 0xf13771b2u, 0x0908122eu, 0x51e1a247u, 0x4729c0fau, 0x2259d6b1u},
-    {0x5000000bu, 0xeab58d5bu, 0x3af7d63du, 0xba3afb1du, 0x908ecc00u, 0xeb72fed7u, 0xad21e1cau, 0x144f5eefu},
-};
-}  // namespace
-
 AlgorithmImpl::AlgorithmImpl(Cipher c, const uint8_t* pk, size_t pk_len, const uint8_t* r1cs, size_t r1cs_len, const EngineConfig& cf) : cipher(c), cfg(cf) {
     // measured crossover with the batch kernels (one 64-column batch: 12.9 ms ChaCha20, 43.7 ms AES): 32 statements for ChaCha20 (10.2 ms), ~23 for AES (8.2 ms + 1.6 ms each: 38.4 ms for 20)
     if (!cfg.few_max) cfg.few_max = cipher == CHACHA20 ? 32 : 20;
@@ -107,69 +95,18 @@ std::atomic<size_t>& prover_bytes_on(int device) {
 }
 
 std::unique_ptr<SolverProgram> AlgorithmImpl::init_program(const R1csFile& cs) {
-    n_wires = cs.n_wires(); n_public = cs.n_public; n_inputs = cs.n_public + cs.n_secret; n_constraints = cs.n_constraints; has_commitment = cs.has_commitment;
     const size_t expect_in = cipher == CHACHA20 ? 1408 : cipher == AES_128 ? 157 : 173;
     if (cs.n_public - 1 + cs.n_secret != expect_in) throw std::runtime_error("r1cs: witness size does not match the cipher's circuit");
-    if (cs.n_coeff() < 5 || memcmp(cs.coeff_limbs.data(), kSmallCoeffs, sizeof kSmallCoeffs)) throw std::runtime_error("r1cs: coefficient ids 0..4 are not 0,1,2,-1,-2");
-    std::unique_ptr<SolverProgram> keep(new SolverProgram(build_solver_program(cs)));
-    const SolverProgram& sp = *keep;
-    n_levels = (uint32_t)sp.n_levels; commit_level = (uint32_t)sp.commit_level; has_div = sp.n_inversions ? 1 : 0;
-    level_width.resize(n_levels); for (uint32_t l = 0; l < n_levels; l++) level_width[l] = sp.sched[2 + l] - sp.sched[1 + l];
-    level_kind = sp.level_kind; level_long = sp.level_long;
-    prog.alloc(sp.words.size()); prog.upload(sp.words.data(), sp.words.size(), stream);
-    sched.alloc(sp.sched.size()); sched.upload(sp.sched.data(), sp.sched.size(), stream);
-    {
-        const FewProgram fp = build_few_program(sp);
-        few_ops.alloc(fp.ops.size() ? fp.ops.size() : 8); few_terms.alloc(fp.terms.size()); few_lstart.alloc(fp.level_start.size());
-        if (!fp.ops.empty()) few_ops.upload(fp.ops.data(), fp.ops.size(), stream);
-        few_terms.upload(fp.terms.data(), fp.terms.size(), stream); few_lstart.upload(fp.level_start.data(), fp.level_start.size(), stream);
-        few_count_first = fp.count_first;
-        few_count_ops.alloc(fp.count_ops.size() + 4); few_count_qoff.alloc(fp.count_qoff.size() + 1);
-        if (!fp.count_ops.empty()) { few_count_ops.upload(fp.count_ops.data(), fp.count_ops.size(), stream); few_count_qoff.upload(fp.count_qoff.data(), fp.count_qoff.size(), stream); }
-    }
-    lookup_coeff.alloc(sp.lookup_coeff.size() ? sp.lookup_coeff.size() : 1);
-    if (!sp.lookup_coeff.empty()) lookup_coeff.upload(sp.lookup_coeff.data(), sp.lookup_coeff.size(), stream);
-    coeff.alloc(cs.n_coeff()); coeff_inv.alloc(cs.n_coeff());
-    HIP_CHECK(hipMemcpyAsync(coeff.p, cs.coeff_limbs.data(), cs.coeff_limbs.size() * 4, hipMemcpyHostToDevice, stream));
-    launch_fr_inverse(coeff.p, coeff_inv.p, cs.n_coeff(), stream);
-    if (!sp.count_ops.empty()) {      // lookup histograms rely on table row i carrying index i: verify once, on the device
-        DevBuf<uint32_t> d_ops(sp.count_ops.size()), d_flag(1); uint32_t flag = 0;
-        d_ops.upload(sp.count_ops.data(), sp.count_ops.size(), stream);
-        HIP_CHECK(hipMemsetAsync(d_flag.p, 0, 4, stream));
-        launch_check_count_tables(prog.p, coeff.p, d_ops.p, (uint32_t)sp.count_ops.size(), d_flag.p, stream);
-        HIP_CHECK(hipMemcpyAsync(&flag, d_flag.p, 4, hipMemcpyDeviceToHost, stream));
-        HIP_CHECK(hipStreamSynchronize(stream));
-        if (flag) throw std::runtime_error("r1cs: unsupported lookup table (index column is not 0..n-1)");
-    }
-    HIP_CHECK(hipStreamSynchronize(stream));
-    return keep;
+    return build_tables(cs, stream);
 }
 
-// The small-integer witness program (wit_small.hpp), when the circuit qualifies: coefficients as integers (from the device: no field
-// arithmetic on the host), the calibration classes of wires and constraint rows, the item lists uploaded once.
+// The small-integer witness program (wit_small.hpp) from the calibration classes, when the circuit qualifies (solver_tables.hip)
 void AlgorithmImpl::init_small(const SolverProgram& sp) {
     if (!cfg.small_witness) return;
-    const size_t nc = coeff.n;
-    DevBuf<long long> d_c(nc ? nc : 1); DevBuf<uint8_t> d_ok(nc ? nc : 1);
-    std::vector<long long> hc(nc); std::vector<uint8_t> ok(nc);
-    launch_coeff_small(coeff.p, nc, d_c.p, d_ok.p, stream);
-    HIP_CHECK(hipGetLastError());
-    if (nc) { HIP_CHECK(hipMemcpyAsync(hc.data(), d_c.p, nc * 8, hipMemcpyDeviceToHost, stream)); HIP_CHECK(hipMemcpyAsync(ok.data(), d_ok.p, nc, hipMemcpyDeviceToHost, stream)); }
-    HIP_CHECK(hipStreamSynchronize(stream));
-    std::vector<int64_t> ci(hc.begin(), hc.end());
     std::vector<uint8_t> ca = row_class_a, cb = row_class_b, cc = row_class_c;
     if (cfg.small_witness == 2) { std::fill(ca.begin(), ca.end(), 0); std::fill(cb.begin(), cb.end(), 0); std::fill(cc.begin(), cc.end(), 0); }      // test: wrong on purpose
-    small = build_small_program(sp, n_wires, n_constraints, ci, ok, row_class, ca, cb, cc);
+    build_small_tables(sp, row_class, ca, cb, cc, stream);
     if (cfg.trace_host) fprintf(stderr, "InitAlgorithm(%d): small-integer witness path: %s%s\n", (int)cipher, small.ok ? "yes" : "no — ", small.ok ? "" : small.why.c_str());
-    if (!small.ok) return;
-    auto up32 = [&](DevBuf<uint32_t>& d, std::vector<uint32_t>& v, size_t pad) { v.resize(v.size() + pad, 0u); d.alloc(v.size()); d.upload(v.data(), v.size(), stream); };
-    auto up64 = [&](DevBuf<long long>& d, std::vector<int64_t>& v, size_t pad) { v.resize(v.size() + pad, 0); d.alloc(v.size()); d.upload(reinterpret_cast<const long long*>(v.data()), v.size(), stream); };
-    // (the kernels fetch descriptors and terms a whole wave at a time: 128 / 64 words beyond the last item may be read)
-    up32(ws_tiny, small.tiny, 128); up32(ws_parts, small.parts, 4); up32(ws_bits, small.bits, 4); up32(ws_twire, small.twire, 64); up64(ws_tcoef, small.tcoef, 64); up32(ws_levels, small.levels, 6);
-    up32(ws_rtiny, small.rtiny, 128); up32(ws_rgen, small.rgen, 8); up32(ws_rtwire, small.rtwire, 64); up64(ws_rtcoef, small.rtcoef, 64);
-    ws_cls_a.alloc(n_constraints); ws_cls_b.alloc(n_constraints); ws_cls_c.alloc(n_constraints);
-    ws_cls_a.upload(small.cls_a.data(), n_constraints, stream); ws_cls_b.upload(small.cls_b.data(), n_constraints, stream); ws_cls_c.upload(small.cls_c.data(), n_constraints, stream);
-    HIP_CHECK(hipStreamSynchronize(stream));
 }
 
 void AlgorithmImpl::pack_inputs(const ProofRequest* reqs, size_t n, size_t B, uint8_t* h_in, uint8_t* h_rs) {
@@ -220,10 +157,7 @@ void AlgorithmImpl::calibrate() {
     HIP_CHECK(hipMemsetAsync(d_status.p, 0xFF, B * 4, stream));
     SolverArgs sa{prog.p, sched.p, 0, n_levels, coeff.p, coeff_inv.p, lookup_coeff.p, d_W.p, d_A.p, d_B.p, d_C.p, B, d_status.p,
                   has_commitment ? d_mask.p : nullptr, has_commitment ? d_commit.p : nullptr, has_div, 0u, nullptr};
-    for (uint32_t l = 0; l < n_levels; l++) {
-        sa.first_level = l; sa.n_long = level_long[l];
-        if (level_kind[l]) launch_solver_count_level(sa, level_width[l], stream); else launch_solver_level(sa, level_width[l], stream);
-    }
+    { SolverWalk walk; walk.n = B; solver_run_levels(*this, sa, walk, 0, n_levels, stream); }      // one launch per level
     DevBuf<uint8_t> d_cls(n_wires);
     launch_classify_wires(d_W.p, n_wires, B, d_status.p, d_cls.p, stream);
     HIP_CHECK(hipGetLastError());

@@ -286,7 +286,7 @@ SolverProgram build_solver_program(const R1csFile& cs) {
         const auto& e = cs.bp_entries[b];
         if (e.size() != 256 * 3) throw std::runtime_error("solver: lookup table is not 256 constant entries");
         table_of_bp[b] = int(sp.n_tables++);
-        for (size_t k = 0; k < 256; k++) { if (e[3 * k] != 1 || e[3 * k + 2] != WIRE_CONST) throw std::runtime_error("solver: non-constant lookup entry"); sp.lookup_coeff.push_back(e[3 * k + 1]); }
+        for (size_t k = 0; k < 256; k++) { if (e[3 * k] != 1 || e[3 * k + 2] != WIRE_CONST) throw std::runtime_error("solver: non-constant lookup entry"); if (e[3 * k + 1] >= cs.n_coeff()) throw std::runtime_error("solver: coefficient id out of range"); sp.lookup_coeff.push_back(e[3 * k + 1]); }
     }
     auto& W = sp.words;
     std::vector<uint32_t> wire_level(nw, 0);          // level at which a wire's value becomes available (inputs: 0)

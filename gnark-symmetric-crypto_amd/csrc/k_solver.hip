@@ -840,10 +840,11 @@ void launch_solver_few(const SolverFewArgs& a, int has_div, uint32_t workgroups,
     if (has_div) hipLaunchKernelGGL(k_solver_few<true>, dim3(workgroups), dim3(64 * FEW_WAVES), dyn, s, a);
     else hipLaunchKernelGGL(k_solver_few<false>, dim3(workgroups), dim3(64 * FEW_WAVES), dyn, s, a);
 }
+uint32_t solver_level_wpb(size_t batch) { return batch <= 2048 ? 8 : 4; }      // measured: 8 waves cut the witness time by 12 % at batch <= 1024 and cost 15 % at 8192
 void launch_solver_level(const SolverArgs& a, uint32_t level_width, hipStream_t s) {
     if (!level_width) return;
     const uint32_t n_short = level_width - a.n_long;
-    const uint32_t wpb = a.batch <= 2048 ? 8 : 4;      // measured: 8 waves cut the witness time by 12 % at batch <= 1024 and cost 15 % at 8192
+    const uint32_t wpb = solver_level_wpb(a.batch);
     const dim3 grid((unsigned)(a.batch / 64), a.n_long + (n_short + wpb - 1) / wpb), block(64 * wpb);
     // the division-free variant (ChaCha20-V3 never divides) carries no call to the inversion routine and so needs no
     // scratch memory: a kernel with scratch pays a per-dispatch setup that dominated the 163 short level launches

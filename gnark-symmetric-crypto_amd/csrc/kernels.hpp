@@ -81,6 +81,7 @@ struct SolverArgs {
 };
 // executes level a.first_level, which holds `level_width` instructions
 void launch_solver_level(const SolverArgs& a, uint32_t level_width, hipStream_t s);
+uint32_t solver_level_wpb(size_t batch);      // the waves per workgroup (k_solver's WPB: 8 or 4) that launch_solver_level takes for this batch
 // Calls with at most MSM_FEW_PROOFS statements: levels [from, to) (none of them an OP_COUNT level) in one launch of a resident grid,
 // one wave per (statement, op), lanes = terms; program layout: formats.hpp FewProgram.  sync: two words; word 0 (arrival counter) zeroed before every
 // launch, word 1 (a launch gave up at a barrier) zeroed once per call: a launch that finds it set returns at once.

@@ -440,6 +440,47 @@ struct gsc_debug_msm_args {
     uint32_t *info;
 };
 extern int gsc_debug_msm(const struct gsc_debug_msm_args *args);
+/* TEST HOOK: the witness solver kernels alone, on a caller's constraint system: a device, but no key and no InitAlgorithm.  The description is an
+ * R1CS file given field by field, exactly what the parser would have produced; the tables are built and uploaded by the functions InitAlgorithm
+ * uses (csrc/solver_tables.hpp: build_solver_program, build_few_program, the count tables' device check, coeff / coeff_inv, build_small_program) and
+ * the levels run through the engine's own loops (solver_run_levels, solver_run_small).
+ *   n_public (wire 0 included), n_secret, n_internal, n_constraints;
+ *   calldata: n_calldata words, every instruction's first word its own length (the boundaries are derived from it); blueprint / constraint_off /
+ *   wire_off: one word per instruction (n_instr of them);  bp_kind[b]: 0 hint, 1 r1c, 2 lookup;  bp_entries: the EntriesCalldata words of the
+ *   blueprints one after the other, bp_entries_len[b] of them for blueprint b (256 x 3 for a lookup, 0 otherwise);
+ *   coeff: n_coeff x 8 little-endian 32-bit limbs, Montgomery, ids 0..4 being 0, 1, 2, -1, -2;  has_commitment, commit_wire, commit_private;
+ *   in_W: the rows of the public and secret wires, [wire][column], 8 Montgomery limbs each, used as given (the caller sets wire 0);
+ *   mask / commit: one Montgomery value per column for the Randomize / commitment hints, or NULL (zero);
+ *   batch: columns, a multiple of 64 up to 4096;  nproofs: 0 = the batch kernels on every column, 1 .. 32 = the resident kernels on the first
+ *   nproofs columns (batch = 64);  workgroups: the resident grid, 0 = the engine's choice, always clamped to the device's compute units;
+ *   mode: 0 = generic solver, 1 = small-integer path (nproofs = 0) from the class predictions class_w[n_wires], class_a / class_b / class_c
+ *   [n_constraints] (0 = bit, 1 = also -1, more = wide);  fill: the byte W (but its input rows), A, B and C hold before the first kernel.
+ * Outputs: W (n_wires rows), A, B, C (n_constraints rows) as stored: [row][column], 8 Montgomery limbs, with their capacities in bytes; status[batch]
+ * (0xFFFFFFFF: satisfied); flag: the small path's misprediction word; why[128]: SmallProgram::why or the refusing builder's text;
+ * info[32]: 0 levels, 1 commit_level, 2 has_div, 3 ops, 4 WPB of the batch launches (0: none), 5 resident workgroups used, 6 resident launches,
+ * 7 a resident launch gave up at a barrier (the call still returns 0 with what it has), 8 the small program qualified, 9 levels with long ops,
+ * 10 count levels, 11 the largest level_long, 12 / 13 the small chain's levels and the bundles of its widest level (16 waves share them),
+ * 14 + l for l < 18: level l as kind | level_long << 1 | width << 12.
+ * 0 on success; -1 (one line on stdout): hooks disabled, a description the builders refuse, an index out of range, a buffer too small, a batch or
+ * nproofs outside the above; -2: mode 1 and the circuit does not qualify (why says why); -3: a device error. */
+struct gsc_debug_solve_args {
+    uint32_t n_public, n_secret, n_internal, n_constraints;
+    const uint32_t *calldata; uint32_t n_calldata;
+    const uint32_t *blueprint, *constraint_off, *wire_off; uint32_t n_instr;
+    const uint8_t *bp_kind; const uint32_t *bp_entries; const uint32_t *bp_entries_len; uint32_t n_blueprints;
+    const uint32_t *coeff; uint32_t n_coeff;
+    int32_t has_commitment; uint32_t commit_wire; const uint32_t *commit_private; uint32_t n_commit_private;
+    const uint32_t *in_W; const uint32_t *mask; const uint32_t *commit;
+    uint32_t batch, nproofs, workgroups; int32_t mode;
+    const uint8_t *class_w, *class_a, *class_b, *class_c;
+    uint32_t fill;
+    uint32_t *W; size_t W_cap;
+    uint32_t *A; size_t A_cap;
+    uint32_t *B; size_t B_cap;
+    uint32_t *C; size_t C_cap;
+    uint32_t *status; uint32_t *flag; uint32_t *info; char *why;
+};
+extern int gsc_debug_solve(const struct gsc_debug_solve_args *args);
 
 #ifdef __cplusplus
 }
