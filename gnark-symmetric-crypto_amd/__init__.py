@@ -28,7 +28,7 @@ EXPORTS = ["enforce_binding", "InitAlgorithm", "Free", "Prove", "ProveBatch", "g
            "gsc_prove_check_init", "gsc_prove_check_stats", "gsc_debug_prove_corrupt",
            "gsc_release_algorithm", "gsc_replace_algorithm", "gsc_memory_info", "gsc_key_generation",
            "gsc_setup_contribute", "gsc_setup_verify_contribution", "gsc_debug_scale_points",
-           "gsc_srs_verify", "gsc_debug_srs_generate", "gsc_debug_group_idft", "gsc_debug_column_sums", "gsc_setup_from_srs", "gsc_debug_msm", "gsc_debug_solve"]
+           "gsc_srs_verify", "gsc_debug_srs_generate", "gsc_debug_group_idft", "gsc_debug_column_sums", "gsc_setup_from_srs", "gsc_debug_msm", "gsc_debug_solve", "gsc_debug_assemble"]
 
 
 class GoSlice(C.Structure):
@@ -62,6 +62,16 @@ class DebugSolveArgs(C.Structure):      # struct gsc_debug_solve_args of include
                 ("fill", C.c_uint32),
                 ("W", C.c_void_p), ("W_cap", C.c_size_t), ("A", C.c_void_p), ("A_cap", C.c_size_t), ("B", C.c_void_p), ("B_cap", C.c_size_t), ("C", C.c_void_p), ("C_cap", C.c_size_t),
                 ("status", C.c_void_p), ("flag", C.c_void_p), ("info", C.c_void_p), ("why", C.c_void_p)]
+
+
+_ASSEMBLE_SETS = ("a", "b1", "k", "z", "b2", "c", "d", "pok")
+
+
+class DebugAssembleArgs(C.Structure):      # struct gsc_debug_assemble_args of include/libprove.h
+    _fields_ = [("batch", C.c_uint32), ("nproofs", C.c_uint32), ("n_wires", C.c_uint32), ("fill", C.c_uint32)] + \
+               [(s + part, C.c_char_p) for s in _ASSEMBLE_SETS for part in ("_pts", "_inf", "_lam")] + \
+               [("rs", C.c_char_p), ("mask", C.c_char_p), ("glv_in", C.c_char_p)] + \
+               [(n, C.c_void_p) for n in ("out", "flags", "tmp", "tmp_inf", "cpts", "commit", "W", "mask_out", "glv")]
 
 
 class ProveReturn(C.Structure):
@@ -175,6 +185,8 @@ def lib():
         L.gsc_debug_msm.argtypes = [C.POINTER(DebugMsmArgs)]
         L.gsc_debug_solve.restype = C.c_int
         L.gsc_debug_solve.argtypes = [C.POINTER(DebugSolveArgs)]
+        L.gsc_debug_assemble.restype = C.c_int
+        L.gsc_debug_assemble.argtypes = [C.POINTER(DebugAssembleArgs)]
         L.gsc_debug_column_sums.restype = C.c_int
         L.gsc_debug_column_sums.argtypes = [C.c_int, C.c_uint32, C.c_char_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_char_p, C.c_void_p, C.c_void_p]
         L.enforce_binding()
@@ -440,6 +452,33 @@ def debug_solve(desc: dict, in_W: bytes, batch: int = 64, nproofs: int = 0, work
     rc = lib().gsc_debug_solve(C.byref(args))
     return {"rc": rc, "W": bufs[0].raw[:need[0]], "A": bufs[1].raw[:need[1]], "B": bufs[2].raw[:need[2]], "C": bufs[3].raw[:need[3]],
             "status": list(status), "flag": flag[0], "info": list(info), "why": why.value.decode("utf-8", "replace")}
+
+
+def debug_assemble(batch: int, sets: dict, rs: bytes, nproofs: int = 0, mask: bytes = None, n_wires: int = 3, fill: int = 0xA5, glv_in: bytes = None):
+    """TEST HOOK: the proof assembly kernels on a caller's sums; see gsc_debug_assemble in include/libprove.h.  sets: "a", "b1", "k", "z", "b2" and
+    optionally "c", "d", "pok" -> (points, infinity bytes, scales) as the header lays them out; rs: batch x 64 bytes (r, s little-endian);
+    mask: batch x 32 bytes little-endian; glv_in: 2 x nproofs records of 44 bytes the latency kernel gets instead of glv_split's.  -> dict: rc, out, flags, tmp, tmp_inf, cpts, commit, W, mask_out, glv (bytes as stored; None where
+    the part did not run)."""
+    bufs = {"out": 256 * batch, "flags": batch, "tmp": 128 * batch, "tmp_inf": 2 * batch, "W": 128 * batch}
+    if sets.get("d") is not None:
+        bufs.update(cpts=128 * batch, commit=32 * batch)
+    if mask is not None:
+        bufs["mask_out"] = 32 * batch
+    if nproofs:
+        bufs["glv"] = 88 * nproofs
+    bufs = {k: C.create_string_buffer(max(1, v)) for k, v in bufs.items()}
+    args = DebugAssembleArgs(batch=batch, nproofs=nproofs, n_wires=n_wires, fill=fill, rs=rs, mask=mask, glv_in=glv_in)
+    for name in _ASSEMBLE_SETS:
+        if sets.get(name) is not None:
+            for part, b in zip(("_pts", "_inf", "_lam"), sets[name]):
+                setattr(args, name + part, b)
+    for k, b in bufs.items():
+        setattr(args, k, C.cast(b, C.c_void_p))
+    rc = lib().gsc_debug_assemble(C.byref(args))
+    res = {k: None for k in ("out", "flags", "tmp", "tmp_inf", "cpts", "commit", "W", "mask_out", "glv")}
+    res.update({k: b.raw for k, b in bufs.items()})
+    res["rc"] = rc
+    return res
 
 
 def prove_raw(cipher: int, records: bytes, n: int):

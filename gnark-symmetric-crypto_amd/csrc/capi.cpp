@@ -16,6 +16,7 @@
 #include "srs_gpu.hpp"
 #include "msm_debug.hpp"
 #include "solver_debug.hpp"
+#include "assemble_debug.hpp"
 #include <sys/random.h>
 #include <cerrno>
 #include <condition_variable>
@@ -523,6 +524,11 @@ int gsc_debug_msm(const gsc_debug_msm_args* args) {
 int gsc_debug_solve(const gsc_debug_solve_args* args) {
     if (hooks_refused("gsc_debug_solve") || !args) return -1;
     try { return debug_solve(config_from_env().device, *args); }
+    catch (const std::exception& e) { printf("%s\n", e.what()); return -1; }
+}
+int gsc_debug_assemble(const gsc_debug_assemble_args* args) {
+    if (hooks_refused("gsc_debug_assemble") || !args) return -1;
+    try { debug_assemble(config_from_env().device, *args); return 0; }
     catch (const std::exception& e) { printf("%s\n", e.what()); return -1; }
 }
 int gsc_debug_srs_generate(int L, const uint8_t* seed32, void** srs, size_t* len) {

@@ -440,6 +440,43 @@ struct gsc_debug_msm_args {
     uint32_t *info;
 };
 extern int gsc_debug_msm(const struct gsc_debug_msm_args *args);
+/* TEST HOOK: the proof assembly kernels alone, on a caller's MSM sums and scalars: no key, no circuit, no InitAlgorithm.  Every sum is given as an
+ * affine point, an infinity byte and a scale l != 0 per column and reaches the kernels as the XYZZ image (x l^2, y l^3, l^2, l^3), four zeros for the
+ * point at infinity.  The production launchers then run in the prover's order: flags zeroed over their padded words; launch_prep_rs; with a
+ * commitment launch_points_to_affine_be (D, bit 8) and launch_challenge_from_point; launch_fin_scalarmul, or launch_fin_scalarmul_few on the halves
+ * glv_split returns on the host; launch_points_to_affine_be (Pok, bit 16); launch_fin_combine.
+ *   batch: 1 .. 256 columns;  nproofs: 0 = the batch kernel, 1 .. 32 (<= batch) = the latency kernel on the first nproofs columns (tmp keeps the stride
+ *   batch; k_fin_combine runs over the whole batch either way, with tmp = infinity in the columns the latency kernel left alone);
+ *   n_wires (<= 4096): k_prep_rs writes its four rows behind that many rows of W;  fill: the byte out, W, mask_out, commit and cpts hold before the
+ *   first kernel;
+ *   x_pts: batch raw points, big-endian X | Y (64 B; B2: 128 B, X.A1 | X.A0 | Y.A1 | Y.A0), not read where x_inf[column] != 0;  x_lam: batch scales,
+ *   32 B big-endian (B2: 64 B, A1 | A0), non-zero and below p.  A, B1, K, Z in G1 and B2 in G2 are required;  C: all three NULL = the launcher gets
+ *   no sumC (the coefficient route);  D and Pok: both given = the commitment part runs, both NULL = it does not;
+ *   rs: batch x 64 bytes, r then s, eight little-endian words each, below r;  mask: NULL, or batch x 32 bytes little-endian, below r;
+ *   glv_in: NULL = the latency kernel gets glv_split's halves of rs, as a prover's call does.  Otherwise (nproofs != 0) 2 x nproofs records laid out
+ *   like the output glv, which the kernel gets INSTEAD: any magnitudes below 2^130 and any neg, the kernel's own contract, of which glv_split's
+ *   results are a part (its k1 is never negative and its magnitudes stay below 2^128).  k_prep_rs still reads rs.
+ * Outputs: out: batch x 256 bytes (Ar x | y, Bs x.a0 | x.a1 | y.a0 | y.a1, Krs x | y: canonical, eight little-endian words each);  flags: one byte per
+ * column (1 Ar, 2 Bs, 4 Krs, 8 D, 16 Pok at infinity);  tmp: 2 x batch x 64 bytes, tmp[0] = s A then tmp[1] = r B1 as canonical little-endian x | y, with
+ * tmp_inf[2 x batch] = 1 (and zeros) for the point at infinity;  cpts: D at column x 64, Pok at (batch + column) x 64, as stored;  commit, mask_out: one
+ * value per column as stored (eight little-endian Montgomery words);  W: the four rows r, s, -r s, 0 as stored, [row][column];  glv: 2 x nproofs
+ * records of 44 bytes (k1[5], k2[5], neg; [column][s, r]) as the kernel got them.
+ * 0 on success; -1 (one line on stdout): hooks disabled, batch / nproofs / n_wires / fill outside the above, a scalar or mask not below r, a scale
+ * that is zero or not below p, a missing buffer, glv_in without nproofs or with a magnitude of 2^130 or more or neg above 3, a point that is not raw, finite, on the curve and in the group. */
+struct gsc_debug_assemble_args {
+    uint32_t batch, nproofs, n_wires, fill;
+    const uint8_t *a_pts, *a_inf, *a_lam;
+    const uint8_t *b1_pts, *b1_inf, *b1_lam;
+    const uint8_t *k_pts, *k_inf, *k_lam;
+    const uint8_t *z_pts, *z_inf, *z_lam;
+    const uint8_t *b2_pts, *b2_inf, *b2_lam;
+    const uint8_t *c_pts, *c_inf, *c_lam;
+    const uint8_t *d_pts, *d_inf, *d_lam;
+    const uint8_t *pok_pts, *pok_inf, *pok_lam;
+    const uint8_t *rs; const uint8_t *mask; const uint8_t *glv_in;
+    uint8_t *out, *flags, *tmp, *tmp_inf, *cpts, *commit, *W, *mask_out, *glv;
+};
+extern int gsc_debug_assemble(const struct gsc_debug_assemble_args *args);
 /* TEST HOOK: the witness solver kernels alone, on a caller's constraint system: a device, but no key and no InitAlgorithm.  The description is an
  * R1CS file given field by field, exactly what the parser would have produced; the tables are built and uploaded by the functions InitAlgorithm
  * uses (csrc/solver_tables.hpp: build_solver_program, build_few_program, the count tables' device check, coeff / coeff_inv, build_small_program) and

@@ -21,6 +21,7 @@ arithmetic on the twist, the whole pairing by generic lines on E(Fp12); on the l
 documents.
 """
 import functools
+import hashlib
 import itertools
 import os
 import random
@@ -1547,3 +1548,308 @@ def msm_case_names():
         MSM_CASE_NAMES = list(msm_case_table(0))
         assert MSM_CASE_NAMES == list(msm_case_table(1))
     return MSM_CASE_NAMES
+
+
+# ---------------------------------------------------------------- proof assembly ----------------------------------------------------------------
+# gsc_debug_assemble (include/libprove.h).  Every input point is a known multiple of the generator, so every output is one: tmp[0] = (s a) G,
+# tmp[1] = (r b1) G, Krs = (k + z + s a + r b1 [+ c]) G, and the point at infinity exactly when that integer is 0 mod r.  A point is carried as its
+# discrete logarithm, None for the point at infinity.  The scalar multiplications are modelled twice: the batch kernel as the plain product, the
+# latency kernel lane by lane from the words glv_split hands it (glv_words is glv.hpp's arithmetic in Python integers;
+# test_assemble_model_host.py holds it against the C++).  `variant` names a WRONG kernel, for the sensitivity check of the table.
+GLV_LAMBDA = 0xb3c4d79d41a917585bfc41088d8daaa78b17ea66b99c90dd
+GLV_BETA = 0x59e26bcea0d48bacd4f263f1acdb5c4f5763473177fffffe
+GLV_A1 = 9931322734385697763
+GLV_B1_ABS = 147946756881789319000765030803803410728
+GLV_A2 = 147946756881789319010696353538189108491
+GLV_G1, GLV_G2 = (GLV_A1 << 384) // R, (GLV_B1_ABS << 384) // R
+FR_MONT = (1 << 256) % R
+ASSEMBLE_VARIANTS = ("rs_exchanged", "neg_exchanged", "straddle_ignored", "q25_ignored", "batch_from_bit_252", "beta_on_first_half", "c_ignored",
+                     "flag_shift_wrong", "flagged_part_zeroed")
+ASSEMBLE_SETS = ("a", "b1", "k", "z", "b2", "c", "d", "pok")
+STRADDLES = (6, 12, 19, 25)
+
+
+def expand_message_xmd48(msg, dst):
+    """RFC 9380 expand_message_xmd with SHA-256, 48 bytes out"""
+    dst = dst + bytes([len(dst)])
+    b0 = hashlib.sha256(bytes(64) + msg + (48).to_bytes(2, "big") + b"\0" + dst).digest()
+    b1 = hashlib.sha256(b0 + b"\x01" + dst).digest()
+    b2 = hashlib.sha256(bytes(x ^ y for x, y in zip(b0, b1)) + b"\x02" + dst).digest()
+    return (b1 + b2)[:48]
+
+
+def commitment_challenge(cpts64):
+    """k_challenge_from_point: hash_to_field of the commitment's 64 bytes, DST "bsb22-commitment" """
+    return int.from_bytes(expand_message_xmd48(cpts64, b"bsb22-commitment"), "big") % R
+
+
+def glv_halves(k):
+    """glv.hpp glv_split: (k1, k2) signed, k = k1 + k2 lambda mod r"""
+    c1, c2 = (k * GLV_G1) >> 384, (k * GLV_G2) >> 384
+    return k - c1 * GLV_A1 - c2 * GLV_A2, c1 * GLV_B1_ABS - c2 * GLV_A1
+
+
+def glv_words(k):
+    """the GlvSplit record of k: (five words of |k1|, five words of |k2|, neg)"""
+    k1, k2 = glv_halves(k)
+    assert abs(k1) < 1 << 130 and abs(k2) < 1 << 130
+    words = lambda v: tuple((abs(v) >> (32 * i)) & 0xFFFFFFFF for i in range(5))
+    return words(k1), words(k2), (1 if k1 < 0 else 0) | (2 if k2 < 0 else 0)
+
+
+def glv_record(k, rec=None):
+    k1, k2, neg = glv_words(k) if rec is None else rec
+    return struct.pack("<11I", *k1, *k2, neg)
+
+
+def glv_chosen(k1, k2, neg):
+    """a GlvSplit record from chosen magnitudes below 2^130, and the scalar it stands for"""
+    assert 0 <= k1 < 1 << 130 and 0 <= k2 < 1 << 130 and 0 <= neg <= 3
+    words = lambda v: tuple((v >> (32 * i)) & 0xFFFFFFFF for i in range(5))
+    return (words(k1), words(k2), neg), ((-k1 if neg & 1 else k1) + (-k2 if neg & 2 else k2) * GLV_LAMBDA) % R
+
+
+def glv_chunks(words, variant=None):
+    """the 26 five-bit chunks k_fin_scalarmul_few's lanes cut from five words"""
+    out = []
+    for q in range(26):
+        o = 5 * q
+        w, sh = o >> 5, o & 31
+        chunk = words[w] >> sh
+        if sh > 27 and variant != "straddle_ignored":
+            chunk |= (words[w + 1] << (32 - sh)) & 0xFFFFFFFF
+        out.append(0 if variant == "q25_ignored" and q == 25 else chunk & 31)
+    return out
+
+
+def latency_product(k, a, variant=None, rec=None):
+    """the discrete logarithm of what k_fin_scalarmul_few's wave leaves for the point a G and the halves of the scalar k (rec: a GlvSplit record
+    given instead of glv_split's): lanes 0..25 own the chunks of k1 on 2^(5q) P, lanes 32..57 those of k2 on phi(2^(5q) P) = lambda 2^(5q) P,
+    each half negated by its bit of neg; the other lanes hold chunk 0"""
+    k1w, k2w, neg = glv_words(k) if rec is None else rec
+    if variant == "neg_exchanged":
+        neg = (neg >> 1) | ((neg & 1) << 1)
+    total = 0
+    for second, words in ((False, k1w), (True, k2w)):
+        phi = second != (variant == "beta_on_first_half")
+        sign = -1 if (neg >> (1 if second else 0)) & 1 else 1
+        for q, chunk in enumerate(glv_chunks(words, variant)):
+            total += sign * chunk * (a << (5 * q)) * (GLV_LAMBDA if phi else 1)
+    return total % R
+
+
+def batch_product(k, a, variant=None):
+    """k_fin_scalarmul: double-and-add over bits 253..0"""
+    return (k & ((1 << (253 if variant == "batch_from_bit_252" else 254)) - 1)) * a % R
+
+
+@functools.lru_cache(maxsize=None)
+def _dlog_point(group, e):
+    return None if e is None else gen_mul(group, e)
+
+
+def _le_point(group, e):
+    return pack_point(1 if group == 0 else 2, _dlog_point(group, e))
+
+
+def _dsum(*es):
+    es = [e for e in es if e is not None]
+    return (sum(es) % R or None) if es else None
+
+
+class AssembleCase:
+    """Columns of one gsc_debug_assemble call.  A column: the discrete logarithms a, b1, k, z, c, d, pok (G1) and b2 (G2), None = infinity; r, s,
+    mask; name."""
+
+    def __init__(self, cols):
+        self.cols = list(cols)
+        self.batch = len(self.cols)
+
+    def rotated(self, by):
+        return AssembleCase(self.cols[by:] + self.cols[:by])
+
+    def scalars(self):
+        return [c[key] for c in self.cols for key in ("r", "s")]
+
+    def rs(self):
+        return b"".join(_le32(c["r"]) + _le32(c["s"]) for c in self.cols)
+
+    def mask(self):
+        return b"".join(_le32(c["mask"]) for c in self.cols)
+
+    def sets(self, has_c=True, has_commit=True, unit_scales=False):
+        """the point sets as the hook takes them: raw big-endian points (zeros at infinity), infinity bytes, big-endian scales"""
+        out = {}
+        for j, name in enumerate(ASSEMBLE_SETS):
+            if (name == "c" and not has_c) or (name in ("d", "pok") and not has_commit):
+                continue
+            group = 1 if name == "b2" else 0
+            sc = scales(group)
+            pts, inf, lam = [], bytearray(), []
+            for p, col in enumerate(self.cols):
+                e = col[name]
+                pts.append(bytes(128 if group else 64) if e is None else raw_point(group, _dlog_point(group, e)))
+                inf.append(1 if e is None else 0)
+                l = f_small(2 if group else 1, 1) if unit_scales else sc[(5 * p + 3 * j + 1) % len(sc)]
+                lam.append(b"".join(int(v).to_bytes(32, "big") for v in reversed(l)))
+            out[name] = (b"".join(pts), bytes(inf), b"".join(lam))
+        return out
+
+    def expected(self, nproofs=0, has_c=True, has_commit=True, fill=0xA5, variant=None, halves=None):
+        """every output of the hook, byte for byte.  nproofs != 0: the latency kernel wrote Ar, its flag and tmp of the first nproofs columns only;
+        k_fin_combine ran over the whole batch with tmp = infinity in the others.  halves: the records [column][s, r] the kernel got as glv_in"""
+        B = self.batch
+        out, flags = bytearray([fill]) * (256 * B), bytearray(B)
+        tmp, tmp_inf = bytearray(128 * B), bytearray(2 * B)
+        cpts, commit, W, mask_out = bytearray(128 * B), bytearray(32 * B), bytearray(128 * B), bytearray(32 * B)
+        product = functools.partial(latency_product if nproofs else batch_product, variant=variant)
+        assert halves is None or len(halves) == nproofs
+
+        def flag(p, bit):
+            q = (p & ~3) | ((p + 1) & 3) if variant == "flag_shift_wrong" else p
+            if q < B:
+                flags[q] |= bit
+
+        def part(p, off, size, group, e, bit):
+            if e is None:
+                flag(p, bit)
+                if variant == "flagged_part_zeroed":
+                    out[256 * p + off:256 * p + off + size] = bytes(size)
+            else:
+                out[256 * p + off:256 * p + off + size] = _le_point(group, e)
+
+        for p, col in enumerate(self.cols):
+            r, s = col["r"], col["s"]
+            for row, v in enumerate((r, s, -r * s % R, 0)):
+                W[32 * (row * B + p):32 * (row * B + p) + 32] = _le32(v * FR_MONT % R)
+            mask_out[32 * p:32 * p + 32] = _le32(col["mask"] * FR_MONT % R)
+            if variant == "rs_exchanged":
+                r, s = s, r
+            t = [None, None]
+            if not nproofs or p < nproofs:
+                part(p, 0, 64, 0, col["a"], 1)
+                rec = [{}, {}] if halves is None else [{"rec": h} for h in (halves[p][::-1] if variant == "rs_exchanged" else halves[p])]
+                t = [None if col["a"] is None else product(s, col["a"], **rec[0]) or None, None if col["b1"] is None else product(r, col["b1"], **rec[1]) or None]
+            for role in (0, 1):
+                tmp[64 * (role * B + p):64 * (role * B + p) + 64] = _le_point(0, t[role])
+                tmp_inf[role * B + p] = 1 if t[role] is None else 0
+            part(p, 64, 128, 1, col["b2"], 2)
+            part(p, 192, 64, 0, _dsum(col["k"], col["z"], t[0], t[1], col["c"] if has_c and variant != "c_ignored" else None), 4)
+            if has_commit:
+                for at, e, bit in ((p, col["d"], 8), (B + p, col["pok"], 16)):
+                    if e is None:
+                        flag(p, bit)
+                    else:
+                        cpts[64 * at:64 * at + 64] = raw_point(0, _dlog_point(0, e))
+                commit[32 * p:32 * p + 32] = _le32(commitment_challenge(bytes(cpts[64 * p:64 * p + 64])) * FR_MONT % R)
+        res = {"out": bytes(out), "flags": bytes(flags), "tmp": bytes(tmp), "tmp_inf": bytes(tmp_inf), "W": bytes(W), "mask_out": bytes(mask_out)}
+        if has_commit:
+            res.update(cpts=bytes(cpts), commit=bytes(commit))
+        if nproofs:
+            res["glv"] = b"".join(glv_record(c[key], halves and halves[p][i]) for p, c in enumerate(self.cols[:nproofs]) for i, key in enumerate(("s", "r")))
+        return res
+
+
+def glv_compose(k1, k2):
+    return (k1 + k2 * GLV_LAMBDA) % R
+
+
+def assemble_scalars():
+    """(the edge values, the values built from chosen halves)"""
+    rnd = random.Random(1201)
+    lam = GLV_LAMBDA
+    fixed = [0, 1, 2, R - 1, R - 2, HALF_R, HALF_R + 1, 1 << 253, (1 << 253) + 1, lam, lam - 1, lam + 1, R - lam, lam * lam % R, 1 << 127, (1 << 128) - 1, 1 << 128]
+    a, b = rnd.getrandbits(120) | 1 << 119, rnd.getrandbits(120) | 1 << 119
+    built = [glv_compose(a, b), glv_compose(a, -b), glv_compose(-a, b), glv_compose(-a, -b), glv_compose(0, b), glv_compose(a, 0),
+             glv_compose((1 << 125) - 1, (1 << 125) - 1), glv_compose((1 << 130) - 1, (1 << 130) - 1)]
+    for q in range(26):      # one non-zero chunk at position q of one half; the top position takes a value the split keeps below 2^127
+        c = (31, 1, 16, 21, 10)[q % 5] if q < 25 else 3
+        built += [glv_compose(c << (5 * q), 0), glv_compose(0, -(c << (5 * q)) if q & 1 else c << (5 * q))]
+    # the straddling positions with all five bits set, in both halves at once, under each pair of signs
+    for i, q in enumerate(STRADDLES):
+        v = (31 if q < 25 else 3) << (5 * q)
+        built.append(glv_compose(-v if i & 1 else v, -v if i & 2 else v))
+    return fixed, built
+
+
+def assemble_halves():
+    """32 columns of chosen halves [s, r] for glv_in: what k_fin_scalarmul_few's contract admits and glv_split never returns, too.  Every chunk 31
+    under each pair of signs; a zero half, also with its sign bit set; one non-zero chunk at each of the 26 positions of each half, the top one
+    (bits 125..129, the fifth word) included; random 130-bit magnitudes under each pair of signs."""
+    rnd = random.Random(1203)
+    top = (1 << 130) - 1
+    recs = [glv_chosen(top, top, neg) for neg in range(4)]
+    recs += [glv_chosen(0, rnd.getrandbits(130), 0), glv_chosen(rnd.getrandbits(130), 0, 0), glv_chosen(0, rnd.getrandbits(130), 3), glv_chosen(rnd.getrandbits(130), 0, 3)]
+    for q in range(26):
+        c = (31, 1, 16, 21, 10)[q % 5] if q < 25 else 31
+        recs += [glv_chosen(c << (5 * q), 0, q & 3), glv_chosen(0, c << (5 * q), (q + 1) & 3)]
+    recs += [glv_chosen(rnd.getrandbits(130) | 1 << 129, rnd.getrandbits(130) | 1 << 129, neg) for neg in range(4)]
+    assert len(recs) == 64
+    return [(recs[2 * p][0], recs[2 * p + 1][0]) for p in range(32)]
+
+
+def assemble_columns(n=64):
+    """The case table: one pattern per column.  Flagged columns sit at p = 4 g + g mod 4 (one per 32-bit flag word, at each byte position in turn), with
+    clean columns around them; n = 67 adds three columns in a partly used flag word, each flagged differently."""
+    assert n in (64, 67)
+    rnd = random.Random(1202)
+    fixed, built = assemble_scalars()
+    nz = lambda: rnd.randrange(1, R)
+    ordinary = [rnd.getrandbits(250), nz(), nz(), rnd.getrandbits(64), nz(), rnd.getrandbits(250), nz()] + [nz() for _ in range(6)]
+    pool = built + ordinary
+    assert len(fixed) == 17 and len(pool) == 17 + 60
+    r_list = fixed + [fixed[(5 * i + 3) % 17] for i in range(17, 34)] + pool[17:77:2]
+    s_list = pool[:17] + fixed + pool[18:77:2]
+    assert len(r_list) == 64 and len(s_list) == 64
+    cols = []
+    for p in range(64):
+        col = {key: nz() for key in ASSEMBLE_SETS}
+        col.update(r=r_list[p], s=s_list[p], mask=(0, 1, R - 1)[p] if p < 3 else nz(), name="generic")
+        cols.append(col)
+
+    def pattern(p, name, **kw):
+        cols[p].update(kw, name=name)
+        return cols[p]
+
+    sa_rb = lambda c: (c["s"] * c["a"] + c["r"] * c["b1"]) % R
+    # flagged in every mode
+    c = pattern(0, "Ar, Bs and Krs at infinity", a=None, b2=None, c=None); c["z"] = R - c["k"]; assert c["r"] == 0
+    pattern(5, "A at infinity", a=None)
+    pattern(10, "B2 at infinity", b2=None)
+    pattern(15, "all at infinity", **{key: None for key in ASSEMBLE_SETS})
+    # flagged in some modes
+    pattern(16, "D at infinity", d=None)
+    pattern(21, "Pok at infinity", pok=None)
+    c = pattern(26, "K + Z = -(sA + rB1)"); c["z"] = (-sa_rb(c) - c["k"]) % R
+    c = pattern(31, "K + Z + sA + rB1 = -C"); c["c"] = (-sa_rb(c) - c["k"] - c["z"]) % R
+    # clean
+    c = pattern(1, "K = Z"); c["z"] = c["k"]
+    c = pattern(2, "K = -Z"); c["z"] = R - c["k"]
+    c = pattern(3, "sA = rB1"); c["s"] = c["r"]; c["b1"] = c["a"]
+    c = pattern(4, "sA = -rB1"); c["b1"] = -c["s"] * c["a"] * pow(c["r"], -1, R) % R
+    c = pattern(6, "K + Z = sA + rB1"); c["z"] = (sa_rb(c) - c["k"]) % R
+    c = pattern(7, "K + Z + sA + rB1 = C"); c["c"] = (sa_rb(c) + c["k"] + c["z"]) % R
+    pattern(8, "C at infinity", c=None)
+    pattern(9, "B1 at infinity", b1=None)
+    pattern(11, "K at infinity", k=None)
+    pattern(12, "Z at infinity", z=None)
+    c = pattern(17, "s = 0 with A finite"); assert c["s"] == 0
+    c = pattern(30, "r = 0"); assert c["r"] == 0
+    for c in cols:
+        assert all(c[key] is None or 0 < c[key] < R for key in ASSEMBLE_SETS) and 0 <= c["r"] < R and 0 <= c["s"] < R
+    if n == 67:
+        for name, kw in (("A at infinity", {"a": None}), ("B2 at infinity", {"b2": None}), ("D and Krs at infinity", {"d": None, "k": None, "z": None, "c": None, "s": 0, "r": 0})):
+            col = {key: nz() for key in ASSEMBLE_SETS}
+            col.update(r=nz(), s=nz(), mask=nz(), name=name)
+            col.update(kw)
+            cols.append(col)
+    return cols
+
+
+_assemble_cache = {}
+
+
+def assemble_table(n=64):
+    if n not in _assemble_cache:
+        _assemble_cache[n] = AssembleCase(assemble_columns(n))
+    return _assemble_cache[n]

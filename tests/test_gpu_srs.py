@@ -3,10 +3,9 @@ Files come from two writers: tests/srsmodel.py (Python, from known tau, alpha, b
 of the check then cover 2N-2 / N-1 = 6 / 3, 126 / 63 and 254 / 127 points against the 64-thread blocks of k_phase2_rlc — one below a block, a
 partial second block, a partial fourth).  A wrong file differs from a right one in ONE element, replaced by another valid point of its group
 (or in one byte, for the decoding rules), so that the rule the case is about decides; the line the library prints names the rule."""
-import hashlib
-
 import pytest
 
+import devref
 import keyraw
 import srsmodel
 
@@ -23,11 +22,7 @@ def toxic(seed, label):
     """gsc_setup's seeded scalar (csrc/setup.cpp toxic): expand_message_xmd(SHA-256) of seed | label padded to 32 bytes, 48 bytes out,
     DST "gsc-test-setup", as a big-endian integer mod r"""
     msg = seed + label.encode().ljust(32, b"\0")
-    dst = b"gsc-test-setup" + bytes([14])
-    b0 = hashlib.sha256(bytes(64) + msg + (48).to_bytes(2, "big") + b"\0" + dst).digest()
-    b1 = hashlib.sha256(b0 + b"\x01" + dst).digest()
-    b2 = hashlib.sha256(bytes(x ^ y for x, y in zip(b0, b1)) + b"\x02" + dst).digest()
-    return int.from_bytes((b1 + b2)[:48], "big") % keyraw.R or 1
+    return int.from_bytes(devref.expand_message_xmd48(msg, b"gsc-test-setup"), "big") % keyraw.R or 1
 
 
 @pytest.fixture(scope="module")

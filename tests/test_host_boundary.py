@@ -47,6 +47,7 @@ def test_test_hooks_refuse_without_the_environment_opt_in(gsc):
         "assert L.gsc_debug_curve_ops(0, 0, bytes(64), bytes(1), bytes(64), 1, 1, C.create_string_buffer(64), C.create_string_buffer(1)) == -1\n"
         "assert L.gsc_debug_msm(C.byref(g.DebugMsmArgs())) == -1\n"
         "assert L.gsc_debug_solve(C.byref(g.DebugSolveArgs())) == -1\n"
+        "assert L.gsc_debug_assemble(C.byref(g.DebugAssembleArgs())) == -1\n"
         "s, keep = g._slice(b'{}'); assert L.gsc_debug_prove(s) == -1\n"
         "L.gsc_debug_compute_h.restype = C.c_longlong; assert L.gsc_debug_compute_h(0, None, 0, None, 0) == -1\n"
         "L.gsc_debug_compute_d.restype = C.c_longlong; assert L.gsc_debug_compute_d(0, None, 0, None, 0) == -1\n"
@@ -55,7 +56,7 @@ def test_test_hooks_refuse_without_the_environment_opt_in(gsc):
         "try:\n    g.set_deterministic_randomness(1, 1)\nexcept RuntimeError: print('refused')\n" % ROOT)
     env = {k: v for k, v in os.environ.items() if k != "GSC_ENABLE_TEST_HOOKS"}
     out = subprocess.check_output([sys.executable, "-c", code], env=env).decode()
-    assert "refused\n" in out and out.count("test hooks are disabled") == 12      # (C stdio and Python flush in their own order)
+    assert "refused\n" in out and out.count("test hooks are disabled") == 13      # (C stdio and Python flush in their own order)
     assert gsc.lib().gsc_set_deterministic_randomness(None, None, None) == 0      # this process opted in (conftest.py)
 
 
