@@ -3,7 +3,7 @@
 // conventions of engine_prove.hip (stage_upload, stage_witness, stage_early_sums / stage_msms, stage_assembly): flags zeroed over their padded
 // words; launch_prep_rs; launch_points_to_affine_be (bit 8) and launch_challenge_from_point for a commitment; launch_fin_scalarmul, or
 // launch_fin_scalarmul_few on glv_split's halves (or on the caller's, to reach the rest of the kernel's contract); launch_points_to_affine_be (bit 16); launch_fin_combine.  No production kernel is changed or
-// copied for it: the two kernels here build an XYZZ sum from its affine form and turn tmp back into affine coordinates.
+// copied for it: the two kernels here build an XYZZ sum from its affine form and turn tmp back into affine coordinates (debug_ops.hpp's sum_out).
 // tests/test_gpu_assemble.py is the caller.
 #include "assemble_debug.hpp"
 #include "engine_impl.hpp"
@@ -27,18 +27,8 @@ __global__ __launch_bounds__(64) void k_debug_assemble_in(const fe* pts, const u
 // out[i] = sums[i] as canonical little-endian x, y; inf[i] = 1 and zeros for the point at infinity
 __global__ __launch_bounds__(64) void k_debug_assemble_out(const fe* sums, size_t n, fe* out, uint8_t* inf) {
     const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const Xyzz9<Fp29f> v = G1x::load_xyzz(sums + 4 * i);
-    if (v.inf) { inf[i] = 1; store_fe(out + 2 * i, fe{}); store_fe(out + 2 * i + 1, fe{}); return; }
-    inf[i] = 0;
-    const Aff9<Fp29f> a = G1x::to_aff(v);
-    store_fe(out + 2 * i, Fp29::pack(Fp29::from_mont(a.x))); store_fe(out + 2 * i + 1, Fp29::pack(Fp29::from_mont(a.y)));
+    if (i < n) dbg::sum_out<Fp29f>(sums, i, out, inf);
 }
-
-const uint8_t kFrModBE[32] = {0x30, 0x64, 0x4e, 0x72, 0xe1, 0x31, 0xa0, 0x29, 0xb8, 0x50, 0x45, 0xb6, 0x81, 0x81, 0x58, 0x5d,
-                              0x28, 0x33, 0xe8, 0x48, 0x79, 0xb9, 0x70, 0x91, 0x43, 0xe1, 0xf5, 0x93, 0xf0, 0x00, 0x00, 0x01};
-const uint8_t kFpModBE[32] = {0x30, 0x64, 0x4e, 0x72, 0xe1, 0x31, 0xa0, 0x29, 0xb8, 0x50, 0x45, 0xb6, 0x81, 0x81, 0x58, 0x5d,
-                              0x97, 0x81, 0x6a, 0x91, 0x68, 0x71, 0xca, 0x8d, 0x3c, 0x20, 0x8c, 0x16, 0xd8, 0x7c, 0xfd, 0x47};
 
 [[noreturn]] void refuse(const std::string& why) { throw std::runtime_error("gsc_debug_assemble: " + why); }
 
@@ -196,9 +186,7 @@ void debug_assemble(int device, const gsc_debug_assemble_args& a) {
     const PointSet sets[8] = {{"A", a.a_pts, a.a_inf, a.a_lam, 1}, {"B1", a.b1_pts, a.b1_inf, a.b1_lam, 1}, {"K", a.k_pts, a.k_inf, a.k_lam, 1}, {"Z", a.z_pts, a.z_inf, a.z_lam, 1},
                               {"B2", a.b2_pts, a.b2_inf, a.b2_lam, 2}, {"C", a.c_pts, a.c_inf, a.c_lam, 1}, {"D", a.d_pts, a.d_inf, a.d_lam, 1}, {"Pok", a.pok_pts, a.pok_inf, a.pok_lam, 1}};
     check(a, sets);      // every refusal the host can decide comes before a device is asked for
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) throw std::runtime_error("no HIP device available");
-    HIP_CHECK(hipSetDevice(device));
+    use_device(device);
     run(a, sets);
 }
 

@@ -7,6 +7,7 @@
 #include "../../include/libprove.h"
 #include "engine.hpp"
 #include "dispatch.hpp"
+#include "formats.hpp"
 #include "registry.hpp"
 #include "glv.hpp"
 #include "host_ciphers.hpp"
@@ -57,10 +58,6 @@ bool hooks_refused(const char* what) {
     printf("%s refused: test hooks are disabled (start the process with GSC_ENABLE_TEST_HOOKS=1)\n", what);
     return true;
 }
-
-// Fr modulus, big-endian
-const uint8_t kFrModBE[32] = {0x30, 0x64, 0x4e, 0x72, 0xe1, 0x31, 0xa0, 0x29, 0xb8, 0x50, 0x45, 0xb6, 0x81, 0x81, 0x58, 0x5d,
-                              0x28, 0x33, 0xe8, 0x48, 0x79, 0xb9, 0x70, 0x91, 0x43, 0xe1, 0xf5, 0x93, 0xf0, 0x00, 0x00, 0x01};
 
 // OS CSPRNG bytes, fetched 16 KiB at a time per thread: a batch of 8192 proofs draws ~25 000 scalars, and one getrandom() system
 // call per scalar was a measurable part of the step (the GPU idles meanwhile).  The buffer is wiped as it is consumed.

@@ -1,6 +1,7 @@
 // TEST HOOKS: one element of gsc_debug_limb_ops / gsc_debug_curve_ops (include/libprove.h).  The hook kernels of k_init.hip call these
 // per thread; tests/native builds the same functions for the host, where the products of bn254_fp29.hpp are plain C, so that the case
-// tables and the references of the tests are proven on a CPU before the device code is judged by them.  No production kernel includes this.
+// tables and the references of the tests are proven on a CPU before the device code is judged by them; and the element function that returns the sums of the
+// hooks gsc_debug_msm / gsc_debug_assemble (device builds only).  No production kernel includes this.
 #pragma once
 #include "bn254_fp29.hpp"
 
@@ -94,6 +95,25 @@ DEVFN uint32_t curve_op(int op, size_t k, const fe* pts, const uint8_t* inf, con
     CurveIO<F>::out(out, a.x); CurveIO<F>::out(out + W, a.y);
     return flags;
 }
+
+#ifdef __HIPCC__
+// The results of the hooks gsc_debug_msm and gsc_debug_assemble, one element: out[i] = the XYZZ sum sums[i] as canonical little-endian coordinates
+// (G1 x, y; G2 x.a0, x.a1, y.a0, y.a1); inf[i] = 1 and zeros for the point at infinity
+template <class F>
+DEVFN void sum_out(const fe* sums, size_t i, fe* out, uint8_t* inf) {
+    using C = Curve9<F>;
+    const Xyzz9<F> v = C::load_xyzz(sums + i * (4 * F::WORDS));
+    fe* o = out + i * (2 * F::WORDS);
+    if (v.inf) { inf[i] = 1; for (int q = 0; q < 2 * F::WORDS; q++) store_fe(o + q, fe{}); return; }
+    inf[i] = 0;
+    const Aff9<F> a = C::to_aff(v);
+    if constexpr (F::WORDS == 1) { store_fe(o, Fp29::pack(Fp29::from_mont(a.x))); store_fe(o + 1, Fp29::pack(Fp29::from_mont(a.y))); }
+    else {
+        store_fe(o, Fp29::pack(Fp29::from_mont(a.x.a0))); store_fe(o + 1, Fp29::pack(Fp29::from_mont(a.x.a1)));
+        store_fe(o + 2, Fp29::pack(Fp29::from_mont(a.y.a0))); store_fe(o + 3, Fp29::pack(Fp29::from_mont(a.y.a1)));
+    }
+}
+#endif
 
 }  // namespace dbg
 }  // namespace bn254

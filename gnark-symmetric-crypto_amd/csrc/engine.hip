@@ -73,9 +73,7 @@ EngineConfig config_from_env() {
 }
 
 void debug_field_ops(int device, int field, int op, const uint8_t* a, const uint8_t* b, uint8_t* out, size_t n, int chain) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) throw std::runtime_error("no HIP device available");
-    HIP_CHECK(hipSetDevice(device));
+    use_device(device);
     DevBuf<fe> da(n), db(n), dout(n);
     HIP_CHECK(hipMemcpy(da.p, a, 32 * n, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(db.p, b, 32 * n, hipMemcpyHostToDevice));
     if (!launch_field_ops(field, op, da.p, db.p, dout.p, n, chain, nullptr)) throw std::runtime_error("gsc_debug_field_ops: field " + std::to_string(field) + " has no op " + std::to_string(op));
@@ -88,9 +86,7 @@ void debug_limb_ops(int device, int field, int op, const int32_t* a, const int32
     const int operands = op == 0 ? 2 : op == 2 ? 4 : 1;      // mul: a, b; fmms: a, b, c, d; sqr / norm / freeze / freeze_near: a
     const int32_t* src[4] = {a, b, c, d};
     for (int j = 0; j < operands; j++) if (!src[j]) throw std::runtime_error("gsc_debug_limb_ops: operand missing");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) throw std::runtime_error("no HIP device available");
-    HIP_CHECK(hipSetDevice(device));
+    use_device(device);
     DevBuf<int32_t> din[4], dout(9 * n);
     for (int j = 0; j < 4; j++) {      // an operand the op does not read is a copy of a
         din[j].alloc(9 * n);
@@ -109,9 +105,7 @@ void debug_curve_ops(int device, int group, int op, const uint8_t* pts, const ui
     // an AFFINE operand cannot be the point at infinity: every point of madd but the first, every point of the partial sums
     if (op == 1 || op == 2 || op == 5)
         for (size_t i = 0; i < n; i++) for (size_t j = op == 5 ? 0 : 1; j < k; j++) if (inf[k * i + j]) throw std::runtime_error("gsc_debug_curve_ops: infinity as an affine operand");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) throw std::runtime_error("no HIP device available");
-    HIP_CHECK(hipSetDevice(device));
+    use_device(device);
     const size_t w = group == 0 ? 1 : 2;      // 32-byte values per coordinate
     DevBuf<fe> dpts(2 * w * k * n), dlam(2 * w * n), dout(2 * w * n);
     DevBuf<uint8_t> dinf(k * n), dflags(n);
@@ -132,9 +126,7 @@ void debug_decode_points(int device, int group, const uint8_t* bytes, size_t len
     const size_t used = walk_points(bytes, len, n, cb, pts.x, pts.y, "points");      // the walk parse_pk makes over every slice
     if (used != len) throw std::runtime_error("points: trailing bytes");
     if (!n) return;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) throw std::runtime_error("no HIP device available");
-    HIP_CHECK(hipSetDevice(device));
+    use_device(device);
     DevBuf<fe> dpts(2 * w * n), dcanon(2 * w * n);
     const std::vector<uint8_t> st = group == 0 ? decode_g1_points(pts, reinterpret_cast<G1Aff*>(dpts.p), nullptr) : decode_g2_points(pts, reinterpret_cast<G2Aff*>(dpts.p), nullptr);
     launch_fp_from_mont(dpts.p, dcanon.p, 2 * w * n, nullptr);
@@ -159,9 +151,7 @@ bool debug_tower_ops(int device, int path, int op, const int32_t* in, size_t n, 
     if (!tower_ops_words(path, op, &iw, &ow)) return false;
     if (n > (1u << 16)) throw std::runtime_error("gsc_debug_tower_ops: too many elements");
     if (!n) return true;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) throw std::runtime_error("no HIP device available");
-    HIP_CHECK(hipSetDevice(device));
+    use_device(device);
     DevBuf<int32_t> din((size_t)iw * n), dout((size_t)(ow ? ow : 1) * n);
     DevBuf<uint8_t> dflags(n);
     HIP_CHECK(hipMemcpy(din.p, in, 4 * (size_t)iw * n, hipMemcpyHostToDevice));
@@ -183,9 +173,7 @@ void debug_quot_fold_dft(int device, int L, uint32_t m, const uint32_t* perm, co
         std::vector<uint8_t> seen(n, 0);
         for (size_t i = 0; i < n; i++) { pm[i] = perm ? perm[i] : (uint32_t)i; if (pm[i] >= n || seen[pm[i]]++) throw std::runtime_error("gsc_debug_quot_fold_dft: perm is not a permutation of 0 .. n - 1"); }
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) throw std::runtime_error("no HIP device available");
-    HIP_CHECK(hipSetDevice(device));
+    use_device(device);
     DevBuf<uint32_t> d_perm(n);
     DevBuf<uint8_t> d_be((m + n) * 64), d_inf(m + n), d_stU(m), d_stV(n), d_stU2(m), d_stV2(m - 1), d_out((2 * (size_t)m - 1) * 64), d_flags(2 * (size_t)m - 1), scratch(quot_fold_dft_scratch_bytes(L, m));
     DevBuf<G1Aff> d_U(m), d_V(n), d_U2(m), d_V2(m - 1);
@@ -204,8 +192,7 @@ void debug_quot_fold_dft(int device, int L, uint32_t m, const uint32_t* perm, co
 }
 
 float debug_wipe(int device, uint64_t bytes, int fill, const uint64_t* desc, size_t ndesc, const uint8_t* cls, size_t ncls, uint8_t* out, const uint64_t* win, size_t nwin, uint64_t* counts) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) throw std::runtime_error("no HIP device available");
+    use_device(device);
     if (!bytes || bytes > ((uint64_t)1 << 36)) throw std::runtime_error("gsc_debug_wipe: buffer size out of range");
     // every descriptor inside the buffer (no overflow: each factor is bounded first), image descriptors only with a class array
     auto checked = [&](const uint64_t* d, uint8_t* base, const uint8_t* d_cls) {
@@ -219,7 +206,6 @@ float debug_wipe(int device, uint64_t bytes, int fill, const uint64_t* desc, siz
         if (d[4] && (!d_cls || !ncls)) throw std::runtime_error("gsc_debug_wipe: plane image without row classes");
         return WipeDesc{base + off, rows, pitch, width, d[4] ? d_cls : nullptr, d[4] ? (uint64_t)ncls : 0};
     };
-    HIP_CHECK(hipSetDevice(device));
     DevBuf<uint8_t> buf(bytes), d_cls(ncls ? ncls : 1); DevBuf<unsigned long long> d_cnt(nwin ? nwin : 1);
     if (ncls) HIP_CHECK(hipMemcpy(d_cls.p, cls, ncls, hipMemcpyHostToDevice));
     std::vector<WipeDesc> ds, ws;

@@ -9,6 +9,7 @@
 #include "kernels.hpp"
 #include "wit_small.hpp"
 #include "solver_tables.hpp"
+#include "msm_set.hpp"
 #include "wipe_plan.hpp"
 #include "prove_check.hpp"
 #include <atomic>
@@ -47,48 +48,7 @@ struct KeyPoints {
 std::vector<uint8_t> decode_g1_points(const KeyPoints& pts, G1Aff* out, hipStream_t stream);
 std::vector<uint8_t> decode_g2_points(const KeyPoints& pts, G2Aff* out, hipStream_t stream);
 
-// Slice partials -> one sum per column: reduction levels over the ping-pong buffers pa (the partials) and pb until one group is left, which goes to
-// `out`.  levels (optional, the test hook gsc_debug_msm): the slices entering every level and whether it took the by-proof kernel.
-template <class XyzzT>
-inline void msm_reduce_slices(hipStream_t st, XyzzT* pa, XyzzT* pb, size_t nslices, size_t cols, XyzzT* out, std::vector<std::pair<size_t, bool>>* levels = nullptr) {
-    XyzzT* src = pa; XyzzT* alt = pb; size_t ns = nslices;
-    for (;;) {
-        const size_t groups = msm_reduce_groups(ns, cols);
-        XyzzT* dst = groups == 1 ? out : alt;
-        if (levels) levels->emplace_back(ns, msm_reduce_by_proof(ns, cols));
-        launch_msm_reduce(src, ns, cols, dst, st);
-        if (groups == 1) break;
-        XyzzT* t = src; src = dst; alt = t; ns = groups;
-    }
-}
-// the same for the first `npr` columns of every row of `stride` (latency path: nobody reads the padding proofs' columns)
-template <class XyzzT>
-inline void msm_reduce_slices_few(hipStream_t st, XyzzT* pa, XyzzT* pb, size_t nslices, size_t cols, size_t stride, size_t npr, XyzzT* out, std::vector<std::pair<size_t, bool>>* levels = nullptr) {
-    XyzzT* src = pa; XyzzT* alt = pb; size_t ns = nslices;
-    for (;;) {
-        const size_t groups = (ns + 63) / 64;
-        XyzzT* dst = groups == 1 ? out : alt;
-        if (levels) levels->emplace_back(ns, false);
-        launch_msm_reduce_few(src, ns, cols, stride, npr, dst, st);
-        if (groups == 1) break;
-        XyzzT* t = src; src = dst; alt = t; ns = groups;
-    }
-}
-
-template <class AffT>
-struct MsmSet {                     // one fixed-base MSM of the proving key (kernels.hpp, "multi-scalar multiplication")
-    size_t nbases = 0;              // bases of the key in this set
-    // windowed part (uniform rows of 2^(c-1) multiples): every base of Z; the wide wires of a wire set when there are many
-    DevBuf<AffT> wtable; DevBuf<uint32_t> wrows; size_t nwide = 0; int c = 0, nwin = 0;
-    // the folded Z set (init_key): the last quotient kernel lays the digits out for this many bases, of which the kernel walks the first nwide (0: nwide)
-    size_t digit_bases = 0;
-    // flat part: [bit groups of eight][narrow wires, own row lengths][window octets of a few wide wires (cv-bit digits)]
-    DevBuf<AffT> ftable; DevBuf<uint64_t> rowoff; DevBuf<uint32_t> rowlen; DevBuf<uint32_t> frows; DevBuf<int32_t> octwin;
-    size_t nflat = 0, nbit = 0, nexpanded = 0; int cv = 0; DevBuf<AffT> sub; DevBuf<uint8_t> group_ok;
-    // latency path: the windowed part once more as a flat set of (base, window) rows of 8-bit digits (no Horner pass behind it)
-    std::unique_ptr<MsmSet<AffT>> few_wide;
-    bool latency_flat() const { return !nwide || few_wide; }       // calls with a handful of statements need no windowed kernel for this set
-};
+// (one MSM set of the key, its tables and the launch sequence of a call over it: MsmSet, msm_build_tables, msm_run — msm_set.hpp)
 
 // The engines' streams come from a process-wide pool and go back to it, drained, when an engine goes: the HIP runtime binds a stream to one of
 // its hardware queues when the stream is created, and a queue keeps the scratch memory its kernels needed for the life of the process.  An
@@ -245,10 +205,6 @@ class AlgorithmImpl : public SolverTables {
     static constexpr size_t EXPAND_MAX = 64;      // up to this many wide wires of a set are laid out as window octets of its flat part
     static constexpr int EXPAND_C = 15, NARROW_MAX_BITS = 14;
 
-    // rows of multiples for `n` bases (row i: len[i] entries at off[i]); work is cut into segments of at most 256 multiples
-    template <class AffT, class XyzzT>
-    void build_rows(const AffT* bases, size_t n, const std::vector<uint64_t>& off, const std::vector<uint32_t>& len, AffT* table);
-
     // Lays out one MSM set and builds its tables.  uniform = true (Z): every base gets a full row, windowed kernel.  Otherwise the
     // bases are sorted by what calibrate() saw on their wires: values in {-1, 0, 1} -> bit groups of eight; values of up to
     // NARROW_MAX_BITS bits (with the margin) -> flat rows of that length; the rest (r, s, the lookup argument's products and inverses)
@@ -258,15 +214,11 @@ class AlgorithmImpl : public SolverTables {
     // row n_wires + 3 of W); latency_layout: also build the (base, window) rows of the windowed part for calls with a handful of statements
     void build_set(MsmSet<AffT>& set, const KeyPoints& raw, size_t point_bytes, const std::vector<uint32_t>& rows, int c, const char* what, Decomp decomp, bool uniform, int expand_cv = 0,
                    const std::vector<uint8_t>* classes = nullptr, uint32_t zero_row = 0xFFFFFFFFu, bool latency_layout = true);
-    // group tables are built in chunks so that the projective scratch stays below ~2 GiB
-    template <class AffT, class XyzzT>
-    void build_subset(const AffT* b, size_t ng, AffT* t, uint8_t* ok);
-
     void init_key(const R1csFile& cs, const PkFile& key);
 
     void alloc_lane(Lane& ln, size_t B);
 
-    // (slices of an MSM launch: msm_slices, msm_layout.hpp)
+    // (slices and scratch of an MSM call: msm_geometry, msm_layout.hpp)
     RouteFacts route_facts() const { return RouteFacts{small.ok, has_commitment, quotient_eval, fuse_z_digits, mZfew.nflat != 0, mA.latency_flat(), mB1.latency_flat(), mB2.latency_flat()}; }
     // one chunk of statements on its way through the stages of prove_chunk: what it is, the route it takes (decided once, read by every stage)
     struct Chunk {
@@ -277,8 +229,7 @@ class AlgorithmImpl : public SolverTables {
         std::vector<uint8_t> verdict = {};                   // with check: one byte per statement, 0 = not to be released
         bool check_fell_back = false;
     };
-    size_t WIN_SLICE = 256;      // bases per slice of the windowed kernel at full batches (measured 64 .. 512: kernel time within 1 %)
-    struct MsmCtx { hipStream_t stream; uint4* digits; uint8_t* gok; const int8_t* plane = nullptr; size_t plane_rows = 0, plane_stride = 0; };      // plane: the scalars' byte plane (small-integer witness path)
+    MsmLaunchOpts msm_opts;      // win_slice: cfg.win_slice (GSC_WIN_SLICE, test hooks); the rest the engine's own choice
     // the byte plane that stands for the scalar matrix `scalars` in the chunk this lane is proving (none: the matrix holds every row)
     MsmCtx with_plane(MsmCtx c, const Lane& ln, const fe* scalars) const {
         if (!ln.small_active) return c;
@@ -286,19 +237,9 @@ class AlgorithmImpl : public SolverTables {
         else if (scalars == ln.d_C.p) { c.plane = ln.d_C8.p; c.plane_rows = n_constraints; c.plane_stride = n_constraints; }
         return c;
     }
-    template <class XyzzT>
-    void reduce_slices(hipStream_t st, XyzzT* pa, XyzzT* pb, size_t nslices, size_t cols, XyzzT* out);
-    // the same for the first `npr` columns of every row of `stride` (latency path: nobody reads the padding proofs' columns)
-    template <class XyzzT>
-    void reduce_slices_few(hipStream_t st, XyzzT* pa, XyzzT* pb, size_t nslices, size_t cols, size_t stride, size_t npr, XyzzT* out);
-    // scalars: the wire matrix W (Montgomery; wire sets) or h (canonical; Z)
-    // The Horner pass of the windowed part is NOT launched here: it is queued in `pending` and flushed together with those of other
-    // sets (flush_horner), because each is a serial chain of 254 doublings whose duration does not depend on the batch.
-    // latency: the chunk takes the latency kernels (ChunkRoute::latency), which work on its n_real statements' columns only
-    template <class AffT, class XyzzT>
-    void run_msm(Lane& ln, const MsmCtx& ctx, const MsmSet<AffT>& set, const fe* scalars, bool wires, size_t B, size_t n_real, bool latency, XyzzT* pa, XyzzT* pb, XyzzT* sj, XyzzT* flat, XyzzT* sum, bool timed, bool digits_ready,
-                 MsmHornerJobs& pending);
     int set_index(const MsmSet<G1Aff>& set) const { const MsmSet<G1Aff>* all[Lane::NSETS] = {&mA, &mB1, &mK, &mZ, &mPed, &mPedSigma, &mZfew, &mC}; for (int k = 0; k < Lane::NSETS; k++) if (all[k] == &set) return k; return 0; }
+    // The lane adapters of msm_run (msm_set.hpp): which stream, which digit buffer, which scratch, the byte plane.  scalars: the wire matrix W
+    // (Montgomery; wire sets) or h (canonical; Z).  The Horner pass is queued in the lane's pending jobs (flush_horner).
     // side = true: on the lane's side stream with scratch buffers of its own (flat sets of calls with a handful of statements only)
     // digits_ready: the windowed part's digits are already in the lane's digit buffer (fuse_z_digits): no recoding pass
     void run_msm_g1(Lane& ln, const Chunk& ck, const MsmSet<G1Aff>& set, const fe* scalars, int mont, G1Xyzz* sum, bool timed = false, bool side = false, bool digits_ready = false);

@@ -1,5 +1,5 @@
 // Per-batch half of the engine: witness -> quotient -> MSMs -> assembly for one chunk of statements on one lane (prove_chunk and its
-// stage_* functions; which kernels a chunk takes is decided once, by chunk_route.hpp), the MSM orchestration (run_msm) and proof
+// stage_* functions; which kernels a chunk takes is decided once, by chunk_route.hpp), the lane adapters of the MSM calls (msm_run, msm_set.hpp) and proof
 // serialisation.  See engine_impl.hpp; reference: groth16.Prove + proof.WriteTo behind
 // libraries/prover/impl/provers.go:148-157, :216-226.
 #include "engine_impl.hpp"
@@ -23,81 +23,31 @@ bool be_greater(const uint8_t* a, const uint8_t* b) { int c = memcmp(a, b, 32); 
 bool be_is_zero(const uint8_t* a) { for (int i = 0; i < 32; i++) if (a[i]) return false; return true; }
 }  // namespace
 
-template <class XyzzT>
-void AlgorithmImpl::reduce_slices(hipStream_t st, XyzzT* pa, XyzzT* pb, size_t nslices, size_t cols, XyzzT* out) { msm_reduce_slices(st, pa, pb, nslices, cols, out); }
-
-template <class XyzzT>
-void AlgorithmImpl::reduce_slices_few(hipStream_t st, XyzzT* pa, XyzzT* pb, size_t nslices, size_t cols, size_t stride, size_t npr, XyzzT* out) { msm_reduce_slices_few(st, pa, pb, nslices, cols, stride, npr, out); }
-
-template <class AffT, class XyzzT>
-void AlgorithmImpl::run_msm(Lane& ln, const MsmCtx& ctx, const MsmSet<AffT>& set, const fe* scalars, bool wires, size_t B, size_t n_real, bool latency, XyzzT* pa, XyzzT* pb, XyzzT* sj, XyzzT* flat, XyzzT* sum, bool timed, bool digits_ready,
-             MsmHornerJobs& pending) {
-    size_t per = 0;
-    // the flat rows of `m` for a call with a handful of statements: lanes = octets of bases, partial sums to `out`; returns their slices
-    auto flat_few = [&](const MsmSet<AffT>& m, XyzzT* out, bool stamp) -> size_t {
-        if (!m.nflat) return 0;
-        const size_t nslices = msm_flat_few_slices(m.nflat);
-        MsmFlatRecodeArgs ra{scalars, m.frows.p, m.octwin.p, m.nflat, B, m.cv, ctx.digits, m.nbit, m.group_ok.p, ctx.gok, wires ? 1 : 0, ctx.plane, ctx.plane_rows, ctx.plane_stride};
-        launch_msm_recode_flat_few(ra, n_real, ctx.stream);
-        MsmFlatArgs a{m.ftable.p, m.rowoff.p, m.rowlen.p, m.nflat, ctx.digits, B, nslices, 512, out, m.nbit, m.sub.p, ctx.gok, scalars, m.frows.p};
-        if (stamp) HIP_CHECK(hipEventRecord(ln.ev[5], ctx.stream));
-        launch_msm_flat_few<AffT>(a, n_real, ctx.stream);
-        if (stamp) HIP_CHECK(hipEventRecord(ln.ev[6], ctx.stream));
-        return nslices;
-    };
-    if (latency && set.latency_flat()) {
-        // every part of the set as flat rows: the partial sums of both parts side by side, one reduction, no Horner pass
-        size_t ns = flat_few(set, pa, timed);
-        if (set.few_wide) ns += flat_few(*set.few_wide, pa + ns * B, false);
-        if (ns) reduce_slices_few(ctx.stream, pa, pb, ns, B, B, n_real, sum);
-        else HIP_CHECK(hipMemsetAsync(sum, 0, B * sizeof(XyzzT), ctx.stream));
-        return;
-    }
-    if (set.nflat && latency) {       // (a set whose windowed part has no latency layout: GSC_FEW_WIDE=0)
-        const size_t nslices = flat_few(set, pa, timed);
-        reduce_slices_few(ctx.stream, pa, pb, nslices, B, B, n_real, set.nwide ? flat : sum);
-    } else if (set.nflat) {
-        MsmFlatRecodeArgs ra{scalars, set.frows.p, set.octwin.p, set.nflat, B, set.cv, ctx.digits, set.nbit, set.group_ok.p, ctx.gok, wires ? 1 : 0, ctx.plane, ctx.plane_rows, ctx.plane_stride};
-        const size_t nslices = msm_slices(set.nflat, 1, 256, B, per);
-        launch_msm_recode_flat(ra, ctx.stream);
-        MsmFlatArgs a{set.ftable.p, set.rowoff.p, set.rowlen.p, set.nflat, ctx.digits, B, nslices, per, pa, set.nbit, set.sub.p, ctx.gok, scalars, set.frows.p};
-        launch_msm_flat<AffT>(a, ctx.stream);
-        reduce_slices(ctx.stream, pa, pb, nslices, B, set.nwide ? flat : sum);
-    }
-    if (set.nwide) {
-        size_t nslices = msm_slices(set.nwide, (size_t)set.nwin, WIN_SLICE, B, per);
-        if (latency) msm_slices_latency(set.nwide, nslices, per);      // a single Prove call (lanes = bases): slices of 512 bases
-        const size_t Bw = B * (size_t)set.nwin;
-        MsmRecodeArgs ra{scalars, set.wrows.p, wires ? 1 : 0, set.nwide, B, set.c, set.nwin, ctx.digits};
-        if (!digits_ready) launch_msm_recode(ra, ctx.stream);
-        MsmWinArgs a{set.wtable.p, set.c, set.nwin, set.nwide, ctx.digits, B, nslices, per, pa, timed && !latency ? ln.d_clk.p : nullptr,
-                     timed && cfg.z_exp_entry_bits > 0 && cfg.z_exp_entry_bits < 31 ? (1u << cfg.z_exp_entry_bits) - 1 : 0u,
-                     digits_ready ? set.digit_bases : 0};      // (digits recoded here are laid out for the bases walked)
-        if (timed) HIP_CHECK(hipEventRecord(ln.ev[5], ctx.stream));
-        if (latency) launch_msm_win_few<AffT>(a, n_real, ctx.stream);
-        else launch_msm_win<AffT>(a, ctx.stream);
-        if (timed) HIP_CHECK(hipEventRecord(ln.ev[6], ctx.stream));
-        if (latency) reduce_slices_few(ctx.stream, pa, pb, nslices, Bw, B, n_real, sj);
-        else reduce_slices(ctx.stream, pa, pb, nslices, Bw, sj);      // slices -> one sum per (window, proof)
-        if (pending.n >= MSM_HORNER_JOBS) throw std::runtime_error("internal: too many pending Horner passes");
-        pending.job[pending.n++] = MsmHornerJob{sj, set.nflat ? flat : (XyzzT*)nullptr, sum, set.nwin, set.c};
-    }
-    if (!set.nflat && !set.nwide) HIP_CHECK(hipMemsetAsync(sum, 0, B * sizeof(XyzzT), ctx.stream));      // empty set: the point at infinity
-}
-
 void AlgorithmImpl::run_msm_g1(Lane& ln, const Chunk& ck, const MsmSet<G1Aff>& set, const fe* scalars, int mont, G1Xyzz* sum, bool timed, bool side, bool digits_ready) {
     const int k = set_index(set);
+    MsmRun<G1Xyzz> r{MsmCtx{ln.stream, ln.d_digits_w.p && &set != &mZ ? ln.d_digits_w.p : ln.d_digits.p, ln.d_gok.p}, scalars, mont != 0, ck.B, ck.n, ck.rt.latency,
+                     ln.d_part1a.p, ln.d_part1b.p, ln.d_sj1[k].p, ln.d_flat1[k].p, sum};
     if (side) {
         if (!set.latency_flat() || ck.B != 64) throw std::runtime_error("internal: side-stream MSM on a set with a windowed part");
-        run_msm(ln, with_plane(MsmCtx{ln.side, ln.d_digits_s.p, ln.d_gok_s.p}, ln, scalars), set, scalars, mont != 0, ck.B, ck.n, ck.rt.latency, ln.d_part1c.p, ln.d_part1d.p, ln.d_sj1[k].p, ln.d_flat1[k].p, sum, false, false, ln.pending1);
-        return;
+        r.ctx = MsmCtx{ln.side, ln.d_digits_s.p, ln.d_gok_s.p}; r.pa = ln.d_part1c.p; r.pb = ln.d_part1d.p;
+    } else {
+        r.digits_ready = digits_ready;
+        if (timed) {      // the dominant kernel (Z): its events, and at full batches its clock stamps
+            r.ev_begin = ln.ev[5]; r.ev_end = ln.ev[6];
+            if (!ck.rt.latency) r.clk = ln.d_clk.p;
+            if (cfg.z_exp_entry_bits > 0 && cfg.z_exp_entry_bits < 31) r.clk_mask = (1u << cfg.z_exp_entry_bits) - 1;
+        }
     }
-    run_msm(ln, with_plane(MsmCtx{ln.stream, ln.d_digits_w.p && &set != &mZ ? ln.d_digits_w.p : ln.d_digits.p, ln.d_gok.p}, ln, scalars), set, scalars, mont != 0, ck.B, ck.n, ck.rt.latency, ln.d_part1a.p, ln.d_part1b.p, ln.d_sj1[k].p, ln.d_flat1[k].p, sum, timed, digits_ready, ln.pending1);
+    r.ctx = with_plane(r.ctx, ln, scalars); r.opts = msm_opts;
+    msm_run<G1Aff, G1Xyzz>(set, r, ln.pending1);
 }
 
 void AlgorithmImpl::run_msm_g2(Lane& ln, const Chunk& ck, const MsmSet<G2Aff>& set, const fe* scalars, int mont, G2Xyzz* sum, bool side) {
     if (side && (!set.latency_flat() || ck.B != 64)) throw std::runtime_error("internal: side-stream MSM on a set with a windowed part");
-    run_msm(ln, with_plane(side ? MsmCtx{ln.side2, ln.d_digits_s2.p, ln.d_gok_s2.p} : MsmCtx{ln.stream, ln.d_digits_w.p ? ln.d_digits_w.p : ln.d_digits.p, ln.d_gok.p}, ln, scalars), set, scalars, mont != 0, ck.B, ck.n, ck.rt.latency, ln.d_part2a.p, ln.d_part2b.p, ln.d_sj2.p, ln.d_flat2.p, sum, false, false, ln.pending2);
+    MsmRun<G2Xyzz> r{with_plane(side ? MsmCtx{ln.side2, ln.d_digits_s2.p, ln.d_gok_s2.p} : MsmCtx{ln.stream, ln.d_digits_w.p ? ln.d_digits_w.p : ln.d_digits.p, ln.d_gok.p}, ln, scalars),
+                     scalars, mont != 0, ck.B, ck.n, ck.rt.latency, ln.d_part2a.p, ln.d_part2b.p, ln.d_sj2.p, ln.d_flat2.p, sum};
+    r.opts = msm_opts;
+    msm_run<G2Aff, G2Xyzz>(set, r, ln.pending2);
 }
 
 void AlgorithmImpl::fetch_column(Lane& ln, const fe* mat, size_t rows, size_t B, size_t col, std::vector<uint8_t>& out) {

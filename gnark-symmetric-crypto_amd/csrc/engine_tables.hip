@@ -16,7 +16,7 @@ AlgorithmImpl::AlgorithmImpl(Cipher c, const uint8_t* pk, size_t pk_len, const u
     if (!cfg.few_max) cfg.few_max = cipher == CHACHA20 ? 32 : 20;
     // the latency kernels' layouts hold MSM_FEW_PROOFS statements, and the route of a chunk (chunk_route.hpp) takes such a call for one 64-column batch
     if (cfg.few_max < 0 || cfg.few_max > (int)MSM_FEW_PROOFS) throw std::runtime_error("EngineConfig::few_max must be in [0, " + std::to_string(MSM_FEW_PROOFS) + "]");
-    WIN_SLICE = (size_t)cfg.win_slice;
+    msm_opts.win_slice = (size_t)cfg.win_slice;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) throw std::runtime_error("no HIP device available: the GPU prover has no CPU fallback");
     HIP_CHECK(hipSetDevice(cfg.device));
@@ -203,90 +203,34 @@ std::vector<uint8_t> decode_g2_points(const KeyPoints& pts, G2Aff* out, hipStrea
     return decode_points<G2Aff, 64>(pts, out, stream, launch_decompress_g2, launch_decode_raw_g2, launch_g2_subgroup);
 }
 
-template <class AffT, class XyzzT>
-void AlgorithmImpl::build_rows(const AffT* bases, size_t n, const std::vector<uint64_t>& off, const std::vector<uint32_t>& len, AffT* table) {
-    const uint32_t cap = 256;
-    const std::vector<MsmRowSeg> segs = msm_row_segments(off, len, cap);
-    if (segs.empty()) return;
-    size_t chunk = ((size_t)4 << 30) / (cap * sizeof(XyzzT)); if (chunk > segs.size()) chunk = segs.size();
-    DevBuf<XyzzT> scratch(chunk * cap); DevBuf<MsmRowSeg> d_segs(segs.size());
-    d_segs.upload(segs.data(), segs.size(), stream);
-    for (size_t t0 = 0; t0 < segs.size(); t0 += chunk) launch_build_rows(bases, d_segs.p + t0, segs.size() - t0 < chunk ? segs.size() - t0 : chunk, cap, table, scratch.p, stream);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipStreamSynchronize(stream));
-}
-
 template <class AffT, class XyzzT, class Decomp>
 void AlgorithmImpl::build_set(MsmSet<AffT>& set, const KeyPoints& raw, size_t point_bytes, const std::vector<uint32_t>& rows, int c, const char* what, Decomp decomp, bool uniform, int expand_cv,
                               const std::vector<uint8_t>* classes, uint32_t zero_row, bool latency_layout) {
     const std::vector<uint8_t>& cls = classes ? *classes : row_class;
     const size_t n = raw.x.size() / point_bytes;
     if (rows.size() != n) throw std::runtime_error(std::string("pk: row map size mismatch for ") + what);
-    set.nbases = n; set.c = c; set.nwin = msm_windows(c);
+    set.nbases = n;
     DevBuf<AffT> bases(n ? n : 1);
     const std::vector<uint8_t> st = decomp(raw, bases.p);
     for (size_t i = 0; i < n; i++) if (st[i] == 1) throw std::runtime_error(std::string("pk: invalid point in ") + what);
-    const size_t D = (size_t)1 << (c - 1);
     const uint32_t ROW_ZERO = zero_row != 0xFFFFFFFFu ? zero_row : (uint32_t)(n_wires + 3);
     // The layout (msm_layout.hpp); the point at infinity contributes nothing: dropped.
     // flat part: [bits][narrow][padding to an octet][window octets of the expanded wide wires]; expand_cv > 0: EVERY base becomes window octets of that
     // digit width (the latency-path layout of the quotient bases: no Horner pass)
     const MsmFlatPlan plan = msm_plan_flat(msm_sort_bases(st, rows, cls, uniform, cfg.bit_groups, cfg.row_margin_bits, NARROW_MAX_BITS), rows, ROW_ZERO, uniform, expand_cv, EXPAND_MAX, EXPAND_C, msm_windows);
-    const std::vector<uint32_t>&src = plan.src, &shift = plan.shift, &frows = plan.frows, &len = plan.len, &wide = plan.wide; const std::vector<int32_t>& octwin = plan.octwin;
-    if (plan.nexpanded) { set.cv = plan.cv; set.nexpanded = plan.nexpanded; }
-    set.nflat = src.size(); set.nbit = plan.nbit;
-    if (set.nflat) {
-        DevBuf<AffT> fb(set.nflat); DevBuf<uint32_t> d_src(set.nflat), d_shift(set.nflat);
-        d_src.upload(src.data(), src.size(), stream); d_shift.upload(shift.data(), shift.size(), stream);
-        launch_shift_bases(bases.p, d_src.p, d_shift.p, set.nflat, fb.p, stream);
-        std::vector<uint64_t> off; const size_t entries = msm_row_offsets(len, off);
-        set.ftable.alloc(entries); table_bytes += set.ftable.bytes();
-        set.rowoff.alloc(set.nflat); set.rowlen.alloc(set.nflat); set.frows.alloc(set.nflat); set.octwin.alloc(octwin.size());
-        set.rowoff.upload(off.data(), set.nflat, stream); set.rowlen.upload(len.data(), set.nflat, stream);
-        set.frows.upload(frows.data(), set.nflat, stream); set.octwin.upload(octwin.data(), octwin.size(), stream);
-        build_rows<AffT, XyzzT>(fb.p, set.nflat, off, len, set.ftable.p);
-        if (set.nbit) {
-            const size_t ng = set.nbit / 8;
-            set.sub.alloc(ng * MSM_GROUP_ENTRIES); set.group_ok.alloc(ng);
-            table_bytes += set.sub.bytes();
-            build_subset<AffT, XyzzT>(fb.p, ng, set.sub.p, set.group_ok.p);
+    msm_build_tables<AffT, XyzzT>(set, bases.p, plan, rows, c, stream, &table_bytes);
+    // the windowed part once more in the latency layout (the quotient bases have their own budgeted layout: init_key)
+    if (set.nwide && !uniform && cfg.few_path && cfg.few_wide && latency_layout) {
+        const std::vector<uint32_t>& wide = plan.wide;
+        KeyPoints raw_w; raw_w.x.resize(set.nwide * point_bytes); if (!raw.y.empty()) raw_w.y.resize(set.nwide * point_bytes);
+        std::vector<uint32_t> rows_w(set.nwide);
+        for (size_t i = 0; i < set.nwide; i++) {
+            memcpy(raw_w.x.data() + i * point_bytes, raw.x.data() + (size_t)wide[i] * point_bytes, point_bytes); rows_w[i] = rows[wide[i]];
+            if (!raw.y.empty()) memcpy(raw_w.y.data() + i * point_bytes, raw.y.data() + (size_t)wide[i] * point_bytes, point_bytes);
         }
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipStreamSynchronize(stream));      // fb, d_src, d_shift go out of scope
+        set.few_wide.reset(new MsmSet<AffT>());
+        build_set<AffT, XyzzT>(*set.few_wide, raw_w, point_bytes, rows_w, c, what, decomp, true, 8, classes, zero_row);
     }
-    set.nwide = wide.size();
-    if (set.nwide) {      // windowed part: uniform rows
-        DevBuf<AffT> wb(set.nwide); DevBuf<uint32_t> d_src(set.nwide), d_shift(set.nwide);
-        std::vector<uint32_t> zero(set.nwide, 0u), wrows(set.nwide);
-        for (size_t i = 0; i < set.nwide; i++) wrows[i] = rows[wide[i]];
-        d_src.upload(wide.data(), set.nwide, stream); d_shift.upload(zero.data(), set.nwide, stream);
-        launch_shift_bases(bases.p, d_src.p, d_shift.p, set.nwide, wb.p, stream);
-        set.wrows.alloc(set.nwide); set.wrows.upload(wrows.data(), set.nwide, stream);
-        set.wtable.alloc(set.nwide * D); table_bytes += set.wtable.bytes();
-        std::vector<uint64_t> off(set.nwide); std::vector<uint32_t> len(set.nwide, (uint32_t)D);
-        for (size_t i = 0; i < set.nwide; i++) off[i] = i * D;
-        build_rows<AffT, XyzzT>(wb.p, set.nwide, off, len, set.wtable.p);
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipStreamSynchronize(stream));
-        if (!uniform && cfg.few_path && cfg.few_wide && latency_layout) {      // (the quotient bases have their own budgeted layout: init_key)
-            KeyPoints raw_w; raw_w.x.resize(set.nwide * point_bytes); if (!raw.y.empty()) raw_w.y.resize(set.nwide * point_bytes);
-            std::vector<uint32_t> rows_w(set.nwide);
-            for (size_t i = 0; i < set.nwide; i++) {
-                memcpy(raw_w.x.data() + i * point_bytes, raw.x.data() + (size_t)wide[i] * point_bytes, point_bytes); rows_w[i] = rows[wide[i]];
-                if (!raw.y.empty()) memcpy(raw_w.y.data() + i * point_bytes, raw.y.data() + (size_t)wide[i] * point_bytes, point_bytes);
-            }
-            set.few_wide.reset(new MsmSet<AffT>());
-            build_set<AffT, XyzzT>(*set.few_wide, raw_w, point_bytes, rows_w, c, what, decomp, true, 8, classes, zero_row);
-        }
-    }
-}
-
-template <class AffT, class XyzzT>
-void AlgorithmImpl::build_subset(const AffT* b, size_t ng, AffT* t, uint8_t* ok) {
-    size_t chunk = ((size_t)2 << 30) / (MSM_GROUP_ENTRIES * sizeof(XyzzT)); if (chunk > ng) chunk = ng;
-    DevBuf<XyzzT> sc(chunk * MSM_GROUP_ENTRIES);
-    for (size_t g0 = 0; g0 < ng; g0 += chunk) launch_build_subset(b + 8 * g0, ng - g0 < chunk ? ng - g0 : chunk, t + g0 * MSM_GROUP_ENTRIES, sc.p, ok + g0, stream);
-    HIP_CHECK(hipStreamSynchronize(stream));
 }
 
 // The fold (k_quot_bases.hip): U' and V' from U and V by three group transforms (launch_quot_fold_dft) — 3 n points and the weights as scratch.
@@ -518,19 +462,11 @@ void AlgorithmImpl::alloc_lane(Lane& ln, size_t B) {
     }
     // partial-sum / digit buffers: the largest need over every batch size this context can be asked for
     size_t p1 = 0, p1b = 0, p2 = 0, p2b = 0, dg = 0, dgz = 0, sj2 = 0, gk = 0; size_t sj1[Lane::NSETS] = {0, 0, 0, 0, 0, 0, 0, 0};
-    auto need = [&](auto& m, size_t b, size_t& pa, size_t& pb, size_t& sj) {
-        auto part = [&](size_t nb, size_t ns, size_t cols) {
-            if (ns * cols > pa) pa = ns * cols;
-            if ((ns + MSM_REDUCE_FANIN - 1) / MSM_REDUCE_FANIN * cols > pb) pb = (ns + MSM_REDUCE_FANIN - 1) / MSM_REDUCE_FANIN * cols;
-        };
-        size_t per = 0;
-        if (m.nflat) { part(m.nflat, msm_slices(m.nflat, 1, 256, b, per), b); if (m.nflat / 8 * b > dg) dg = m.nflat / 8 * b; if (m.nbit / 8 * (b / 64) > gk) gk = m.nbit / 8 * (b / 64); if (m.nbit / 8 * MSM_FEW_PROOFS > gk) gk = m.nbit / 8 * MSM_FEW_PROOFS; }
-        if (b == 64 && m.few_wide) {      // latency layout of the wide wires: digits of its octets, partial sums of both parts side by side
-            const size_t o2 = (m.few_wide->nflat + 7) / 8;
-            if (o2 * 64 > dg) dg = o2 * 64;
-            part(0, ((m.nflat + 7) / 8 + 63) / 64 + (o2 + 63) / 64, 64);
+    auto need = [&](auto& m, size_t b, size_t& pa, size_t& pb, size_t& sj) {      // a batch call of b columns; 64 columns: a latency call as well
+        for (int latency = 0; latency <= (b == 64 ? 1 : 0); latency++) {
+            const MsmGeometry g = msm_geometry(m.shape(), b, latency != 0, msm_opts);
+            pa = std::max(pa, g.pa); pb = std::max(pb, g.pb); sj = std::max(sj, g.sj); dg = std::max(dg, g.digit_words); gk = std::max(gk, g.gok_bytes);
         }
-        if (m.nwide) { const size_t bw = b * (size_t)m.nwin; part(m.nwide, msm_slices(m.nwide, (size_t)m.nwin, WIN_SLICE, b, per), bw); if (bw > sj) sj = bw; const size_t d = (size_t)m.nwin * (((m.digit_bases ? m.digit_bases : m.nwide) + 7) / 8) * b * msm_digit_words(m.c); if (d > dg) dg = d; }
     };
     MsmSet<G1Aff>* g1sets[Lane::NSETS] = {&mA, &mB1, &mK, &mZ, &mPed, &mPedSigma, &mZfew, &mC};
     ln.need_at.clear();

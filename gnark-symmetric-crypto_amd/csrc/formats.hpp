@@ -18,6 +18,12 @@ constexpr uint32_t HINT_RANDOMIZE = 1774611027u;  // internal/hints.Randomize
 constexpr uint32_t HINT_BSB22 = 4156202267u;      // frontend/cs.Bsb22CommitmentComputePlaceholder
 constexpr uint32_t WIRE_CONST = 0xFFFFFFFFu;
 
+// the moduli of BN254's scalar field (r) and base field (p), big-endian: what the entry points hold a caller's values against
+inline constexpr uint8_t kFrModBE[32] = {0x30, 0x64, 0x4e, 0x72, 0xe1, 0x31, 0xa0, 0x29, 0xb8, 0x50, 0x45, 0xb6, 0x81, 0x81, 0x58, 0x5d,
+                                         0x28, 0x33, 0xe8, 0x48, 0x79, 0xb9, 0x70, 0x91, 0x43, 0xe1, 0xf5, 0x93, 0xf0, 0x00, 0x00, 0x01};
+inline constexpr uint8_t kFpModBE[32] = {0x30, 0x64, 0x4e, 0x72, 0xe1, 0x31, 0xa0, 0x29, 0xb8, 0x50, 0x45, 0xb6, 0x81, 0x81, 0x58, 0x5d,
+                                         0x97, 0x81, 0x6a, 0x91, 0x68, 0x71, 0xca, 0x8d, 0x3c, 0x20, 0x8c, 0x16, 0xd8, 0x7c, 0xfd, 0x47};
+
 enum BlueprintKind { BP_HINT = 0, BP_R1C = 1, BP_LOOKUP = 2 };
 
 struct R1csFile {

@@ -239,7 +239,7 @@ void launch_shift_bases(const G2Aff* in, const uint32_t* src, const uint32_t* sh
 // e_{8o..8o+7, j} of proof p (noct = ceil(nbases / 8); bases beyond nbases get zero digits).  nwin = msm_windows(c).  c = 17 (MSM_MAX_WINDOW):
 // digits need 18 bits, so an octet takes TWO 16-byte words of eight int32 — digits[2 * index], digits[2 * index + 1]: buffers twice the size.
 constexpr int MSM_MAX_WINDOW = 17;
-inline size_t msm_digit_words(int c) { return c > 16 ? 2 : 1; }      // 16-byte words per (window, octet, proof)
+// (msm_digit_words(c), msm_layout.hpp: 16-byte words per (window, octet, proof))
 struct MsmRecodeArgs {
     const fe* scalars; const uint32_t* rows;   // [row][batch]; scalar row per base (nullptr: row k)
     int mont;                                  // 1: Montgomery residues of wire values (sign-normalised before recoding), 0: canonical integers < r
@@ -277,7 +277,7 @@ struct MsmWinArgs {
 template <class AffT> void launch_msm_win(const MsmWinArgs& a, hipStream_t s);
 // The same partial sums for the first `nproofs` proofs only (columns nproofs .. batch-1 of `partial` are not written): lanes are bases
 // instead of proofs — the latency path of a single Prove call.  Worth it below MSM_FEW_PROOFS proofs.
-constexpr size_t MSM_FEW_PROOFS = 32;     // layout bound of the latency kernels; the engine's threshold is EngineConfig::few_max
+// (MSM_FEW_PROOFS = 32, msm_layout.hpp: the layout bound of the latency kernels)
 template <class AffT> void launch_msm_win_few(const MsmWinArgs& a, size_t nproofs, hipStream_t s);
 // out[p] = sum_j 2^(c j) S[j * batch + p] (+ addend[p] when addend != nullptr), for up to MSM_HORNER_JOBS independent sets in one launch
 constexpr int MSM_HORNER_JOBS = 6;
@@ -331,7 +331,7 @@ template <class AffT> void launch_msm_flat_few(const MsmFlatArgs& a, size_t npro
 // is the final sum).  `batch` counts independent columns (proofs, or windows x proofs).  Groups hold 64 slices (butterfly over
 // lanes, small batches) or MSM_REDUCE_FANIN (lanes = columns, large batches), so `out` must have room for
 // ceil(nslices / MSM_REDUCE_FANIN) * batch points; it must not alias `partial`.
-constexpr size_t MSM_REDUCE_FANIN = 32;
+// (MSM_REDUCE_FANIN = 32: msm_layout.hpp)
 inline bool msm_reduce_by_proof(size_t nslices, size_t batch) { return (batch / 64) * ((nslices + MSM_REDUCE_FANIN - 1) / MSM_REDUCE_FANIN) >= 128; }   // by-proof does 8x less work; the butterfly only wins when there are too few (proof group, chunk) waves
 inline size_t msm_reduce_groups(size_t nslices, size_t batch) { const size_t f = msm_reduce_by_proof(nslices, batch) ? MSM_REDUCE_FANIN : 64; return (nslices + f - 1) / f; }
 size_t launch_msm_reduce(const G1Xyzz* partial, size_t nslices, size_t batch, G1Xyzz* out, hipStream_t s);

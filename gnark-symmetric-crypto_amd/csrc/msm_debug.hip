@@ -1,37 +1,26 @@
 // TEST HOOK gsc_debug_msm (include/libprove.h): the MSM kernels on a caller's bases and scalars, without a key, a circuit or a witness.
-// The layout comes from the planner build_set uses (msm_layout.hpp), the tables from the same builders, and the sums run through run_msm's launch
-// sequence: launch_shift_bases, launch_build_rows, launch_build_subset; launch_msm_recode / launch_msm_recode_flat(_few); launch_msm_flat(_few) /
-// launch_msm_win(_few); the reduction loops of reduce_slices(_few); launch_msm_horner with the flat sum as addend.  No production kernel is changed
-// or copied for it: the one kernel here turns the XYZZ sums into canonical affine coordinates.  tests/test_gpu_msm.py is the caller.
+// What is the hook's own: the refusals (check), decoding the caller's points and scalars, scratch for one call (sized by msm_geometry), the info
+// block and the copies back.  Everything between is the engine's own code: the planner build_set uses (msm_plan_flat, msm_layout.hpp), its table
+// builder (msm_build_tables, msm_set.hpp) and the launch sequence of a prover's MSM (msm_run), then launch_msm_horner on the job that left.  With
+// digit_bases the hook recodes digit_rows into the digit buffer itself (launch_msm_recode), as the last quotient kernel does for the folded Z set.
+// No production kernel is changed or copied for it: the one kernel here turns the XYZZ sums into canonical affine coordinates (debug_ops.hpp's sum_out).
+// tests/test_gpu_msm.py is the caller.
 #include "msm_debug.hpp"
 #include "engine_impl.hpp"
 #include "msm_dev.hpp"
+#include "debug_ops.hpp"
 
 namespace gsc {
 using namespace bn254;
 
 namespace {
 
-// out[i] = sums[i] as canonical little-endian coordinates (G1 x, y; G2 x.a0, x.a1, y.a0, y.a1); inf[i] = 1 and zeros for the point at infinity
+// out[i] = sums[i] as canonical little-endian coordinates; inf[i] = 1 and zeros for the point at infinity
 template <class F>
 __global__ __launch_bounds__(64) void k_debug_msm_out(const fe* sums, size_t n, fe* out, uint8_t* inf) {
-    using C = Curve9<F>;
     const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const Xyzz9<F> v = C::load_xyzz(sums + i * (4 * F::WORDS));
-    fe* o = out + i * (2 * F::WORDS);
-    if (v.inf) { inf[i] = 1; for (int q = 0; q < 2 * F::WORDS; q++) store_fe(o + q, fe{}); return; }
-    inf[i] = 0;
-    const Aff9<F> a = C::to_aff(v);
-    if constexpr (F::WORDS == 1) { store_fe(o, Fp29::pack(Fp29::from_mont(a.x))); store_fe(o + 1, Fp29::pack(Fp29::from_mont(a.y))); }
-    else {
-        store_fe(o, Fp29::pack(Fp29::from_mont(a.x.a0))); store_fe(o + 1, Fp29::pack(Fp29::from_mont(a.x.a1)));
-        store_fe(o + 2, Fp29::pack(Fp29::from_mont(a.y.a0))); store_fe(o + 3, Fp29::pack(Fp29::from_mont(a.y.a1)));
-    }
+    if (i < n) dbg::sum_out<F>(sums, i, out, inf);
 }
-
-const uint8_t kFrModBE[32] = {0x30, 0x64, 0x4e, 0x72, 0xe1, 0x31, 0xa0, 0x29, 0xb8, 0x50, 0x45, 0xb6, 0x81, 0x81, 0x58, 0x5d,
-                              0x28, 0x33, 0xe8, 0x48, 0x79, 0xb9, 0x70, 0x91, 0x43, 0xe1, 0xf5, 0x93, 0xf0, 0x00, 0x00, 0x01};
 
 [[noreturn]] void refuse(const std::string& why) { throw std::runtime_error("gsc_debug_msm: " + why); }
 
@@ -85,19 +74,6 @@ Checked check(const gsc_debug_msm_args& a) {
     return ck;
 }
 
-template <class AffT, class XyzzT>
-void build_rows(const AffT* bases, const std::vector<uint64_t>& off, const std::vector<uint32_t>& len, AffT* table, hipStream_t s) {
-    const uint32_t cap = 256;
-    const std::vector<MsmRowSeg> segs = msm_row_segments(off, len, cap);
-    if (segs.empty()) return;
-    size_t chunk = ((size_t)1 << 30) / (cap * sizeof(XyzzT)); if (chunk > segs.size()) chunk = segs.size();
-    DevBuf<XyzzT> scratch(chunk * cap); DevBuf<MsmRowSeg> d_segs(segs.size());
-    d_segs.upload(segs.data(), segs.size(), s);
-    for (size_t t0 = 0; t0 < segs.size(); t0 += chunk) launch_build_rows(bases, d_segs.p + t0, segs.size() - t0 < chunk ? segs.size() - t0 : chunk, cap, table, scratch.p, s);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipStreamSynchronize(s));
-}
-
 void copy_out(uint8_t* dst, size_t cap, const void* src, size_t bytes, uint32_t& written, const char* what, hipStream_t s) {
     written = 0;
     if (!dst && !cap) return;
@@ -110,11 +86,11 @@ template <class AffT, class XyzzT>
 void run(const gsc_debug_msm_args& a, const Checked& ck) {
     using F = typename GroupOf<AffT>::F;
     const MsmFlatPlan& pl = ck.plan;
-    const size_t B = a.batch, n = a.nbases, nflat = pl.src.size(), nwide = pl.wide.size(), nwin = (size_t)ck.nwin, npr = a.nproofs;
+    const size_t B = a.batch, n = a.nbases, nflat = pl.src.size(), nwide = pl.wide.size(), npr = a.nproofs;
     const bool few = npr != 0;
     hipStream_t s = nullptr;
     uint32_t* info = a.info; memset(info, 0, 64 * sizeof(uint32_t));
-    info[0] = (uint32_t)nflat; info[1] = (uint32_t)pl.nbit; info[2] = (uint32_t)pl.nexpanded; info[3] = (uint32_t)nwide; info[4] = (uint32_t)nwin;
+    info[0] = (uint32_t)nflat; info[1] = (uint32_t)pl.nbit; info[2] = (uint32_t)pl.nexpanded; info[3] = (uint32_t)nwide; info[4] = (uint32_t)ck.nwin;
     info[44] = (uint32_t)ck.ncols; info[45] = (uint32_t)(nflat / 8); info[46] = (uint32_t)ck.noct_w; info[47] = (uint32_t)pl.cv;
 
     // the bases, decoded like a key's points
@@ -143,111 +119,49 @@ void run(const gsc_debug_msm_args& a, const Checked& ck) {
     DevBuf<int8_t> plane;
     if (a.plane) { const size_t pb = (B / 64) * (size_t)a.plane_stride * 64; plane.alloc(pb ? pb : 1); if (pb) HIP_CHECK(hipMemcpy(plane.p, a.plane, pb, hipMemcpyHostToDevice)); }
 
-    DevBuf<XyzzT> sum(B), flat(B);
+    // the tables: the engine's builder on the plan
+    MsmSet<AffT> set; size_t table_bytes = 0;
+    msm_build_tables<AffT, XyzzT>(set, bases.p, pl, std::vector<uint32_t>(a.rows, a.rows + n), a.c, s, &table_bytes);
+    if (nwide) set.digit_bases = a.digit_bases;
+    // scratch for this one call
+    MsmLaunchOpts opts; opts.per_flat = a.per_flat; opts.per_win = a.per_win;
+    const MsmGeometry g = msm_geometry(set.shape(), B, few, opts);
+    info[5] = (uint32_t)g.flat_slices; info[6] = (uint32_t)g.flat_per; info[7] = (uint32_t)g.win_slices; info[8] = (uint32_t)g.win_per;
+    DevBuf<XyzzT> sum(B), flat(B), pa(g.pa + 1), pb(g.pb + 1), sj(g.sj + 1);
+    DevBuf<uint4> fdigits(g.digit_words + 1), wdigits(g.digit_words + 1); DevBuf<uint8_t> gok(g.gok_bytes + 1);
     HIP_CHECK(hipMemsetAsync(sum.p, 0, sum.bytes(), s)); HIP_CHECK(hipMemsetAsync(flat.p, 0, flat.bytes(), s));
-    std::vector<std::pair<size_t, bool>> levels;
-    auto put_levels = [&](uint32_t at) {
-        if (levels.size() > 8) refuse("more than eight reduction levels");
-        info[at] = (uint32_t)levels.size();
-        for (size_t i = 0; i < levels.size(); i++) { info[at + 1 + 2 * i] = (uint32_t)levels[i].first; info[at + 2 + 2 * i] = levels[i].second ? 1u : 0u; }
-        levels.clear();
+    HIP_CHECK(hipMemsetAsync(pa.p, 0, pa.bytes(), s)); HIP_CHECK(hipMemsetAsync(pb.p, 0, pb.bytes(), s)); HIP_CHECK(hipMemsetAsync(sj.p, 0, sj.bytes(), s));
+    HIP_CHECK(hipMemsetAsync(fdigits.p, 0, fdigits.bytes(), s)); HIP_CHECK(hipMemsetAsync(wdigits.p, 0, wdigits.bytes(), s)); HIP_CHECK(hipMemsetAsync(gok.p, 0, gok.bytes(), s));
+    DevBuf<uint32_t> drows;
+    if (set.digit_bases) {      // in the last quotient kernel's place: the digits of digit_rows, laid out for digit_bases bases
+        drows.alloc(a.digit_bases); drows.upload(a.digit_rows, a.digit_bases, s);
+        launch_msm_recode(MsmRecodeArgs{scalars.p, drows.p, a.mont ? 1 : 0, a.digit_bases, B, a.c, set.nwin, wdigits.p}, s);
+    }
+    // the call: the engine's launch sequence, then the Horner job it left
+    MsmLevels levels; MsmHornerJobs jobs{};
+    MsmRun<XyzzT> r{MsmCtx{s, fdigits.p, gok.p, a.plane ? plane.p : nullptr, a.plane ? a.plane_rows : 0u, a.plane ? a.plane_stride : 0u}, scalars.p, a.mont != 0, B, npr, few, pa.p, pb.p, sj.p, flat.p, sum.p};
+    r.digits_ready = set.digit_bases != 0; r.opts = opts; r.win_digits = wdigits.p; r.levels = &levels;
+    msm_run<AffT, XyzzT>(set, r, jobs);
+    if (jobs.n) launch_msm_horner<AffT>(jobs, B, s);
+    HIP_CHECK(hipGetLastError());
+    auto put_levels = [&](uint32_t at, const std::vector<std::pair<size_t, bool>>& lv) {
+        if (lv.size() > 8) refuse("more than eight reduction levels");
+        info[at] = (uint32_t)lv.size();
+        for (size_t i = 0; i < lv.size(); i++) { info[at + 1 + 2 * i] = (uint32_t)lv[i].first; info[at + 2 + 2 * i] = lv[i].second ? 1u : 0u; }
     };
-
-    // ---- flat part ----
-    DevBuf<AffT> ftable, sub; DevBuf<uint64_t> rowoff; DevBuf<uint32_t> rowlen, frows; DevBuf<int32_t> octwin; DevBuf<uint8_t> group_ok, gok; DevBuf<uint4> fdigits;
-    DevBuf<XyzzT> fpa, fpb;
-    if (nflat) {
-        {
-            DevBuf<AffT> fb(nflat); DevBuf<uint32_t> d_src(nflat), d_shift(nflat);
-            d_src.upload(pl.src.data(), nflat, s); d_shift.upload(pl.shift.data(), nflat, s);
-            launch_shift_bases(bases.p, d_src.p, d_shift.p, nflat, fb.p, s);
-            ftable.alloc(ck.flat_entries); rowoff.alloc(nflat); rowlen.alloc(nflat); frows.alloc(nflat); octwin.alloc(pl.octwin.size());
-            rowoff.upload(ck.off.data(), nflat, s); rowlen.upload(pl.len.data(), nflat, s); frows.upload(pl.frows.data(), nflat, s); octwin.upload(pl.octwin.data(), pl.octwin.size(), s);
-            build_rows<AffT, XyzzT>(fb.p, ck.off, pl.len, ftable.p, s);
-            const size_t ng = pl.nbit / 8;
-            if (ng) {
-                sub.alloc(ng * MSM_GROUP_ENTRIES); group_ok.alloc(ng);
-                DevBuf<XyzzT> sc(ng * MSM_GROUP_ENTRIES);
-                launch_build_subset(fb.p, ng, sub.p, sc.p, group_ok.p, s);
-                HIP_CHECK(hipGetLastError());
-                HIP_CHECK(hipStreamSynchronize(s));
-            }
-            HIP_CHECK(hipGetLastError());
-            HIP_CHECK(hipStreamSynchronize(s));
-        }
-        const size_t noct = nflat / 8, ng = pl.nbit / 8, gok_n = ng * (few ? MSM_FEW_PROOFS : B / 64);
-        fdigits.alloc(noct * B); gok.alloc(gok_n ? gok_n : 1);
-        HIP_CHECK(hipMemsetAsync(fdigits.p, 0, fdigits.bytes(), s)); HIP_CHECK(hipMemsetAsync(gok.p, 0, gok.bytes(), s));
-        MsmFlatRecodeArgs ra{scalars.p, frows.p, octwin.p, nflat, B, pl.cv, fdigits.p, pl.nbit, group_ok.p, gok.p, a.mont ? 1 : 0, a.plane ? plane.p : nullptr, a.plane ? a.plane_rows : 0, a.plane ? a.plane_stride : 0};
-        size_t per = 512, nslices;
-        if (few) nslices = msm_flat_few_slices(nflat);
-        else if (a.per_flat) { per = a.per_flat; nslices = (nflat + per - 1) / per; }
-        else nslices = msm_slices(nflat, 1, 256, B, per);
-        if (per % 8 || per > 512 || nslices * per < nflat) refuse("internal: flat slices do not cover the bases");
-        info[5] = (uint32_t)nslices; info[6] = (uint32_t)per;
-        fpa.alloc(nslices * B); fpb.alloc(nslices * B);
-        HIP_CHECK(hipMemsetAsync(fpa.p, 0, fpa.bytes(), s)); HIP_CHECK(hipMemsetAsync(fpb.p, 0, fpb.bytes(), s));
-        MsmFlatArgs fa{ftable.p, rowoff.p, rowlen.p, nflat, fdigits.p, B, nslices, per, fpa.p, pl.nbit, sub.p, gok.p, scalars.p, frows.p};
-        XyzzT* dst = nwide ? flat.p : sum.p;
-        if (few) {
-            launch_msm_recode_flat_few(ra, npr, s);
-            launch_msm_flat_few<AffT>(fa, npr, s);
-            msm_reduce_slices_few(s, fpa.p, fpb.p, nslices, B, B, npr, dst, &levels);
-        } else {
-            launch_msm_recode_flat(ra, s);
-            launch_msm_flat<AffT>(fa, s);
-            msm_reduce_slices(s, fpa.p, fpb.p, nslices, B, dst, &levels);
-        }
-        HIP_CHECK(hipGetLastError());
-        put_levels(9);
-    }
-    // ---- windowed part ----
-    DevBuf<AffT> wtable; DevBuf<uint32_t> wrows; DevBuf<uint4> wdigits; DevBuf<XyzzT> wpa, wpb, sj;
-    if (nwide) {
-        const size_t nrec = a.digit_bases ? a.digit_bases : nwide;
-        {
-            DevBuf<AffT> wb(nwide); DevBuf<uint32_t> d_src(nwide), d_shift(nwide);
-            std::vector<uint32_t> zero(nwide, 0u), wr(nrec);
-            for (size_t i = 0; i < nrec; i++) wr[i] = a.digit_bases ? a.digit_rows[i] : a.rows[pl.wide[i]];
-            d_src.upload(pl.wide.data(), nwide, s); d_shift.upload(zero.data(), nwide, s);
-            launch_shift_bases(bases.p, d_src.p, d_shift.p, nwide, wb.p, s);
-            wrows.alloc(nrec); wrows.upload(wr.data(), nrec, s);
-            wtable.alloc(nwide * ck.D);
-            std::vector<uint64_t> off(nwide); std::vector<uint32_t> len(nwide, (uint32_t)ck.D);
-            for (size_t i = 0; i < nwide; i++) off[i] = i * ck.D;
-            build_rows<AffT, XyzzT>(wb.p, off, len, wtable.p, s);
-        }
-        size_t per = 0, nslices;
-        if (a.per_win) { per = a.per_win; nslices = (nwide + per - 1) / per; }
-        else { nslices = msm_slices(nwide, nwin, 256, B, per); if (few) msm_slices_latency(nwide, nslices, per); }
-        if (!per || per % 8 || nslices * per < nwide) refuse("internal: windowed slices do not cover the bases");
-        info[7] = (uint32_t)nslices; info[8] = (uint32_t)per;
-        const size_t Bw = B * nwin;
-        wdigits.alloc(nwin * ck.noct_w * B * msm_digit_words(a.c));
-        wpa.alloc(nslices * Bw); wpb.alloc(nslices * Bw); sj.alloc(Bw);
-        HIP_CHECK(hipMemsetAsync(wdigits.p, 0, wdigits.bytes(), s)); HIP_CHECK(hipMemsetAsync(wpa.p, 0, wpa.bytes(), s)); HIP_CHECK(hipMemsetAsync(wpb.p, 0, wpb.bytes(), s)); HIP_CHECK(hipMemsetAsync(sj.p, 0, sj.bytes(), s));
-        MsmRecodeArgs ra{scalars.p, wrows.p, a.mont ? 1 : 0, nrec, B, a.c, (int)nwin, wdigits.p};
-        launch_msm_recode(ra, s);
-        MsmWinArgs wa{wtable.p, a.c, (int)nwin, nwide, wdigits.p, B, nslices, per, wpa.p, nullptr, 0u, a.digit_bases ? (size_t)a.digit_bases : 0};
-        if (few) { launch_msm_win_few<AffT>(wa, npr, s); msm_reduce_slices_few(s, wpa.p, wpb.p, nslices, Bw, B, npr, sj.p, &levels); }
-        else { launch_msm_win<AffT>(wa, s); msm_reduce_slices(s, wpa.p, wpb.p, nslices, Bw, sj.p, &levels); }
-        MsmHornerJobs jobs{}; jobs.n = 1;
-        jobs.job[0] = MsmHornerJob{sj.p, nflat ? flat.p : (XyzzT*)nullptr, sum.p, (int)nwin, a.c};
-        launch_msm_horner<AffT>(jobs, B, s);
-        HIP_CHECK(hipGetLastError());
-        put_levels(26);
-        info[43] = nflat ? 1u : 0u;
-    }
+    put_levels(9, levels.flat); put_levels(26, levels.win);
+    info[43] = jobs.n && jobs.job[0].addend ? 1u : 0u;
     // ---- results ----
     DevBuf<fe> d_out(2 * F::WORDS * ck.ncols); DevBuf<uint8_t> d_inf(ck.ncols);
     hipLaunchKernelGGL(k_debug_msm_out<F>, dim3((unsigned)((ck.ncols + 63) / 64)), dim3(64), 0, s, reinterpret_cast<const fe*>(sum.p), ck.ncols, d_out.p, d_inf.p);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipMemcpyAsync(a.out, d_out.p, d_out.bytes(), hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipMemcpyAsync(a.out_inf, d_inf.p, ck.ncols, hipMemcpyDeviceToHost, s));
-    copy_out(a.flat_digits, a.flat_digits_cap, fdigits.p, fdigits.bytes(), info[48], "the flat digits", s);
-    copy_out(a.win_digits, a.win_digits_cap, wdigits.p, wdigits.bytes(), info[49], "the windowed digits", s);
+    const size_t win_words = nwide ? (size_t)set.nwin * ck.noct_w * B * msm_digit_words(a.c) : 0;
+    copy_out(a.flat_digits, a.flat_digits_cap, fdigits.p, nflat / 8 * B * sizeof(uint4), info[48], "the flat digits", s);
+    copy_out(a.win_digits, a.win_digits_cap, wdigits.p, win_words * sizeof(uint4), info[49], "the windowed digits", s);
     copy_out(a.gok, a.gok_cap, gok.p, pl.nbit / 8 * (few ? MSM_FEW_PROOFS : B / 64), info[50], "gok", s);
-    copy_out(a.group_ok, a.group_ok_cap, group_ok.p, pl.nbit / 8, info[51], "group_ok", s);
+    copy_out(a.group_ok, a.group_ok_cap, set.group_ok.p, pl.nbit / 8, info[51], "group_ok", s);
     HIP_CHECK(hipStreamSynchronize(s));
 }
 
@@ -255,9 +169,7 @@ void run(const gsc_debug_msm_args& a, const Checked& ck) {
 
 void debug_msm(int device, const gsc_debug_msm_args& a) {
     const Checked ck = check(a);      // every refusal the host can decide comes before a device is asked for
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) throw std::runtime_error("no HIP device available");
-    HIP_CHECK(hipSetDevice(device));
+    use_device(device);
     if (a.group == 0) run<G1Aff, G1Xyzz>(a, ck); else run<G2Aff, G2Xyzz>(a, ck);
 }
 

@@ -1,7 +1,8 @@
 // Host-side planning of an MSM set (no HIP: builds with a plain compiler): which bases become bit groups, narrow rows, window octets or the
-// windowed part, the flat part's order and row geometry, the row-building work items and the slice counts of a launch.  ONE definition,
-// called by AlgorithmImpl::build_set / run_msm (engine_tables.hip, engine_prove.hip) and by the test hook gsc_debug_msm (msm_debug.hip);
-// tests/test_msm_layout_host.py holds it against a Python statement of the same rules.
+// windowed part, the flat part's order and row geometry, the row-building work items, and msm_geometry: the slice counts of a launch with the
+// scratch a call can write.  ONE definition: the planner is called by AlgorithmImpl::build_set (engine_tables.hip) and by the test hook
+// gsc_debug_msm (msm_debug.hip); msm_geometry by msm_run (msm_set.hip, the launch sequence of both), by alloc_lane for the lanes' scratch and by the
+// hook for its own.  tests/test_msm_layout_host.py holds both against a Python statement of the same rules.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -98,5 +99,46 @@ inline void msm_slices_latency(size_t nbases, size_t& nslices, size_t& per) {
 }
 // slices of a flat set's latency kernel: lanes = octets, 64 octets per wave
 inline size_t msm_flat_few_slices(size_t nflat) { return ((nflat + 7) / 8 + 63) / 64; }
+
+constexpr size_t MSM_REDUCE_FANIN = 32;   // slices per group of a reduction level by proof (launch_msm_reduce, kernels.hpp); a level's output holds ceil(slices / 32) groups
+constexpr size_t MSM_FEW_PROOFS = 32;     // layout bound of the latency kernels; the engine's threshold is EngineConfig::few_max
+inline size_t msm_digit_words(int c) { return c > 16 ? 2 : 1; }      // 16-byte words per (window, octet, proof) of the windowed digits
+
+// The geometry of one MSM call over a set: the slices the launches take, and what the call can write of its scratch.
+// few_wide_nflat: the flat bases of the latency layout of the windowed part (MsmSet::few_wide), 0 = none.
+struct MsmShape { size_t nflat = 0, nbit = 0, nwide = 0; int c = 0, nwin = 0; size_t digit_bases = 0, few_wide_nflat = 0; };
+// win_slice: bases per slice of the windowed kernel at full batches (measured 64 .. 512: kernel time within 1 %); per_flat / per_win: bases per slice
+// whatever the batch (the test hook; per_flat is not read by a latency call), 0 = the choice of msm_slices
+struct MsmLaunchOpts { size_t win_slice = 256, per_flat = 0, per_win = 0; };
+struct MsmGeometry {
+    size_t flat_slices = 0, flat_per = 0, win_slices = 0, win_per = 0;      // what the launches take
+    size_t few_wide_slices = 0;      // latency call: the last of flat_slices belong to the latency layout of the windowed part, side by side in the same partial buffer
+    size_t pa = 0, pb = 0, sj = 0;   // points: slice partials, the first reduction level's output, the per-window sums
+    size_t digit_words = 0, gok_bytes = 0;      // 16-byte digit words, bit-group verdicts
+};
+inline MsmGeometry msm_geometry(const MsmShape& m, size_t B, bool latency, const MsmLaunchOpts& o = MsmLaunchOpts()) {
+    MsmGeometry g;
+    auto raise = [](size_t& v, size_t to) { if (to > v) v = to; };
+    if (m.nflat) {
+        if (latency) { g.flat_per = 512; g.flat_slices = msm_flat_few_slices(m.nflat); }
+        else if (o.per_flat) { g.flat_per = o.per_flat; g.flat_slices = (m.nflat + o.per_flat - 1) / o.per_flat; }
+        else g.flat_slices = msm_slices(m.nflat, 1, 256, B, g.flat_per);
+        g.digit_words = m.nflat / 8 * B;
+        g.gok_bytes = m.nbit / 8 * (B / 64); raise(g.gok_bytes, m.nbit / 8 * MSM_FEW_PROOFS);
+    }
+    if (latency && m.few_wide_nflat) {
+        g.flat_per = 512; g.few_wide_slices = msm_flat_few_slices(m.few_wide_nflat); g.flat_slices += g.few_wide_slices;
+        raise(g.digit_words, (m.few_wide_nflat + 7) / 8 * B);
+    }
+    if (m.nwide) {
+        if (o.per_win) { g.win_per = o.per_win; g.win_slices = (m.nwide + o.per_win - 1) / o.per_win; }
+        else { g.win_slices = msm_slices(m.nwide, (size_t)m.nwin, o.win_slice, B, g.win_per); if (latency) msm_slices_latency(m.nwide, g.win_slices, g.win_per); }
+        g.sj = B * (size_t)m.nwin;
+        raise(g.digit_words, (size_t)m.nwin * (((m.digit_bases ? m.digit_bases : m.nwide) + 7) / 8) * B * msm_digit_words(m.c));
+    }
+    g.pa = g.flat_slices * B; raise(g.pa, g.win_slices * g.sj);
+    g.pb = (g.flat_slices + MSM_REDUCE_FANIN - 1) / MSM_REDUCE_FANIN * B; raise(g.pb, (g.win_slices + MSM_REDUCE_FANIN - 1) / MSM_REDUCE_FANIN * g.sj);
+    return g;
+}
 
 }  // namespace gsc

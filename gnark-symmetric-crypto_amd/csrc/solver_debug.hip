@@ -137,10 +137,8 @@ int run(int device, const gsc_debug_solve_args& a, const R1csFile& cs) {
 
 int debug_solve(int device, const gsc_debug_solve_args& a) {
     const R1csFile cs = describe(a);      // every refusal the host can decide without the builders comes before a device is asked for
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) throw std::runtime_error("no HIP device available");
     try {
-        HIP_CHECK(hipSetDevice(device));
+        use_device(device);
         return run(device, a, cs);
     } catch (const DeviceError& e) { printf("gsc_debug_solve: %s\n", e.what()); return -3; }
     catch (const std::runtime_error& e) {

@@ -17,6 +17,13 @@ namespace gsc {
 
 #define HIP_CHECK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) throw std::runtime_error(std::string("HIP error: ") + hipGetErrorString(e_) + " at " #expr); } while (0)
 
+// the calling thread's device for what follows; throws when the process sees no HIP device at all (the hooks: after every refusal the host can decide)
+inline void use_device(int device) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) throw std::runtime_error("no HIP device available");
+    HIP_CHECK(hipSetDevice(device));
+}
+
 // alloc_lane points this at the lane's byte count for its duration: every DevBuf the thread allocates meanwhile is counted, so that the lane's
 // region table (wipe_plan.hpp) can be held against what was really allocated
 inline thread_local size_t* devbuf_tally = nullptr;

@@ -144,13 +144,13 @@ extern long long gsc_debug_compute_h(GoUint8 algorithmID, const uint8_t *abc_be,
  * csrc/k_quot_bases.hip).  ab_be: a, then b, each [m][64] canonical big-endian values.  d_out: [domain][64] canonical little-endian
  * values, row i = A(zeta w^i) * B(zeta w^i) * 2^261 mod r in natural order (zeta: the primitive 2n-th root of unity, w = zeta^2 the
  * domain generator; A, B the interpolation polynomials of a, b).  Returns the domain size (also for d_out == NULL), -1 on error. */
+extern long long gsc_debug_compute_d(GoUint8 algorithmID, const uint8_t *ab_be, size_t m, uint8_t *d_out, size_t cap);
 /* TEST HOOK: n samples {100 MHz clock, shader clock}, interval_us apart, taken by a one-wave kernel that stays resident beside whatever the
  * device runs meanwhile (call it from a thread of its own around a Prove): the shader clock each kernel of a call is granted.  Blocks. */
 extern int gsc_debug_clock_trace(uint32_t n, uint32_t interval_us, unsigned long long *out);
 /* TEST HOOK: bytes of a finished call's secrets (key wires of the witness, r, s, -rs, the raw input records, commitment masks) that are still
  * non-zero in the algorithm's device buffers — the engine clears them behind the last kernel of every call, so 0; -1 on error / hooks disabled. */
 extern long long gsc_debug_secret_residue(GoUint8 algorithmID);
-extern long long gsc_debug_compute_d(GoUint8 algorithmID, const uint8_t *ab_be, size_t m, uint8_t *d_out, size_t cap);
 // TEST HOOK: the evaluation-form quotient sum (sum c_i U_i + sum d_i V_i) of 64 columns through the batch kernels and whatever sets InitAlgorithm built.
 // abc_be: a, b, c = a b row by row, [m][64] canonical big-endian values; out: 64 x 64 B big-endian X | Y; flags[i] = 1: the point at infinity.  0 on success.
 extern int gsc_debug_z_sum(GoUint8 algorithmID, const uint8_t *abc_be, size_t m, uint8_t *out, uint8_t *flags);
@@ -401,7 +401,8 @@ extern int gsc_debug_column_sums(int group, uint32_t n_rows, const uint8_t *rows
                                  uint8_t *out, uint8_t *out_inf);
 /* TEST HOOK: the MSM kernels alone, on a caller's bases and scalars: no key, no circuit, no witness.  The bases are laid out by the planner the
  * engine uses for a key's sets (csrc/msm_layout.hpp) from the caller's per-base description, the tables are built, and one sum per column runs
- * through the launch sequence of a prover's MSM: recoding, gather-accumulate (flat and windowed part), slice reductions, Horner.
+ * through the launch sequence of a prover's MSM, the function the engine calls (msm_run, csrc/msm_set.hpp): recoding, gather-accumulate (flat and
+ * windowed part), slice reductions, Horner.
  *   group 0: G1 (64 B per point), 1: G2 (128 B, A1 before A0); points: nbases raw finite points, big-endian X | Y;
  *   kind[k]: 0 bit, 1 narrow with rowlen[k] table entries (1 .. 32768), 2 wide; rows[k] < n_rows: the scalar row of base k; zero_row: a row of zeros
  *   (padding slots);  c in [4, 17]: digit width of the windowed part;  cv: 0 = wide bases take the windowed kernel, 4 .. 15 = every wide base becomes

@@ -5,6 +5,9 @@
 //     stdin : n, uniform, bit_groups, margin, max_bits, expand_cv, expand_max, expand_c, zero_row, ncls (int32 LE) | status: n bytes | rows: n u32 | cls: ncls bytes
 //     stdout: nbit, nexpanded, cv, nflat, noct, nwide, nsegs (u32) | src, shift, frows, len: nflat u32 each | octwin: noct i32 | wide: nwide u32 |
 //             off: nflat u64 | entries u64
+//   "geometry" : msm_geometry (csrc/msm_layout.hpp) on the calls of stdin, one per line, its answer to stdout, one line each
+//     stdin : nflat nbit nwide c nwin digit_bases few_wide_nflat B latency win_slice per_flat per_win
+//     stdout: flat_slices flat_per win_slices win_per few_wide_slices pa pb sj digit_words gok_bytes
 #include "msm_dev.hpp"
 #include <cstdio>
 #include <cstring>
@@ -108,4 +111,22 @@ static int layout() {
     return 0;
 }
 
-int main(int argc, char** argv) { return argc > 1 && !strcmp(argv[1], "layout") ? layout() : self_check(); }
+static int geometry() {
+    unsigned long long v[12];
+    for (;;) {
+        int got = 0;
+        while (got < 12 && scanf("%llu", &v[got]) == 1) got++;
+        if (!got) return 0;
+        if (got != 12) return 2;
+        MsmShape m; m.nflat = v[0]; m.nbit = v[1]; m.nwide = v[2]; m.c = (int)v[3]; m.nwin = (int)v[4]; m.digit_bases = v[5]; m.few_wide_nflat = v[6];
+        MsmLaunchOpts o; o.win_slice = v[9]; o.per_flat = v[10]; o.per_win = v[11];
+        const MsmGeometry g = msm_geometry(m, v[7], v[8] != 0, o);
+        printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\n", g.flat_slices, g.flat_per, g.win_slices, g.win_per, g.few_wide_slices, g.pa, g.pb, g.sj, g.digit_words, g.gok_bytes);
+    }
+}
+
+int main(int argc, char** argv) {
+    if (argc > 1 && !strcmp(argv[1], "layout")) return layout();
+    if (argc > 1 && !strcmp(argv[1], "geometry")) return geometry();
+    return self_check();
+}

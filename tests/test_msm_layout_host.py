@@ -1,7 +1,8 @@
 """The host-side geometry of the MSM kernels, built for the host (tests/native/msm_geometry_check.cpp): xcd_slice and slice_bounds
-(csrc/msm_dev.hpp), msm_slices, the row segments and the layout planner that build_set and gsc_debug_msm share (csrc/msm_layout.hpp), the
-reduction levels (csrc/kernels.hpp).  The self-check also runs once under ASan + UBSan as a stand-alone program; the planner is held against
-a Python statement of the same rules (devref.FlatPlan, devref.sort_bases) on hand-built classes."""
+(csrc/msm_dev.hpp), msm_slices, the row segments, the layout planner that build_set and gsc_debug_msm share and msm_geometry, the slices and
+scratch of a call that msm_run, alloc_lane and gsc_debug_msm share (csrc/msm_layout.hpp), the reduction levels (csrc/kernels.hpp).  The self-check
+also runs once under ASan + UBSan as a stand-alone program; the planner is held against a Python statement of the same rules (devref.FlatPlan,
+devref.sort_bases) on hand-built classes, msm_geometry against the one below."""
 import os
 import struct
 import subprocess
@@ -101,3 +102,107 @@ def test_the_hand_built_classes_cover_the_rules():
     assert w64.len[8:32] == [1 << 14] * 17 + [1] * 7 and w64.shift[8:32] == [15 * q for q in range(17)] + [0] * 7 and w64.octwin[1:5] == [0, 8, 16, 0]
     assert len(plans["infinity_dropped"].src) == 8 and plans["infinity_dropped"].nbit == 0
     assert plans["narrow_lengths"].len[:6] == [4, 8, 128, 4096, 8192, 16384] and plans["narrow_lengths"].nexpanded == 2
+
+
+# ---- msm_geometry: the slices of a call and the scratch it can write ----
+MSM_REDUCE_FANIN = 32
+_ceil = lambda a, b: -(-a // b)
+
+
+def _slices(nbases, nwin, most, B):
+    """msm_slices: slices of up to `most` bases, shorter ones while that leaves fewer than ~8k waves; whole octets, no empty slice"""
+    gw = (B // 64) * nwin
+    n = (max(_ceil(nbases, most), _ceil(8192, gw)) + 7) & ~7
+    per = ((_ceil(nbases, n) + 7) & ~7) or 8
+    return _ceil(nbases, per) or 1, per
+
+
+def _geometry(shape, B, latency, win_slice=256, per_flat=0, per_win=0):
+    """the rules, stated once more: (flat_slices, flat_per, win_slices, win_per, few_wide_slices, pa, pb, sj, digit_words, gok_bytes)"""
+    nflat, nbit, nwide, c, nwin, digit_bases, few_wide_nflat = shape
+    few = lambda n: _ceil(_ceil(n, 8), 64)
+    fs = fp = ws = wp = fws = 0
+    if nflat and latency:
+        fs, fp = few(nflat), 512
+    elif nflat and per_flat:
+        fs, fp = _ceil(nflat, per_flat), per_flat
+    elif nflat:
+        fs, fp = _slices(nflat, 1, 256, B)
+    if latency and few_wide_nflat:      # side by side in the same partial buffer
+        fws, fp = few(few_wide_nflat), 512
+        fs += fws
+    if nwide and per_win:
+        ws, wp = _ceil(nwide, per_win), per_win
+    elif nwide:
+        ws, wp = _slices(nwide, nwin, win_slice, B)
+        if latency and ws > _ceil(nwide, 512):
+            ws, wp = _ceil(nwide, 512), 512
+    sj = B * nwin if nwide else 0
+    pa = max(fs * B, ws * B * nwin)
+    pb = max(_ceil(fs, MSM_REDUCE_FANIN) * B, _ceil(ws, MSM_REDUCE_FANIN) * B * nwin)
+    digits = max(nflat // 8 * B, _ceil(few_wide_nflat, 8) * 64 if latency else 0,
+                 nwin * _ceil(digit_bases or nwide, 8) * B * (2 if c > 16 else 1) if nwide else 0)
+    gok = max(nbit // 8 * (B // 64), nbit // 8 * D.MSM_FEW_PROOFS) if nflat else 0
+    return fs, fp, ws, wp, fws, pa, pb, sj, digits, gok
+
+
+def _shapes():
+    """name -> (nflat, nbit, nwide, c, nwin, digit_bases, few_wide_nflat).  The first five are ChaCha20-V3's sets as gsc_describe names them
+    (profiles/r18_ab_default.txt): grouped bits, an octet of narrow rows and padding, one wide wire expanded into the 24 slots of its 17 windows
+    at EXPAND_C = 15; Z folded; C with a windowed part"""
+    w = D.msm_windows
+    expanded = 8 * _ceil(w(EXPAND_C), 8)
+    return {
+        "chacha_A": (22000 + 8 + expanded, 22000, 0, 16, w(16), 0, 0),
+        "chacha_B": (12528 + 8 + expanded, 12528, 0, 16, w(16), 0, 0),
+        "chacha_K": (22128 + 8 + expanded, 22128, 0, 16, w(16), 0, 0),
+        "chacha_Z": (0, 0, 23616, 17, w(17), 32768, 0),                 # 23616 live of 32768 digit bases, two words per digit octet
+        "chacha_C": (23280 + 8, 23280, 336, 16, w(16), 0, 0),
+        "flat_only": (520, 16, 0, 6, w(6), 0, 0),
+        "flat_one_octet": (8, 0, 0, 16, w(16), 0, 0),
+        "windowed_only": (0, 0, 1000, 16, w(16), 0, 0),
+        "windowed_c17": (0, 0, 129, 17, w(17), 0, 0),
+        "both": (72, 8, 65, 8, w(8), 0, 0),
+        "digit_bases": (0, 0, 19, 6, w(6), 40, 0),
+        "few_wide": (23288, 23280, 336, 16, w(16), 0, 336 * 8 * _ceil(w(8), 8)),      # the windowed part once more as (base, window) rows of 8-bit digits
+        "few_wide_alone": (0, 0, 70, 16, w(16), 0, 70 * 8 * _ceil(w(8), 8)),
+        "empty": (0, 0, 0, 16, w(16), 0, 0),
+    }
+
+
+def _calls():
+    out = []
+    for name, shape in _shapes().items():
+        for B in (64, 128, 1024, 8192):
+            out.append((name, shape, B, 0, 256, 0, 0))
+        out.append((name, shape, 64, 1, 256, 0, 0))
+        out.append((name, shape, 128, 0, 64, 0, 0))                    # GSC_WIN_SLICE
+        out.append((name, shape, 64, 0, 256, 8, 0)); out.append((name, shape, 64, 0, 256, 0, 64)); out.append((name, shape, 128, 0, 256, 512, 8))      # the overrides
+        out.append((name, shape, 64, 1, 256, 8, 64))                   # a latency call reads per_win, not per_flat
+    return out
+
+
+def test_geometry_matches_the_python_statement(geometry_exe):
+    calls = _calls()
+    text = "".join("%d %d %d %d %d %d %d %d %d %d %d %d\n" % (shape + (B, lat, ws, pf, pw)) for _, shape, B, lat, ws, pf, pw in calls)
+    out = subprocess.run([geometry_exe, "geometry"], input=text, capture_output=True, text=True, timeout=60, check=True).stdout.splitlines()
+    assert len(out) == len(calls)
+    for (name, shape, B, lat, ws, pf, pw), line in zip(calls, out):
+        got = tuple(int(x) for x in line.split())
+        assert got == _geometry(shape, B, bool(lat), ws, pf, pw), (name, B, lat, ws, pf, pw)
+        # whatever the rules: whole octets per slice, the slices cover the bases, a flat slice holds at most 512, the first reduction level fits pb
+        nflat, nbit, nwide, c, nwin = shape[:5]
+        fs, fp, wsl, wp, fws, pa, pb, sj = got[:8]
+        assert fp % 8 == 0 and fp <= 512 and wp % 8 == 0 and (fs - fws) * fp >= nflat and wsl * wp >= nwide and fws * 512 >= (shape[6] if lat else 0)
+        assert bool(fs - fws) == bool(nflat) and bool(wsl) == bool(nwide)
+        assert pa >= fs * B and pa >= wsl * sj and pb >= _ceil(fs, 32) * B and pb >= _ceil(wsl, 32) * sj
+
+
+def test_the_lanes_scratch_is_the_batch_calls_and_the_latency_call_at_64():
+    """alloc_lane's rule, on the Python statement: a latency call never needs more partial sums, window sums or verdicts than the batch call of 64
+    columns over the same set, and more digit words only for a latency layout of the windowed part"""
+    for name, shape in _shapes().items():
+        batch, lat = _geometry(shape, 64, False), _geometry(shape, 64, True)
+        if not shape[6]:
+            assert all(l <= b for l, b in zip(lat[5:], batch[5:])), name
+        assert lat[7] == batch[7] and lat[9] == batch[9], name
