@@ -28,7 +28,8 @@ EXPORTS = ["enforce_binding", "InitAlgorithm", "Free", "Prove", "ProveBatch", "g
            "gsc_prove_check_init", "gsc_prove_check_stats", "gsc_debug_prove_corrupt",
            "gsc_release_algorithm", "gsc_replace_algorithm", "gsc_memory_info", "gsc_key_generation",
            "gsc_setup_contribute", "gsc_setup_verify_contribution", "gsc_debug_scale_points",
-           "gsc_srs_verify", "gsc_debug_srs_generate", "gsc_debug_group_idft", "gsc_debug_column_sums", "gsc_setup_from_srs", "gsc_debug_msm", "gsc_debug_solve", "gsc_debug_assemble"]
+           "gsc_srs_verify", "gsc_debug_srs_generate", "gsc_debug_group_idft", "gsc_debug_column_sums", "gsc_setup_from_srs", "gsc_debug_msm", "gsc_debug_solve", "gsc_debug_assemble",
+           "gsc_srs_initial", "gsc_srs_contribute", "gsc_srs_verify_contribution", "gsc_debug_scale_powers"]
 
 
 class GoSlice(C.Structure):
@@ -177,6 +178,14 @@ def lib():
         L.gsc_srs_verify.argtypes = [GoSlice]
         L.gsc_debug_srs_generate.restype = C.c_int
         L.gsc_debug_srs_generate.argtypes = [C.c_int, C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
+        L.gsc_srs_initial.restype = C.c_int
+        L.gsc_srs_initial.argtypes = [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
+        L.gsc_srs_contribute.restype = C.c_int
+        L.gsc_srs_contribute.argtypes = [GoSlice, C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_void_p]
+        L.gsc_srs_verify_contribution.restype = C.c_int
+        L.gsc_srs_verify_contribution.argtypes = [GoSlice, GoSlice, C.c_char_p]
+        L.gsc_debug_scale_powers.restype = C.c_int
+        L.gsc_debug_scale_powers.argtypes = [C.c_int, C.c_char_p, C.c_char_p, C.c_size_t, C.c_char_p, C.c_char_p, C.c_uint64, C.c_void_p, C.c_void_p]
         L.gsc_setup_from_srs.restype = C.c_int
         L.gsc_setup_from_srs.argtypes = [GoSlice, GoSlice, C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
         L.gsc_debug_group_idft.restype = C.c_int
@@ -333,6 +342,60 @@ def srs_verify(srs: bytes) -> bool:
     if rc < 0:
         raise RuntimeError("gsc_srs_verify: device error (%d)" % rc)
     return rc == 1
+
+
+SRS_CONTRIBUTION_BYTES = 544
+
+
+def srs_initial(L: int) -> bytes:
+    """gsc_srs_initial: the ceremony's starting powers file for N = 2^L (tau = alpha = beta = 1: every element a generator).  Host only and
+    deterministic.  Raises ValueError outside 1 <= L <= 24."""
+    p, n = C.c_void_p(), C.c_size_t()
+    if lib().gsc_srs_initial(L, C.byref(p), C.byref(n)) != 0:
+        raise ValueError("gsc_srs_initial: L outside [1, 24]")
+    out = C.string_at(p.value, n.value)
+    lib().Free(p)
+    return out
+
+
+def srs_contribute(srs: bytes, seed: bytes = None):
+    """gsc_srs_contribute: one contribution to a powers file (include/libprove.h) -> (srs', record).  seed (32 bytes) fixes the secrets and
+    needs the test hooks; None = the OS CSPRNG.  Raises RuntimeError with the return code (-1 seed without hooks, -2 refused file, -3 device
+    error; the reason is on stdout)."""
+    s, keep = _slice(srs)
+    p, n = C.c_void_p(), C.c_size_t()
+    rec = C.create_string_buffer(SRS_CONTRIBUTION_BYTES)
+    rc = lib().gsc_srs_contribute(s, seed, C.byref(p), C.byref(n), rec)
+    if rc != 0:
+        raise RuntimeError("gsc_srs_contribute failed: %d (see stdout)" % rc)
+    out = C.string_at(p.value, n.value), rec.raw
+    lib().Free(p)
+    return out
+
+
+def srs_verify_contribution(prev: bytes, nxt: bytes, record: bytes) -> bool:
+    """gsc_srs_verify_contribution: is `nxt` a contribution to `prev` that `record` proves, and a powers file?  `prev` is not checked in full: a
+    chain is verified link by link from srs_initial(L).  A refusal names its rule on stdout.  Raises RuntimeError on a device error."""
+    if len(record) != SRS_CONTRIBUTION_BYTES:
+        return False
+    s1, k1 = _slice(prev)
+    s2, k2 = _slice(nxt)
+    rc = lib().gsc_srs_verify_contribution(s1, s2, record)
+    if rc < 0:
+        raise RuntimeError("gsc_srs_verify_contribution: device error (%d)" % rc)
+    return rc == 1
+
+
+def debug_scale_powers(group: int, pts: bytes, inf: bytes, x: int, m: int, first: int = 0):
+    """TEST HOOK: m * x^(first + i) * P_i for raw big-endian points (64 B in G1, 128 B in G2) through k_fr_powers and the per-point ladder ->
+    (points, infinity flags)."""
+    w = 64 if group == 0 else 128
+    n = len(inf)
+    assert len(pts) == w * n
+    out, oinf = C.create_string_buffer(max(1, w * n)), C.create_string_buffer(max(1, n))
+    if lib().gsc_debug_scale_powers(group, pts, inf, n, int(x).to_bytes(32, "big"), int(m).to_bytes(32, "big"), first, out, oinf) != 0:
+        raise RuntimeError("gsc_debug_scale_powers failed (see stdout)")
+    return out.raw[:w * n], oinf.raw[:n]
 
 
 def setup_from_srs(r1cs: bytes, srs: bytes, seed: bytes = None):

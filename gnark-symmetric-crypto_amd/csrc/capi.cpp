@@ -15,6 +15,8 @@
 #include "setup.hpp"
 #include "phase2_gpu.hpp"
 #include "srs_gpu.hpp"
+#include "srs_contrib.hpp"
+#include "srs_contrib_gpu.hpp"
 #include "msm_debug.hpp"
 #include "solver_debug.hpp"
 #include "assemble_debug.hpp"
@@ -278,6 +280,15 @@ void retire(ServedAlgo& s, const char* who) {
     } catch (const std::exception& e) { printf("%s: the outgoing engine could not be scanned: %s\n", who, e.what()); }
 }
 
+// a result for the caller to release with Free; false when malloc fails
+bool hand_over(const std::vector<uint8_t>& f, void** out, size_t* len) {
+    void* a = malloc(f.size() ? f.size() : 1);
+    if (!a) return false;
+    memcpy(a, f.data(), f.size());
+    *out = a; *len = f.size();
+    return true;
+}
+
 }  // namespace
 
 long long gsc_verify_debug_pairing_impl(const uint8_t* g1, const uint8_t* g2, size_t n, uint8_t* out, bool few);      // verify_gpu.cpp
@@ -485,6 +496,40 @@ int gsc_srs_verify(GoSlice srs) {
     if (!srs.data || srs.len <= 0) { printf("gsc_srs_verify: rule 1: srs: empty file\n"); return 0; }
     try { return srs_verify((const uint8_t*)srs.data, (size_t)srs.len); }
     catch (const std::exception& e) { printf("gsc_srs_verify: %s\n", e.what()); return -3; }
+}
+int gsc_srs_initial(int L, void** srs, size_t* len) {
+    if (!srs || !len) return -2;
+    *srs = nullptr; *len = 0;
+    try {
+        std::vector<uint8_t> f;
+        if (!srsc::initial(L, f)) { printf("gsc_srs_initial: L outside [1, 24]\n"); return -2; }
+        return hand_over(f, srs, len) ? 0 : -2;
+    } catch (const std::exception& e) { printf("gsc_srs_initial: %s\n", e.what()); return -2; }
+}
+int gsc_srs_contribute(GoSlice srs, const uint8_t* seed32, void** srs_out, size_t* len, uint8_t* record) {
+    if (!srs_out || !len || !record) return -2;
+    *srs_out = nullptr; *len = 0; memset(record, 0, GSC_SRS_CONTRIBUTION_BYTES);
+    if (seed32 && hooks_refused("gsc_srs_contribute with a caller-supplied seed")) return -1;      // deterministic secrets: test files only
+    if (!srs.data || srs.len <= 0) { printf("gsc_srs_contribute: srs: empty file\n"); return -2; }
+    try {
+        std::vector<uint8_t> f; uint8_t rec[GSC_SRS_CONTRIBUTION_BYTES];
+        const int rc = srs_contribute((const uint8_t*)srs.data, (size_t)srs.len, seed32, f, rec);
+        if (rc) return rc;
+        if (!hand_over(f, srs_out, len)) return -3;
+        memcpy(record, rec, GSC_SRS_CONTRIBUTION_BYTES);
+        return 0;
+    } catch (const std::exception& e) { printf("gsc_srs_contribute: %s\n", e.what()); return -3; }
+}
+int gsc_srs_verify_contribution(GoSlice prev, GoSlice next, const uint8_t* record) {
+    if (!prev.data || prev.len <= 0 || !next.data || next.len <= 0) { printf("gsc_srs_verify_contribution: rule 1: srs: empty file\n"); return 0; }
+    if (!record) { printf("gsc_srs_verify_contribution: rule 2: no record\n"); return 0; }
+    try { return srs_verify_contribution((const uint8_t*)prev.data, (size_t)prev.len, (const uint8_t*)next.data, (size_t)next.len, record); }
+    catch (const std::exception& e) { printf("gsc_srs_verify_contribution: %s\n", e.what()); return -3; }
+}
+int gsc_debug_scale_powers(int group, const uint8_t* pts, const uint8_t* inf, size_t n, const uint8_t* x_be32, const uint8_t* m_be32, uint64_t first, uint8_t* out, uint8_t* out_inf) {
+    if (hooks_refused("gsc_debug_scale_powers") || !x_be32 || !m_be32 || (n && (!pts || !inf || !out || !out_inf))) return -1;
+    try { srs_debug_scale_powers(group, pts, inf, n, x_be32, m_be32, first, out, out_inf); return 0; }
+    catch (const std::exception& e) { printf("%s\n", e.what()); return -1; }
 }
 int gsc_setup_from_srs(GoSlice r1cs, GoSlice srs, const uint8_t* seed32, void** pk, size_t* pk_len, void** vk, size_t* vk_len) {
     if (!pk || !pk_len || !vk || !vk_len) return -2;

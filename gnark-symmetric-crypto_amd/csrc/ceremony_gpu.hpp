@@ -1,9 +1,12 @@
-// What the key ceremony's host code shares (phase2_gpu.cpp: contributions to a key pair; srs_gpu.cpp: the check of a powers file): device
-// buffers and a stream that clean up behind themselves, the OS CSPRNG, the decoding of raw key points through the verifier's key-point
-// kernel and their way back to bytes, the generators, the refusal line.  Host code that calls HIP: include it from the *_gpu.cpp files only.
+// What the key ceremony's host code shares (phase2_gpu.cpp: contributions to a key pair; srs_gpu.cpp: the check of a powers file;
+// srs_contrib_gpu.cpp: contributions to a powers file): device buffers and a stream that clean up behind themselves, the OS CSPRNG, the
+// decoding of raw key points through the verifier's key-point kernel and their way back to bytes, one point times a public scalar, the
+// generators, the refusal line.  Host code that calls HIP: include it from the *_gpu.cpp files only.
 #pragma once
 #include "phase2_kernels.hpp"
 #include "verify_kernels.hpp"
+#include "srs.hpp"
+#include "host_field.hpp"
 #include <sys/random.h>
 #include <cerrno>
 #include <cstdio>
@@ -43,6 +46,19 @@ inline void os_random(void* out, size_t n) {      // OS CSPRNG bytes; a failure 
         else if (!(r < 0 && errno == EINTR)) throw std::runtime_error(std::string("getrandom failed: ") + strerror(errno));
     }
 }
+// a secret scalar: uniform in [1, r) by rejection; and its image for the device, little-endian canonical bytes
+inline hostf::Fr random_nonzero_fr() {
+    for (;;) {
+        uint8_t be[32];
+        os_random(be, 32);
+        be[0] &= 0x3F;
+        hostf::Fr v;
+        const bool ok = hostf::Fr::from_be(be, v) && !v.is_zero();
+        explicit_bzero(be, sizeof be);
+        if (ok) return v;
+    }
+}
+inline void fr_to_le(const hostf::Fr& v, uint8_t out[32]) { hostf::U256 c = v.canon(); memcpy(out, c.w, 32); explicit_bzero(&c, sizeof c); }
 // n fresh non-zero 128-bit values, four little-endian words each: the factors of a verifier's random combination
 inline std::vector<uint32_t> random_rho(size_t n) {
     std::vector<uint32_t> rho(4 * n);
@@ -85,15 +101,17 @@ template <class P> void download(const P* p, size_t n, uint8_t* out, uint8_t* in
 // one line on stdout; the caller returns rc (a refused step or file: 0; a refused contribution: -2)
 inline int refuse(const char* who, const std::string& why, int rc = 0) { printf("%s: %s\n", who, why.c_str()); return rc; }
 
-// the generators, raw big-endian: G1 (1, 2); G2 as gnark-crypto has it
-inline void generators(uint8_t g1[64], uint8_t g2[128]) {
-    static const char* const hex[4] = {"198e9393920d483a7260bfb731fb5d25f1aa493335a9e71297e485b7aef312c2", "1800deef121f1e76426a00665e5c4479674322d4f75edadd46debd5cd992f6ed",
-                                       "090689d0585ff075ec9e99ad690c3395bc4b313370b38ef355acdadcd122975b", "12c85ea5db8c6deb4aab71808dcb408fe3d1e7690c43d37b4ce6cc0166fa7daa"};
-    memset(g1, 0, 64); g1[31] = 1; g1[63] = 2;
-    for (int c = 0; c < 4; c++) for (int i = 0; i < 32; i++) {
-        auto nib = [](char ch) { return ch <= '9' ? ch - '0' : ch - 'a' + 10; };
-        g2[32 * c + i] = (uint8_t)(nib(hex[c][2 * i]) << 4 | nib(hex[c][2 * i + 1]));
-    }
+using srs::generators;      // raw big-endian G1 and G2 generators (srs.hpp: the host-only writer of gsc_srs_initial needs them too)
+
+// k P for one decoded G1 point and a public scalar (big-endian, < r), as raw bytes (zeros for the point at infinity): a Schnorr equation's side
+inline void scale_one(const vfy::VP1* p, const uint8_t k_be[32], uint8_t out[64], hipStream_t s) {
+    uint8_t le[32]; for (int i = 0; i < 32; i++) le[i] = k_be[31 - i];
+    Buf dk(32), o(sizeof(vfy::VP1));
+    GSC_CER_HIP_CHECK(hipMemcpyAsync(dk.p, le, 32, hipMemcpyHostToDevice, s));
+    launch_scale_points(p, 1, dk.as<uint32_t>(), o.as<vfy::VP1>(), s);
+    GSC_CER_HIP_CHECK(hipGetLastError());
+    uint8_t inf;
+    download(o.as<vfy::VP1>(), 1, out, &inf, s);
 }
 
 }  // namespace cer

@@ -1,9 +1,14 @@
 // Key ceremony, second phase (gsc_setup_contribute / gsc_setup_verify_contribution): the device side.
-//   k_scale_points<P>   one thread per point: out = k P for ONE scalar k shared by every thread.  k is toxic waste (x, 1/x or the Schnorr
-//                       nonce of a contribution), so the ladder takes the same steps whatever its bits are: every step is one doubling and
+//   k_scale_points<P, S>  one thread per point: out = k P.  S says where k comes from: UniformScalar, ONE scalar shared by every thread (x, 1/x
+//                       or the Schnorr nonce of a contribution; uniform loads), or PerPointScalar, a scalar of its own for every point (a
+//                       contribution to a powers file, DESIGN.md §3.12: the rows k_fr_powers wrote, word-major, so a wave's loads coalesce).
+//                       k is toxic waste, so the ladder takes the same steps whatever its bits are: every step is one doubling and
 //                       one exact addition of P that is always computed (madd<true>: it handles acc = infinity and acc = +-P), and the bit
-//                       only selects, limb by limb, which of the two values goes on.  k is read from memory word by word (uniform loads);
-//                       there is no private array indexed by a runtime value.  One inversion per thread makes the result affine.
+//                       only selects, limb by limb, which of the two values goes on.  The current word of k sits in a register and the next
+//                       is loaded when the (uniform) step counter crosses a word; there is no private array indexed by a runtime value.
+//                       One inversion per thread makes the result affine.
+//   k_fr_powers         row i = m x^(first + i) mod r, canonical, word-major: the scalars of one section of a powers file.  The index is
+//                       public, so the square-and-multiply over its bits branches; x, m and the rows are toxic waste (secret buffers).
 //   k_points_be<P>      decoded points -> raw big-endian bytes
 //   k_phase2_rlc<P>, _sum<P>  a verifier's two random combinations sum rho_i a_i, sum rho_i b_i (a contribution's check: Z and K before and
 //                       after; a powers file's check, srs_gpu.cpp: a vector and itself shifted by one, in G1 and in G2): the batched
@@ -43,8 +48,18 @@ template <class F> DEVFN bn254::Xyzz9<F> pick(uint32_t m, const bn254::Xyzz9<F>&
 DEVFN VP1 affine_of(const bn254::Xyzz9<bn254::Fp29f>& p) { return g1_affine(p); }
 DEVFN VP2 affine_of(const bn254::Xyzz9<bn254::Fp2x>& p) { return g2_affine(p); }
 
-template <class P>
-__global__ __launch_bounds__(kThreads) void k_scale_points(const P* in, size_t n, const uint32_t* k, P* out) {
+// where a ladder's scalar comes from: word w (of eight, little-endian) of point i's scalar
+struct UniformScalar {
+    const uint32_t* k;
+    DEVFN uint32_t word(int w, size_t) const { return k[w]; }
+};
+struct PerPointScalar {
+    const uint32_t* k; size_t n;      // word-major over the n points: k[w * n + i]
+    DEVFN uint32_t word(int w, size_t i) const { return k[(size_t)w * n + i]; }
+};
+
+template <class P, class S>
+__global__ __launch_bounds__(kThreads) void k_scale_points(const P* in, size_t n, const S k, P* out) {
     using G = GroupOfPoint<P>;
     using C = typename G::C;
     const size_t i = blockIdx.x * (size_t)kThreads + threadIdx.x;
@@ -53,13 +68,33 @@ __global__ __launch_bounds__(kThreads) void k_scale_points(const P* in, size_t n
     if (p.inf) { out[i] = p; return; }      // which points of a key are infinity is public
     const bn254::Aff9<typename G::F> a{p.x, p.y};
     bn254::Xyzz9<typename G::F> acc = C::infinity();
+    uint32_t w = k.word(7, i);
     for (int b = 253; b >= 0; b--) {        // k < r < 2^254
+        if ((b & 31) == 31) w = k.word(b >> 5, i);      // b is uniform: no branch on the scalar
         acc = C::dbl(acc);
         const bn254::Xyzz9<typename G::F> sum = C::template madd<true>(acc, a);
-        const uint32_t m = 0u - ((k[b >> 5] >> (b & 31)) & 1u);
+        const uint32_t m = 0u - ((w >> (b & 31)) & 1u);
         acc = pick(m, sum, acc);
     }
     out[i] = affine_of(acc);
+}
+
+// rows[w * n + i] = word w of m x^(first + i) mod r (canonical); x, m: eight little-endian words each, canonical, below r
+__global__ __launch_bounds__(kThreads) void k_fr_powers(const uint32_t* x, const uint32_t* m, uint64_t first, size_t n, uint32_t* rows) {
+    using Fr = bn254::Fr;
+    const size_t i = blockIdx.x * (size_t)kThreads + threadIdx.x;
+    if (i >= n) return;
+    bn254::fe xc, mc;
+    for (int j = 0; j < 8; j++) { xc.l[j] = x[j]; mc.l[j] = m[j]; }
+    const bn254::fe xm = Fr::to_mont(xc);
+    const uint64_t e = first + i;           // public: the position in the file
+    bn254::fe acc = Fr::one();
+    for (int b = 63 - __clzll(e | 1); b >= 0; b--) {
+        acc = Fr::sqr(acc);
+        if ((e >> b) & 1) acc = Fr::mul(acc, xm);
+    }
+    const bn254::fe v = Fr::mul(acc, mc);   // Montgomery x^e times canonical m: canonical m x^e
+    for (int j = 0; j < 8; j++) rows[(size_t)j * n + i] = v.l[j];
 }
 
 DEVFN void be32_of(const e1& v, uint8_t* o) {
@@ -121,10 +156,19 @@ unsigned blocks(size_t n) { return (unsigned)((n + kThreads - 1) / kThreads); }
 }  // namespace
 
 void launch_scale_points(const VP1* in, size_t n, const uint32_t* k, VP1* out, hipStream_t s) {
-    if (n) hipLaunchKernelGGL(k_scale_points<VP1>, dim3(blocks(n)), dim3(kThreads), 0, s, in, n, k, out);
+    if (n) hipLaunchKernelGGL((k_scale_points<VP1, UniformScalar>), dim3(blocks(n)), dim3(kThreads), 0, s, in, n, UniformScalar{k}, out);
 }
 void launch_scale_points(const VP2* in, size_t n, const uint32_t* k, VP2* out, hipStream_t s) {
-    if (n) hipLaunchKernelGGL(k_scale_points<VP2>, dim3(blocks(n)), dim3(kThreads), 0, s, in, n, k, out);
+    if (n) hipLaunchKernelGGL((k_scale_points<VP2, UniformScalar>), dim3(blocks(n)), dim3(kThreads), 0, s, in, n, UniformScalar{k}, out);
+}
+void launch_scale_points_each(const VP1* in, size_t n, const uint32_t* rows, VP1* out, hipStream_t s) {
+    if (n) hipLaunchKernelGGL((k_scale_points<VP1, PerPointScalar>), dim3(blocks(n)), dim3(kThreads), 0, s, in, n, PerPointScalar{rows, n}, out);
+}
+void launch_scale_points_each(const VP2* in, size_t n, const uint32_t* rows, VP2* out, hipStream_t s) {
+    if (n) hipLaunchKernelGGL((k_scale_points<VP2, PerPointScalar>), dim3(blocks(n)), dim3(kThreads), 0, s, in, n, PerPointScalar{rows, n}, out);
+}
+void launch_fr_powers(const uint32_t* x, const uint32_t* m, uint64_t first, size_t n, uint32_t* rows, hipStream_t s) {
+    if (n) hipLaunchKernelGGL(k_fr_powers, dim3(blocks(n)), dim3(kThreads), 0, s, x, m, first, n, rows);
 }
 void launch_points_be(const VP1* p, size_t n, uint8_t* out, uint8_t* inf, hipStream_t s) {
     if (n) hipLaunchKernelGGL(k_points_be<VP1>, dim3(blocks(n)), dim3(kThreads), 0, s, p, n, out, inf);

@@ -27,18 +27,6 @@ struct Secrets {
     Secrets(const Secrets&) = delete; Secrets& operator=(const Secrets&) = delete;
     ~Secrets() { explicit_bzero(&x, sizeof x); explicit_bzero(&x_inv, sizeof x_inv); explicit_bzero(&k, sizeof k); explicit_bzero(&t, sizeof t); explicit_bzero(words, sizeof words); }
 };
-void fr_to_le(const Fr& v, uint8_t out[32]) { hostf::U256 c = v.canon(); memcpy(out, c.w, 32); explicit_bzero(&c, sizeof c); }
-Fr random_nonzero_fr() {      // uniform in [1, r) by rejection
-    for (;;) {
-        uint8_t be[32];
-        os_random(be, 32);
-        be[0] &= 0x3F;
-        Fr v;
-        const bool ok = Fr::from_be(be, v) && !v.is_zero();
-        explicit_bzero(be, sizeof be);
-        if (ok) return v;
-    }
-}
 
 // the decoded points of one key file on the device
 struct DevKey {
@@ -59,17 +47,6 @@ bool deltas(const DevKey& k, uint8_t d1[64], uint8_t d2[128], hipStream_t s) {
     download(k.p1() + k.w.d1, 1, d1, &i1, s); download(k.p2() + k.w.d2, 1, d2, &i2, s);
     return !i1 && !i2;
 }
-// k P for one G1 point and a public scalar (big-endian, < r), as raw bytes
-void scale_one(const VP1* p, const uint8_t k_be[32], uint8_t out[64], hipStream_t s) {
-    uint8_t le[32]; for (int i = 0; i < 32; i++) le[i] = k_be[31 - i];
-    Buf dk(32), o(sizeof(VP1));
-    HIP_CHECK(hipMemcpyAsync(dk.p, le, 32, hipMemcpyHostToDevice, s));
-    launch_scale_points(p, 1, dk.as<uint32_t>(), o.as<VP1>(), s);
-    HIP_CHECK(hipGetLastError());
-    uint8_t inf;
-    download(o.as<VP1>(), 1, out, &inf, s);
-}
-
 }  // namespace
 
 int phase2_contribute(const uint8_t* pk, size_t pk_len, const uint8_t* vk, size_t vk_len, const uint8_t* seed32, Phase2Step& out) {

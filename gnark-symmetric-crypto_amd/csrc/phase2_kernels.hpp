@@ -8,6 +8,12 @@ namespace gsc {
 // same for every point.  The ladder does not branch on k's bits.
 void launch_scale_points(const vfy::VP1* in, size_t n, const uint32_t* k, vfy::VP1* out, hipStream_t s);
 void launch_scale_points(const vfy::VP2* in, size_t n, const uint32_t* k, vfy::VP2* out, hipStream_t s);
+// out[i] = k_i in[i]: every point has a scalar of its own, word w of point i's scalar at rows[w * n + i] (eight little-endian words, below r:
+// k_fr_powers' layout).  The same ladder, the same discipline.
+void launch_scale_points_each(const vfy::VP1* in, size_t n, const uint32_t* rows, vfy::VP1* out, hipStream_t s);
+void launch_scale_points_each(const vfy::VP2* in, size_t n, const uint32_t* rows, vfy::VP2* out, hipStream_t s);
+// rows[w * n + i] = word w of m x^(first + i) mod r, canonical, for i < n; x, m: eight little-endian words each in device memory, below r
+void launch_fr_powers(const uint32_t* x, const uint32_t* m, uint64_t first, size_t n, uint32_t* rows, hipStream_t s);
 // decoded points -> raw big-endian canonical bytes (G1: 64 B X | Y; G2: 128 B X.A1 | X.A0 | Y.A1 | Y.A0; zeros for infinity) and infinity flags
 void launch_points_be(const vfy::VP1* p, size_t n, uint8_t* out, uint8_t* inf, hipStream_t s);
 void launch_points_be(const vfy::VP2* p, size_t n, uint8_t* out, uint8_t* inf, hipStream_t s);

@@ -11,8 +11,9 @@
 // the verifier's key-point kernel read.  No compressed element and no point at infinity is admitted.  1 <= L <= 24, and the length of
 // the file is the one L gives, exactly.
 //
-// Here: the bounds and section offsets (walk), and the elements of each group as the fixed-stride vectors the decoder kernel takes (slots).
-// Whether the elements are points, and the powers they claim to be, is the device's part (srs_gpu.cpp).
+// Here: the bounds and section offsets (walk), the elements of each group as the fixed-stride vectors the decoder kernel takes (slots), the
+// generators and the one writer (assemble).  Whether the elements are points, and the powers they claim to be, is the device's part
+// (srs_gpu.cpp); the ceremony that makes such a file is srs_contrib.hpp / srs_contrib_gpu.cpp.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -106,7 +107,18 @@ inline void slots(const uint8_t* b, const Layout& l, std::vector<uint8_t>& g1, s
     memcpy(g2.data() + kG2Bytes * l.i_beta2(), b + l.off_beta2, kG2Bytes);
 }
 
-// the file for its elements in slots() order (the writer gsc_debug_srs_generate uses; the next change's contributions will write the same)
+// the generators, raw big-endian: G1 (1, 2); G2 as gnark-crypto has it
+inline void generators(uint8_t g1[64], uint8_t g2[128]) {
+    static const char* const hex[4] = {"198e9393920d483a7260bfb731fb5d25f1aa493335a9e71297e485b7aef312c2", "1800deef121f1e76426a00665e5c4479674322d4f75edadd46debd5cd992f6ed",
+                                       "090689d0585ff075ec9e99ad690c3395bc4b313370b38ef355acdadcd122975b", "12c85ea5db8c6deb4aab71808dcb408fe3d1e7690c43d37b4ce6cc0166fa7daa"};
+    memset(g1, 0, 64); g1[31] = 1; g1[63] = 2;
+    for (int c = 0; c < 4; c++) for (int i = 0; i < 32; i++) {
+        auto nib = [](char ch) { return ch <= '9' ? ch - '0' : ch - 'a' + 10; };
+        g2[32 * c + i] = (uint8_t)(nib(hex[c][2 * i]) << 4 | nib(hex[c][2 * i + 1]));
+    }
+}
+
+// the file for its elements in slots() order (the one writer: gsc_debug_srs_generate, gsc_srs_initial and gsc_srs_contribute use it)
 inline std::vector<uint8_t> assemble(const Layout& l, const uint8_t* g1, const uint8_t* g2) {
     std::vector<uint8_t> f(l.bytes);
     memcpy(f.data(), kMagic, 8);

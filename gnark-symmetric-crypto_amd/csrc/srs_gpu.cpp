@@ -23,11 +23,11 @@ using hostf::Fr;
 
 #define HIP_CHECK GSC_CER_HIP_CHECK
 
-int srs_verify(const uint8_t* f, size_t len) {
-    const char* who = "gsc_srs_verify";
+int srs_verify(const uint8_t* f, size_t len, const char* who, const std::string& prefix) {
+    auto no = [&](const std::string& why) { return refuse(who, prefix + why); };
     // rule 1: magic, L, length; every element raw and finite (host), canonical, on the curve, G2 in the subgroup (device)
     srs::Layout l; std::string err;
-    if (!srs::walk(f, len, l, err)) return refuse(who, "rule 1: " + err);
+    if (!srs::walk(f, len, l, err)) return no("rule 1: " + err);
     need_device();
     Stream st; hipStream_t s = st.s;
     const size_t N = l.N, n1 = l.n_g1(), n2 = l.n_g2();
@@ -37,13 +37,13 @@ int srs_verify(const uint8_t* f, size_t len) {
     const long long bad = decode_slots_first_bad(s1, n1, s2, n2, g1.as<VP1>(), g2.as<VP2>(), s);
     if (bad >= 0) {
         const std::string name = (size_t)bad < n1 ? srs::g1_name(l, (size_t)bad) : srs::g2_name(l, (size_t)bad - n1);
-        return refuse(who, "rule 1: srs: " + name + " is not a point of its group (a coordinate not below p, off the curve, or G2 outside the subgroup)");
+        return no("rule 1: srs: " + name + " is not a point of its group (a coordinate not below p, off the curve, or G2 outside the subgroup)");
     }
     // rule 2: the vectors start at the generators (the bytes are canonical by rule 1, so equal points are equal bytes)
     uint8_t G1[64], G2[128];
     generators(G1, G2);
-    if (memcmp(s1.data(), G1, 64)) return refuse(who, "rule 2: tauG1[0] is not the G1 generator");
-    if (memcmp(s2.data(), G2, 128)) return refuse(who, "rule 2: tauG2[0] is not the G2 generator");
+    if (memcmp(s1.data(), G1, 64)) return no("rule 2: tauG1[0] is not the G1 generator");
+    if (memcmp(s2.data(), G2, 128)) return no("rule 2: tauG2[0] is not the G2 generator");
 
     // rules 3-6: for each vector v of m + 1 elements, S0 = sum rho_i v[i] and S1 = sum rho_i v[i + 1] over i < m, fresh rho for each
     const size_t m_tau = 2 * N - 2, m = N - 1;
@@ -74,11 +74,11 @@ int srs_verify(const uint8_t* f, size_t len) {
     pair(8, beta1_0, G2);      pair(9, G1, beta2);            // rule 7: e(betaG1[0], G2) = e(G1, betaG2)
     if (gsc_verify_debug_pairing_impl(&p1[0][0], &p2[0][0], 10, fv.data(), true) != 10) throw std::runtime_error("the pairings failed on the device");
     auto same = [&](int i) { return !memcmp(fv.data() + 384 * i, fv.data() + 384 * (i + 1), 384); };
-    if (!same(0)) return refuse(who, "rule 3: tauG1 is not the powers of tauG2[1]'s tau over the G1 generator");
-    if (!same(2)) return refuse(who, "rule 4: tauG2 is not the powers of tauG1[1]'s tau over the G2 generator");
-    if (!same(4)) return refuse(who, "rule 5: alphaG1 is not alphaG1[0] times the powers of tau");
-    if (!same(6)) return refuse(who, "rule 6: betaG1 is not betaG1[0] times the powers of tau");
-    if (!same(8)) return refuse(who, "rule 7: betaG2 and betaG1[0] are not the same multiple of the generators");
+    if (!same(0)) return no("rule 3: tauG1 is not the powers of tauG2[1]'s tau over the G1 generator");
+    if (!same(2)) return no("rule 4: tauG2 is not the powers of tauG1[1]'s tau over the G2 generator");
+    if (!same(4)) return no("rule 5: alphaG1 is not alphaG1[0] times the powers of tau");
+    if (!same(6)) return no("rule 6: betaG1 is not betaG1[0] times the powers of tau");
+    if (!same(8)) return no("rule 7: betaG2 and betaG1[0] are not the same multiple of the generators");
     return 1;
 }
 

@@ -5,14 +5,16 @@
 #include <cstddef>
 #include <cstdint>
 #include <stdexcept>
+#include <string>
 #include <vector>
 #include "setup.hpp"
 
 namespace gsc {
 
 // 1 accepted, 0 refused (one line on stdout naming the first rule that failed, rules 1-7 of DESIGN.md §3.11).  Throws std::runtime_error
-// on a device error.  Thread-safe: a stream and buffers of its own on GSC_DEVICE / the first of GSC_DEVICES.
-int srs_verify(const uint8_t* srs, size_t len);
+// on a device error.  Thread-safe: a stream and buffers of its own on GSC_DEVICE / the first of GSC_DEVICES.  who / prefix: the call the
+// line speaks for and what stands before the rule (gsc_srs_verify_contribution runs this check on a step's next file as its rule 5).
+int srs_verify(const uint8_t* srs, size_t len, const char* who = "gsc_srs_verify", const std::string& prefix = std::string());
 // Groth16 Setup from a powers file (gsc_setup_from_srs): no scalar of the file is known here; the Lagrange bases at tau (group_idft.hpp),
 // the column sums A, B, K (k_srs_columns.hip) and Z are computed in the groups, on the device, and written by setup.cpp's one writer.
 // seed32 == nullptr: gamma = delta = 1, the Pedersen sigma and g from the OS CSPRNG.  seed32 (TEST, the caller gates it): gamma, delta, sigma,

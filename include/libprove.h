@@ -324,7 +324,7 @@ extern uint64_t gsc_key_generation(GoUint8 algorithmID);
 
 /* ---- key ceremony, second phase (an addition): several parties each re-randomise delta of a key pair, so that forging
  * proofs under the final key needs every one of them to collude (or to have kept their secret).  tau, alpha, beta and gamma are NOT
- * re-randomised: that is the first phase, which this library does not have.
+ * re-randomised: that is the first phase (gsc_srs_initial / gsc_srs_contribute below, then gsc_setup_from_srs).
  * A contribution draws a secret x in [1, r) and makes, from (pk, vk) in gnark's layouts (points compressed or raw, as InitAlgorithm takes them),
  * G1.Delta' = x G1.Delta and G2.Delta' = x G2.Delta in pk and vk, G1.Z'[k] = (1/x) G1.Z[k] and G1.K'[i] = (1/x) G1.K[i] in pk; every other byte
  * of both files is copied; the rewritten points are written compressed.  The result is an ordinary key pair for InitAlgorithm,
@@ -366,11 +366,48 @@ extern int gsc_debug_scale_points(int group, const uint8_t *pts, const uint8_t *
  * rule, (3) e(sum rho_i tauG1[i+1], G_2) = e(sum rho_i tauG1[i], tauG2[1]) over i < 2N-2; (4) e(G_1, sum rho_i tauG2[i+1]) = e(tauG1[1],
  * sum rho_i tauG2[i]) over i < N-1; (5) and (6) rule 3's equation over alphaG1 and over betaG1, i < N-1; (7) e(betaG1[0], G_2) = e(G_1, betaG2).
  * A wrong file is accepted with probability about 2^-128.  The check shows that the file is the powers of SOME tau, alpha, beta; it does not
- * show who made the file or that anybody discarded those scalars: that is what a ceremony's contribution records are for, and contributions
- * to a powers file are not part of this library yet.
+ * show who made the file or that anybody discarded those scalars: that is what a ceremony's contribution records are for
+ * (gsc_srs_contribute / gsc_srs_verify_contribution below).
  * 1 accepted, 0 refused (one line on stdout naming the first rule that failed), -3 device error.  Needs no initialised algorithm; runs on
  * GSC_DEVICE, or the first of GSC_DEVICES, and is thread-safe. */
 extern int gsc_srs_verify(GoSlice srs);
+/* ---- key ceremony, first phase: making a powers file (an addition).  The ceremony starts from the file of tau = alpha =
+ * beta = 1 and every party multiplies the scalars by secrets of its own; the final tau, alpha, beta are products that nobody knows unless
+ * every party colludes (or kept its secrets).  The full chain to a proving key, with no test hook on the way: gsc_srs_initial ->
+ * gsc_srs_contribute (each party; everybody checks every link with gsc_srs_verify_contribution) -> gsc_setup_from_srs ->
+ * gsc_setup_contribute (each party; gsc_setup_verify_contribution).
+ * The starting file for N = 2^L, 1 <= L <= 24, in the layout above: every G1 element the G1 generator, every G2 element the G2 generator,
+ * raw.  Host only (no device, no test hooks) and deterministic: a verifier of a chain makes the start itself and compares the published one
+ * byte for byte.  0 on success: *srs malloc'd (release with Free); -2: L out of range, the outputs NULL / 0. */
+extern int gsc_srs_initial(int L, void **srs, size_t *len);
+/* One contribution.  Draws tau', alpha', beta' in [1, r) and three Schnorr nonces from the OS CSPRNG and writes a file of the same L with
+ * tauG1'[i] = tau'^i tauG1[i] (i <= 2N-2), tauG2'[i] = tau'^i tauG2[i], alphaG1'[i] = alpha' tau'^i alphaG1[i], betaG1'[i] = beta' tau'^i betaG1[i]
+ * (i < N), betaG2' = beta' betaG2, every element raw.  The input gets rule 1 of gsc_srs_verify (the walk, and every element decoded on the
+ * device); the powers are computed on the device and every element is multiplied by its own in a ladder that does not branch on the scalar.
+ * The record (GSC_SRS_CONTRIBUTION_BYTES, this project's own format, like the phase-2 record): SHA-256(prev) | SHA-256(next) | then for
+ * s = tau, alpha, beta: new_s raw (64; next's tauG1[1] / alphaG1[0] / betaG1[0]) | T_s = k_s base_s raw (64; base_s: prev's element) |
+ * z_s = k_s + c_s s' mod r, big-endian (32); c_s = the first 31 bytes, as a big-endian integer, of SHA-256("gsc-phase1-v1" | one byte 0 / 1 / 2
+ * for tau / alpha / beta | SHA-256(prev) | base_s raw | new_s raw | T_s raw): three Schnorr proofs that the contributor knows its secrets.
+ * With seed32 (TEST HOOKS only) s' = SHA-256("gsc-phase1-tau" | seed32) mod r (and "-alpha", "-beta"), k_s = SHA-256("gsc-phase1-k-tau" |
+ * seed32) mod r (likewise).
+ * 0 on success: *srs_out malloc'd (release with Free), record filled.  -1: a seed given without test hooks (before a device is asked for);
+ * -2: a refused file (one line on stdout names the element) or a seed that gives a zero scalar; -3: device error.  On failure the outputs
+ * are NULL / 0, the record is zeroed, nothing stays allocated. */
+#define GSC_SRS_CONTRIBUTION_BYTES 544
+extern int gsc_srs_contribute(GoSlice srs, const uint8_t *seed32, void **srs_out, size_t *len, uint8_t record[GSC_SRS_CONTRIBUTION_BYTES]);
+/* One link (prev, next, record) is accepted iff (1) both files pass the host walk (magic, L, length, raw finite elements) with the same L, and
+ * prev's tauG1[1], alphaG1[0], betaG1[0] decode; (2) SHA-256(prev) and SHA-256(next) are the record's; (3) the record's three new elements are
+ * next's tauG1[1], alphaG1[0], betaG1[0]; (4) for s = tau, alpha, beta: z_s < r, T_s a finite raw G1 point, z_s base_s == T_s + c_s new_s (the
+ * line names s); (5) next passes all of gsc_srs_verify, rules 1-7 (the line carries the inner rule: "rule 5: next: rule 3: ...").  Rules 4
+ * and 5 together: next holds the powers of (tau tau', alpha alpha', beta beta') with tau', alpha', beta' known to the contributor.
+ * PREV IS DELIBERATELY NOT CHECKED IN FULL: a chain is verified from the bytes of gsc_srs_initial(L), link by link, and each prev is the next
+ * of the link before it (which rule 5 checked); a verifier who starts in the middle runs gsc_srs_verify on its first prev itself.
+ * 1 accepted, 0 refused (one line on stdout, "gsc_srs_verify_contribution: rule k: ...", naming the first rule that failed), -3 device error. */
+extern int gsc_srs_verify_contribution(GoSlice prev, GoSlice next, const uint8_t record[GSC_SRS_CONTRIBUTION_BYTES]);
+/* TEST HOOK: out[i] = m x^(first + i) pts[i] through the kernels and the launcher a contribution uses (k_fr_powers, the per-point ladder).
+ * Conventions and refusals as gsc_debug_scale_points; x_be32, m_be32 < r.  0 on success, -1 on error / hooks disabled. */
+extern int gsc_debug_scale_powers(int group, const uint8_t *pts, const uint8_t *inf, size_t n, const uint8_t *x_be32, const uint8_t *m_be32,
+                                  uint64_t first, uint8_t *out, uint8_t *out_inf);
 /* Groth16 Setup from a powers file: an ordinary gnark pk / vk (compressed points) for the R1CS, made from the file's group elements alone — no
  * tau, alpha or beta is known to this call.  The Lagrange bases at tau, the column sums A_i(tau), B_i(tau), K_i and the Z_k are computed in the
  * groups, on the device.  The call first runs gsc_srs_verify's whole check on the file.  A larger file serves a smaller circuit: with

@@ -14,9 +14,18 @@ on; anyone checks every link with the published records before the final pair is
   python tools/gsc_keygen.py --verify-contribution PREV_PK PREV_VK NEXT_PK NEXT_VK RECORD
       prints ACCEPTED (exit status 0) or REFUSED (exit status 1; the library's line above it names the rule that failed)
 
-Key ceremony, first phase: a key whose tau, alpha and beta nobody knows starts from a powers file (this project's own
-format, include/libprove.h — not snarkjs' .ptau, not gnark's mpcsetup).
+Key ceremony, first phase: a key whose tau, alpha and beta nobody knows starts from a powers file (this project's
+own format, include/libprove.h — not snarkjs' .ptau, not gnark's mpcsetup).  The file starts at tau = alpha = beta = 1 and every party
+multiplies the scalars by secrets of its own; anyone checks every link, from the starting file on, with the published records.
 
+  python tools/gsc_keygen.py --srs-initial L OUT
+      writes the starting file for N = 2^L (no GPU needed; deterministic: a verifier makes it itself and compares)
+  python tools/gsc_keygen.py --srs-contribute SRS --out-dir D
+      writes D/<name of SRS> and D/srs_contribution.record (544 bytes); the secrets come from the OS CSPRNG and are gone when the command
+      returns
+  python tools/gsc_keygen.py --verify-srs-contribution PREV NEXT RECORD
+      prints ACCEPTED (exit status 0) or REFUSED (exit status 1; the library's line above it names the rule that failed).  PREV is not
+      checked in full: verify a chain from --srs-initial's file, link by link
   python tools/gsc_keygen.py --verify-srs SRS
       prints ACCEPTED (exit status 0) or REFUSED (exit status 1; the library's line above it names the rule that failed)
   python tools/gsc_keygen.py --from-srs SRS R1CS PK VK
@@ -64,6 +73,36 @@ def verify_srs(g, args):
     raise SystemExit(0 if ok else 1)
 
 
+def srs_initial(g, args):
+    if len(args) != 2:
+        raise SystemExit(__doc__)
+    srs = g.srs_initial(int(args[0]))
+    open(args[1], "wb").write(srs)
+    print("srs %d bytes -> %s" % (len(srs), args[1]))
+
+
+def srs_contribute(g, args):
+    if len(args) != 3 or args[1] != "--out-dir":
+        raise SystemExit(__doc__)
+    path, out = args[0], args[2]
+    name = os.path.basename(path)[:-3] if path.endswith(".xz") else os.path.basename(path)
+    if os.path.isdir(out) and os.path.abspath(os.path.join(out, name)) == os.path.abspath(path):
+        raise SystemExit("--out-dir holds the input file: choose another directory")
+    srs, record = g.srs_contribute(_read(path))
+    os.makedirs(out, exist_ok=True)
+    for n, b in ((name, srs), ("srs_contribution.record", record)):
+        open(os.path.join(out, n), "wb").write(b)
+    print("srs %d bytes, record %d bytes -> %s" % (len(srs), len(record), out))
+
+
+def verify_srs_contribution(g, args):
+    if len(args) != 3:
+        raise SystemExit(__doc__)
+    ok = g.srs_verify_contribution(*[_read(p) for p in args])
+    print("ACCEPTED" if ok else "REFUSED")
+    raise SystemExit(0 if ok else 1)
+
+
 def from_srs(g, args):
     if len(args) != 4:
         raise SystemExit(__doc__)
@@ -77,6 +116,12 @@ def main():
     import gsc_loader
     if len(sys.argv) > 1 and sys.argv[1] == "--verify-srs":
         return verify_srs(gsc_loader.load(), sys.argv[2:])
+    if len(sys.argv) > 1 and sys.argv[1] == "--srs-initial":
+        return srs_initial(gsc_loader.load(), sys.argv[2:])
+    if len(sys.argv) > 1 and sys.argv[1] == "--srs-contribute":
+        return srs_contribute(gsc_loader.load(), sys.argv[2:])
+    if len(sys.argv) > 1 and sys.argv[1] == "--verify-srs-contribution":
+        return verify_srs_contribution(gsc_loader.load(), sys.argv[2:])
     if len(sys.argv) > 1 and sys.argv[1] == "--from-srs":
         return from_srs(gsc_loader.load(), sys.argv[2:])
     if len(sys.argv) > 1 and sys.argv[1] == "--contribute":
