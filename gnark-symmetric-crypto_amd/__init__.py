@@ -28,7 +28,7 @@ EXPORTS = ["enforce_binding", "InitAlgorithm", "Free", "Prove", "ProveBatch", "g
            "gsc_prove_check_init", "gsc_prove_check_stats", "gsc_debug_prove_corrupt",
            "gsc_release_algorithm", "gsc_replace_algorithm", "gsc_memory_info", "gsc_key_generation",
            "gsc_setup_contribute", "gsc_setup_verify_contribution", "gsc_debug_scale_points",
-           "gsc_srs_verify", "gsc_debug_srs_generate", "gsc_debug_group_idft", "gsc_debug_column_sums", "gsc_setup_from_srs", "gsc_debug_msm", "gsc_debug_solve", "gsc_debug_assemble",
+           "gsc_srs_verify", "gsc_debug_srs_generate", "gsc_debug_group_idft", "gsc_debug_column_sums", "gsc_setup_from_srs", "gsc_debug_msm", "gsc_debug_solve", "gsc_debug_assemble", "gsc_debug_quotient",
            "gsc_srs_initial", "gsc_srs_contribute", "gsc_srs_verify_contribution", "gsc_debug_scale_powers"]
 
 
@@ -73,6 +73,12 @@ class DebugAssembleArgs(C.Structure):      # struct gsc_debug_assemble_args of i
                [(s + part, C.c_char_p) for s in _ASSEMBLE_SETS for part in ("_pts", "_inf", "_lam")] + \
                [("rs", C.c_char_p), ("mask", C.c_char_p), ("glv_in", C.c_char_p)] + \
                [(n, C.c_void_p) for n in ("out", "flags", "tmp", "tmp_inf", "cpts", "commit", "W", "mask_out", "glv")]
+
+
+class DebugQuotientArgs(C.Structure):      # struct gsc_debug_quotient_args of include/libprove.h
+    _fields_ = [("algorithm", C.c_uint32), ("plain", C.c_int32), ("c", C.c_int32),
+                ("mats_be", C.c_void_p), ("m", C.c_size_t), ("planes", C.c_void_p),
+                ("ncols", C.c_size_t), ("live", C.c_size_t), ("out", C.c_void_p), ("cap", C.c_size_t)]
 
 
 class ProveReturn(C.Structure):
@@ -196,6 +202,8 @@ def lib():
         L.gsc_debug_solve.argtypes = [C.POINTER(DebugSolveArgs)]
         L.gsc_debug_assemble.restype = C.c_int
         L.gsc_debug_assemble.argtypes = [C.POINTER(DebugAssembleArgs)]
+        L.gsc_debug_quotient.restype = C.c_longlong
+        L.gsc_debug_quotient.argtypes = [C.POINTER(DebugQuotientArgs)]
         L.gsc_debug_column_sums.restype = C.c_int
         L.gsc_debug_column_sums.argtypes = [C.c_int, C.c_uint32, C.c_char_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_char_p, C.c_void_p, C.c_void_p]
         L.enforce_binding()
@@ -809,6 +817,36 @@ def debug_compute_d(algorithm_id: int, ab_be: bytes, m: int) -> bytes:
     out = C.create_string_buffer(n * 64 * 32)
     if L.gsc_debug_compute_d(algorithm_id, ab_be, m, out, len(out)) != n:
         raise RuntimeError("gsc_debug_compute_d failed")
+    return out.raw
+
+
+def debug_quotient(algorithm_id: int, ab_be, m: int, planes=None, plain: int = 0, ncols: int = 0, live: int = 0, c: int = 0) -> bytes:
+    """TEST HOOK: the evaluation-form quotient kernels on the routes of a batch call; see gsc_debug_quotient in include/libprove.h.  ab_be: a | b,
+    [m][64] big-endian each, m up to the domain size n; planes: None or the int8 planes of a | b, [n][64] each (bytes, or anything with the buffer
+    protocol).  Returns the raw output: [n][64] little-endian d for c = 0, the digit buffer for c > 0."""
+    L = lib()
+    n = L.gsc_debug_quotient(C.byref(DebugQuotientArgs(algorithm=algorithm_id)))
+    if n <= 0:
+        raise RuntimeError("algorithm not initialised")
+    ab_be = memoryview(ab_be).cast("B")
+    assert len(ab_be) == 2 * m * 64 * 32
+    def held(view):      # a ctypes array over the caller's bytes (copied only when they are read-only); m = 0 has none: one spare byte to point at
+        return C.create_string_buffer(1) if not len(view) else (C.c_char * len(view)).from_buffer_copy(view) if view.readonly else (C.c_char * len(view)).from_buffer(view)
+    keep = [held(ab_be)]
+    if planes is not None:
+        planes = memoryview(planes).cast("B")
+        assert len(planes) == 2 * n * 64
+        keep.append(held(planes))
+    nwin = 0
+    if c:
+        nwin = (254 + c - 1) // c
+        if (0x30644e72e131a029b85045b68181585d2833e84879b9709143e1f593f0000001 >> (c * (nwin - 1))) + 1 > (1 << (c - 1)) - 1:      # msm_windows (csrc/kernels.hpp): the top window absorbs the last carry
+            nwin += 1
+    out = C.create_string_buffer(nwin * (n // 8) * 64 * (32 if c > 16 else 16) if c else n * 64 * 32)
+    args = DebugQuotientArgs(algorithm=algorithm_id, plain=plain, c=c, mats_be=C.addressof(keep[0]), m=m,
+                             planes=C.addressof(keep[1]) if planes is not None else None, ncols=ncols, live=live, out=C.addressof(out), cap=len(out))
+    if L.gsc_debug_quotient(C.byref(args)) != n:
+        raise RuntimeError("gsc_debug_quotient failed (see stdout)")
     return out.raw
 
 

@@ -709,6 +709,15 @@ long long gsc_debug_compute_d(GoUint8 algorithmID, const uint8_t* ab_be, size_t 
     try { a->debug_compute_d(ab_be, m, d_out); return (long long)a->domain_size(); }
     catch (const std::exception& e) { printf("%s\n", e.what()); return -1; }
 }
+long long gsc_debug_quotient(const gsc_debug_quotient_args* args) {
+    if (hooks_refused("gsc_debug_quotient") || !args || args->algorithm > 2) return -1;
+    const Snapshot snap = snapshot((GoUint8)args->algorithm); Algorithm* a = algo_of(snap); if (!a) return -1;
+    if (!args->out) return (long long)a->domain_size();
+    try {
+        a->debug_quotient_routes(args->mats_be, args->m, args->planes, args->plain, args->ncols, args->live, args->c, args->out, args->cap);
+        return (long long)a->domain_size();
+    } catch (const std::exception& e) { printf("%s\n", e.what()); return -1; }
+}
 int gsc_debug_z_sum(GoUint8 algorithmID, const uint8_t* abc_be, size_t m, uint8_t* out, uint8_t* flags) {
     if (hooks_refused("gsc_debug_z_sum") || algorithmID > 2 || !abc_be || !out || !flags) return -1;
     const Snapshot snap = snapshot(algorithmID); Algorithm* a = algo_of(snap); if (!a) return -1;

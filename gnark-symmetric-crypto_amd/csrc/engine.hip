@@ -318,11 +318,12 @@ std::string Algorithm::describe() const {
     return out;
 }
 size_t Algorithm::domain_size() const { return impls_[0]->domain_n; }
-// The set-up the two quotient test hooks share: `mats` matrices [m][64] of canonical big-endian values into A, B (, C) of the first lane,
-// `quot(plan, lane, columns)` on them, A back to the host (out != nullptr).
+// The set-up the quotient test hooks share: `mats` matrices [m][64] of canonical big-endian values into A, B (, C) of the first lane,
+// `quot(plan, lane, columns)` on them, A back to the host (out != nullptr).  The plan is the one stage_quotient builds (the plain-integer tables included:
+// they are read only where a launch passes byte planes with NttNarrow::plain).  m_max: the rows a hook admits.
 template <class Quot>
-static void debug_quotient(AlgorithmImpl& a, const char* who, const uint8_t* mats_be, size_t mats, size_t m, uint8_t* out, Quot quot) {
-    if (m > a.n_constraints) throw std::runtime_error(std::string(who) + ": more rows than constraints");
+static void debug_quotient(AlgorithmImpl& a, const char* who, const uint8_t* mats_be, size_t mats, size_t m, size_t m_max, uint8_t* out, Quot quot) {
+    if (m > m_max) throw std::runtime_error(std::string(who) + (m_max == a.n_constraints ? ": more rows than constraints" : ": more rows than the domain has"));
     HIP_CHECK(hipSetDevice(a.cfg.device));
     struct Hold { AlgorithmImpl& a; size_t i; ~Hold() { a.release_lane(i); } } hold{a, a.acquire_lane(0)};
     AlgorithmImpl::Lane& ln = *a.lanes[0];
@@ -331,24 +332,57 @@ static void debug_quotient(AlgorithmImpl& a, const char* who, const uint8_t* mat
     d_be.upload(mats_be, mats * cnt * 32, ln.stream);
     fe* const dst[3] = {ln.d_A.p, ln.d_B.p, ln.d_C.p};
     for (size_t k = 0; k < mats; k++) launch_fr_from_be(d_be.p + k * cnt * 32, dst[k], cnt, ln.stream);
-    NttPlan plan{a.L, a.tw_fwd.p, a.tw_inv.p, a.scale_mid.p, a.scale_out.p, a.dom.p + 5, a.qr.p};
+    NttPlan plan{a.L, a.tw_fwd.p, a.tw_inv.p, a.scale_mid.p, a.scale_out.p, a.dom.p + 5, a.qr.p, nullptr, a.tw_inv_plain.p, a.scale_mid_plain.p};
     HIP_CHECK(quot(plan, ln, B));
     if (out) HIP_CHECK(hipMemcpyAsync(out, ln.d_A.p, a.domain_n * B * 32, hipMemcpyDeviceToHost, ln.stream));
     if (!a.cfg.keep_secrets && a.cfg.wipe_full) a.wipe_whole(ln, ln.stream);      // the hook's vectors are a caller's data like any other
     HIP_CHECK(hipStreamSynchronize(ln.stream));
 }
 void Algorithm::debug_compute_h(const uint8_t* abc_be, size_t m, uint8_t* h_out) {
-    debug_quotient(*impls_[0], "debug_compute_h", abc_be, 3, m, h_out, [m](const NttPlan& plan, AlgorithmImpl::Lane& ln, size_t B) { return launch_compute_h(plan, ln.d_A.p, ln.d_B.p, ln.d_C.p, m, B, ln.stream); });
+    debug_quotient(*impls_[0], "debug_compute_h", abc_be, 3, m, impls_[0]->n_constraints, h_out, [m](const NttPlan& plan, AlgorithmImpl::Lane& ln, size_t B) { return launch_compute_h(plan, ln.d_A.p, ln.d_B.p, ln.d_C.p, m, B, ln.stream); });
 }
 void Algorithm::debug_compute_d(const uint8_t* ab_be, size_t m, uint8_t* d_out) {
-    debug_quotient(*impls_[0], "debug_compute_d", ab_be, 2, m, d_out, [m](const NttPlan& plan, AlgorithmImpl::Lane& ln, size_t B) { return launch_compute_d(plan, ln.d_A.p, ln.d_B.p, m, B, ln.stream); });
+    debug_quotient(*impls_[0], "debug_compute_d", ab_be, 2, m, impls_[0]->n_constraints, d_out, [m](const NttPlan& plan, AlgorithmImpl::Lane& ln, size_t B) { return launch_compute_d(plan, ln.d_A.p, ln.d_B.p, m, B, ln.stream); });
+}
+size_t Algorithm::debug_quotient_routes_bytes(int c) const {
+    const size_t n = impls_[0]->domain_n;
+    return c ? (size_t)msm_windows(c) * (n / 8) * 64 * msm_digit_words(c) * sizeof(uint4) : n * 64 * sizeof(fe);
+}
+void Algorithm::debug_quotient_routes(const uint8_t* ab_be, size_t m, const int8_t* planes, int plain, size_t ncols, size_t live, int c, uint8_t* out, size_t cap) {
+    AlgorithmImpl& a = *impls_[0];
+    const size_t n = a.domain_n, B = 64;
+    const auto refuse = [](const char* why) { throw std::runtime_error(std::string("gsc_debug_quotient: ") + why); };
+    if (!ab_be || !out) refuse("a missing buffer");
+    if (plain != 0 && plain != 1) refuse("plain is 0 or 1");
+    if (c != 0 && (c < 4 || c > MSM_MAX_WINDOW)) refuse("c is 0 or in [4, 17]");
+    if (ncols > B || (c && ncols)) refuse("ncols above 64, or ncols with digits (whole batches only)");
+    if (live > n) refuse("more live positions than the domain has");
+    if (m > n) refuse("more rows than the domain has");
+    if (cap < debug_quotient_routes_bytes(c)) refuse("too small an output buffer");
+    if (planes) for (size_t k = 0; k < 2; k++) for (size_t i = 0; i < m * B; i++) { const int8_t t = planes[k * n * B + i]; if (t != 0 && t != 1 && t != -1 && t != WS_PLANE_WIDE) refuse("a plane entry below row m that is not 0, 1, -1 or -128"); }
+    HIP_CHECK(hipSetDevice(a.cfg.device));
+    DevBuf<int8_t> d_planes(planes ? 2 * n * B : 0, true);
+    DevBuf<uint4> d_digits(c ? debug_quotient_routes_bytes(c) / sizeof(uint4) : 0, true);
+    debug_quotient(a, "gsc_debug_quotient", ab_be, 2, m, n, c ? nullptr : out, [&](const NttPlan& plan, AlgorithmImpl::Lane& ln, size_t) {
+        // rows m .. n - 1 of a and b are nobody's: the kernels must not read them
+        for (fe* mat : {ln.d_A.p, ln.d_B.p}) if (m < n) HIP_CHECK(hipMemsetAsync(mat + m * B, 0xFF, (n - m) * B * sizeof(fe), ln.stream));
+        if (planes) d_planes.upload(planes, 2 * n * B, ln.stream);
+        // crows = n: one group of 64 columns.  Without planes the pointers are null and `plain` still travels as given: clearing it is launch_quotient's rule
+        const NttNarrow nr{{d_planes.p, planes ? d_planes.p + n * B : nullptr, nullptr}, n, plain};
+        const NttNarrow* narrow = &nr;
+        if (!c) return launch_compute_d(plan, ln.d_A.p, ln.d_B.p, m, B, ln.stream, ncols, narrow, live);
+        HIP_CHECK(hipMemsetAsync(d_digits.p, 0, d_digits.bytes(), ln.stream));      // (live: the words of the other positions are not written)
+        HIP_CHECK(launch_compute_d_digits(plan, ln.d_A.p, ln.d_B.p, m, B, QuotDigits{d_digits.p, c, msm_windows(c)}, ln.stream, narrow, live));
+        HIP_CHECK(hipMemcpyAsync(out, d_digits.p, d_digits.bytes(), hipMemcpyDeviceToHost, ln.stream));
+        return hipGetLastError();
+    });
 }
 void Algorithm::debug_z_sum(const uint8_t* abc_be, size_t m, uint8_t* out, uint8_t* flags) {
     AlgorithmImpl& a = *impls_[0];
     if (!a.quotient_eval) throw std::runtime_error("debug_z_sum: the engine holds the coefficient form");
     HIP_CHECK(hipSetDevice(a.cfg.device));
     DevBuf<uint8_t> d_out(64 * 64), d_flags(64);
-    debug_quotient(a, "debug_z_sum", abc_be, 3, m, nullptr, [&](const NttPlan& plan, AlgorithmImpl::Lane& ln, size_t B) {
+    debug_quotient(a, "debug_z_sum", abc_be, 3, m, a.n_constraints, nullptr, [&](const NttPlan& plan, AlgorithmImpl::Lane& ln, size_t B) {
         AlgorithmImpl::Chunk ck{nullptr, B, B, nullptr, chunk_route(B, a.cfg, a.route_facts(), RouteCall{}), {}, {}, {}};
         ln.small_active = false;
         // rows m .. n - 1 of a, b, c (and the padding row of c) are zero in this call

@@ -129,6 +129,12 @@ class Algorithm {
     // d_out: [domain][64] little-endian canonical values, row i = A(zeta w^i) B(zeta w^i) * 2^261 mod r (natural order).
     void debug_compute_d(const uint8_t* ab_be, size_t m, uint8_t* d_out);
     size_t domain_size() const;
+    // TEST HOOK (gsc_debug_quotient, include/libprove.h): the evaluation-form quotient kernels on the routes a batch call takes.  ab_be as above with
+    // m <= domain size; planes: nullptr, or the byte planes of a and b, [domain][64] each, uploaded into buffers of the hook's own; plain, ncols, live: passed
+    // on to the launcher.  c = 0: launch_compute_d, out = A, [domain][64] little-endian values; c > 0: launch_compute_d_digits into a digit buffer of
+    // the hook's own, out = that buffer.  out (cap bytes) takes debug_quotient_routes_bytes(c) bytes.
+    void debug_quotient_routes(const uint8_t* ab_be, size_t m, const int8_t* planes, int plain, size_t ncols, size_t live, int c, uint8_t* out, size_t cap);
+    size_t debug_quotient_routes_bytes(int c) const;
     // TEST HOOK: the evaluation-form quotient sum sum_i c_i U_i + sum_i d_i V_i of 64 columns through the batch kernels, whatever sets init_key built.
     // abc_be: a, b, c = a b row by row, [m][64] canonical big-endian values.  out: 64 x 64 B big-endian canonical X | Y, flags[i] = 1: infinity.
     void debug_z_sum(const uint8_t* abc_be, size_t m, uint8_t* out, uint8_t* flags);

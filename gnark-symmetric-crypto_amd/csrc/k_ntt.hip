@@ -153,10 +153,19 @@ __device__ __forceinline__ void dif_round4(const Tile& t, uint32_t u4, uint32_t 
         t.put(e1, q, r1); t.put(e3, q, r3);
     }
 }
-// DIF stages s0 .. s1-1 on a tile of E elements.  `d` = doublings of the sum path since its last range reduction (on entry: d0 <= 1);
-// a round that would leave more than four of them reduces instead (values stay below 32 r, products need < 111 r).
-template <bool STRIDED>
+// DIF stages s0 .. s1-1 on a tile of E elements.  `d` = doublings of the sum path since its last range reduction, counted from a reduced value
+// (|value| <= 2.001 r): the tile holds |value| <= 2 r * 2^d.  On entry d0 <= 2, and these are the callers:
+//   d0 = 0  fresh loads of the memory image, [0, 2.001 r) (K2, K4), or canonical rows (K1's generic and narrow9 routes);
+//   d0 = 1  K3's coefficient-form ending: the first stage ran in registers on two products, (-3.2 r, 5.2 r);
+//   d0 = 2  K1's plain-integer route: two stages ran in registers.  The sum path holds a0 + a1, four plane integers (|value| <= 4) or, in the mixed
+//           branch, four values of [0, r] (a wide row x < 2^256 enters as x * 32 / 2^261 in [0, r]): at most 4 r; the other elements lie in (-2 r, 4 r).
+// A left-over single stage runs first, unreduced (d + 1).  A round entered with d >= 1 reduces and one entered with d = 0 does not (d = 2 behind it), so
+// no round is entered above d = 3, and inside a round two more doublings happen before the carry or the product.  The largest value a product or
+// reduce_top() ever takes is therefore 2 r * 2^(3 + 2) = 64 r: d0 = 2 with an odd stage count (Lhi = 9, the 2^17 domain; 32 r from the magnitudes K1 really
+// has there), 41.6 r from K3 (Lhi = 8).  Products need < 111 r, reduce_top() |q| <= NTT_QMAX.  tests/test_gpu_quot_routes.py runs the d0 = 2 entry at its
+// largest magnitudes (every row wide and r-1) at L = 15 and L = 17.
 // Returns true when the last round reduced every entry it wrote (values in (-1.001 r, 2.001 r)): the caller's store can then skip its own range reduction.
+template <bool STRIDED>
 __device__ __forceinline__ bool dif_run(const Tile& t, uint32_t u4, uint32_t q, int s0, int s1, int d0, int L, int Llo, uint32_t tile_id, const NttPlan& pl, uint32_t E) {
     int s = s0, d = d0; bool last_reduced = false;
     auto half_of = [&](int st) { const uint32_t hg = 1u << (L - 1 - st); return STRIDED ? hg >> Llo : hg; };

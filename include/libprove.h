@@ -515,6 +515,33 @@ struct gsc_debug_assemble_args {
     uint8_t *out, *flags, *tmp, *tmp_inf, *cpts, *commit, *W, *mask_out, *glv;
 };
 extern int gsc_debug_assemble(const struct gsc_debug_assemble_args *args);
+/* TEST HOOK: the evaluation-form quotient kernels alone on the routes a batch call takes (csrc/k_ntt.hip: byte planes with and without the
+ * plain-integer first stages, the digits recoded inside the last kernel, a few columns, live tiles), 64 independent columns, on the first lane of
+ * a loaded algorithm and with that algorithm's own transform tables, the plain-integer ones included.
+ *   algorithm: 0 .. 2, initialised;  mats_be: a, then b, each [m][64] canonical big-endian 32-byte values;  m: rows, up to the DOMAIN size n (rows
+ *   m .. n-1 count as zero: the hook fills them with 0xFF bytes, the kernels must not read them);
+ *   planes: NULL, or the byte planes of a and then b, [n][64] each: an entry 0, 1 or -1 stands for that value, -128 says the row's value is the
+ *   one in mats_be; rows >= m may hold anything.  Where an entry is not -128 the value in mats_be is not read;
+ *   plain: 0 or 1, handed to the launcher as NttNarrow::plain unchanged, with planes or (null plane pointers) without: launch_quotient itself clears
+ *   it where its rule says so, e.g. without both planes, and the call then takes the generic route;
+ *   ncols: 0 = every column, else only the first ncols columns (rounded up to 4) are transformed, c = 0 only;
+ *   live: 0 = every table position, else only the positions below live are produced (kernels.hpp quot_live_tiles), the rest of out is leftovers
+ *   (c = 0) or zero (c > 0);
+ *   c: 0 = launch_compute_d, out = [n][64] canonical little-endian values, row i = A(zeta w^i) B(zeta w^i) 2^261 mod r;
+ *      4 .. 17 = launch_compute_d_digits with msm_windows(c) windows into a buffer of the hook's own, out = that buffer as the kernel wrote it:
+ *      16-byte words, word (j * n/8 + octet) * 64 + column (c = 17: two words, at twice that index) holds the digits of window j of the table
+ *      positions 8 octet .. 8 octet + 7 (position t = index quot_digit_index(L, t)) as int16 (c = 17: int32);
+ *   out / cap: the output and its capacity in bytes: n * 64 * 32 for c = 0, windows * n/8 * 64 * 16 (c = 17: * 32) otherwise.
+ * Returns the domain size n (also with out == NULL: size query); -1 (one line on stdout) for hooks disabled, an algorithm that is not loaded,
+ * m or live above n, ncols above 64 or with c > 0, c or plain outside the above, a plane entry below row m that is none of the four, too small a cap. */
+struct gsc_debug_quotient_args {
+    uint32_t algorithm; int32_t plain, c;
+    const uint8_t *mats_be; size_t m;
+    const int8_t *planes;
+    size_t ncols, live;
+    uint8_t *out; size_t cap;
+};
+extern long long gsc_debug_quotient(const struct gsc_debug_quotient_args *args);
 /* TEST HOOK: the witness solver kernels alone, on a caller's constraint system: a device, but no key and no InitAlgorithm.  The description is an
  * R1CS file given field by field, exactly what the parser would have produced; the tables are built and uploaded by the functions InitAlgorithm
  * uses (csrc/solver_tables.hpp: build_solver_program, build_few_program, the count tables' device check, coeff / coeff_inv, build_small_program) and

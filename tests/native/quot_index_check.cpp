@@ -4,9 +4,21 @@
 // them as the bases 4 m + kq, m = g * G/4 + u4.
 #include "../../gnark-symmetric-crypto_amd/csrc/kernels.hpp"
 #include <cstdio>
+#include <string>
 #include <vector>
 
-int main() {
+int main(int argc, char** argv) {
+    // "dump": the kernel's own arithmetic as lines "L position index quot_digit_index(L, position)" at a stride of table positions, for tests/test_quot_routes_model_host.py
+    if (argc > 1 && std::string(argv[1]) == "dump") {
+        for (int L = gsc::NTT_MIN_LOG2; L <= gsc::NTT_MAX_LOG2; L++) {
+            const int Lhi = (L + 1) / 2, Llo = L - Lhi; const uint32_t G = 1u << Lhi;
+            for (uint32_t t = 0; t < (1u << L); t += (t < 1024 ? 1 : 37)) {
+                const uint32_t m = t >> 2, kq = t & 3, g = m / (G / 4), u4 = m % (G / 4);
+                printf("%d %u %u %u\n", L, t, ((u4 + kq * (G / 4)) << Llo) + g, gsc::quot_digit_index(L, t));
+            }
+        }
+        return 0;
+    }
     for (int L = gsc::NTT_MIN_LOG2; L <= gsc::NTT_MAX_LOG2; L++) {
         const uint32_t n = 1u << L; const int Lhi = (L + 1) / 2, Llo = L - Lhi; const uint32_t G = 1u << Lhi, Cn = 1u << Llo;
         std::vector<uint8_t> seen(n, 0);

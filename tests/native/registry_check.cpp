@@ -47,13 +47,15 @@ static auto no_retire = [](StubServed&) {};
 
 // one call as capi.cpp makes it: a snapshot at entry, the proof through the micro-batcher (direct = false) or straight on the engine.
 // Returns the key that served it, 0 for "not initialised".
-static int call(Reg& reg, size_t id, bool direct, std::atomic<int>* entered = nullptr) {
+// served (optional) counts the call as through BEFORE its snapshot is given back: a release that has drained the engine has seen every such count.
+static int call(Reg& reg, size_t id, bool direct, std::atomic<int>* entered = nullptr, std::atomic<int>* served = nullptr) {
     Reg::Ref snap = reg.snapshot(id);
     if (entered) (*entered)++;
     if (!snap) return 0;
     ProofRequest req{}; ProofResult res;
     if (direct) snap->algo->prove_batch(&req, 1, &res, nullptr, false);
     else snap->batcher->submit(req, res);
+    if (served) (*served)++;
     return res.proof[0];
 }
 
@@ -64,7 +66,7 @@ int main() {
         std::atomic<int> entered{0}, done{0}, wrong{0};
         std::vector<std::thread> th;
         // 2 straight on the engine, 6 through the batcher: its two workers take a batch each, the callers that arrive under them stay parked
-        for (int i = 0; i < 8; i++) th.emplace_back([&, i] { if (call(reg, 0, i < 2, &entered) != 1) wrong++; done++; });
+        for (int i = 0; i < 8; i++) th.emplace_back([&, i] { if (call(reg, 0, i < 2, &entered, &done) != 1) wrong++; });
         while (entered.load() < 8) sleep_ms(1);
         sleep_ms(5);
         int done_at_retire = -1;
