@@ -28,6 +28,7 @@ EXPORTS = ["enforce_binding", "InitAlgorithm", "Free", "Prove", "ProveBatch", "g
            "gsc_prove_check_init", "gsc_prove_check_stats", "gsc_debug_prove_corrupt",
            "gsc_release_algorithm", "gsc_replace_algorithm", "gsc_memory_info", "gsc_key_generation",
            "gsc_setup_contribute", "gsc_setup_verify_contribution", "gsc_debug_scale_points",
+           "gsc_pedersen_verify", "gsc_setup_contribute_sigma", "gsc_setup_verify_sigma_contribution", "gsc_setup_verify_from_srs",
            "gsc_srs_verify", "gsc_debug_srs_generate", "gsc_debug_group_idft", "gsc_debug_column_sums", "gsc_setup_from_srs", "gsc_debug_msm", "gsc_debug_solve", "gsc_debug_assemble", "gsc_debug_quotient",
            "gsc_srs_initial", "gsc_srs_contribute", "gsc_srs_verify_contribution", "gsc_debug_scale_powers"]
 
@@ -180,6 +181,14 @@ def lib():
         L.gsc_setup_verify_contribution.argtypes = [GoSlice, GoSlice, GoSlice, GoSlice, C.c_char_p]
         L.gsc_debug_scale_points.restype = C.c_int
         L.gsc_debug_scale_points.argtypes = [C.c_int, C.c_char_p, C.c_char_p, C.c_size_t, C.c_char_p, C.c_void_p, C.c_void_p]
+        L.gsc_pedersen_verify.restype = C.c_int
+        L.gsc_pedersen_verify.argtypes = [GoSlice, GoSlice]
+        L.gsc_setup_contribute_sigma.restype = C.c_int
+        L.gsc_setup_contribute_sigma.argtypes = [GoSlice, GoSlice, C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_void_p]
+        L.gsc_setup_verify_sigma_contribution.restype = C.c_int
+        L.gsc_setup_verify_sigma_contribution.argtypes = [GoSlice, GoSlice, GoSlice, GoSlice, C.c_char_p]
+        L.gsc_setup_verify_from_srs.restype = C.c_int
+        L.gsc_setup_verify_from_srs.argtypes = [GoSlice, GoSlice, GoSlice, GoSlice]
         L.gsc_srs_verify.restype = C.c_int
         L.gsc_srs_verify.argtypes = [GoSlice]
         L.gsc_debug_srs_generate.restype = C.c_int
@@ -328,6 +337,60 @@ def setup_verify_contribution(pk_prev: bytes, vk_prev: bytes, pk_next: bytes, vk
     rc = lib().gsc_setup_verify_contribution(keep[0][0], keep[1][0], keep[2][0], keep[3][0], record)
     if rc < 0:
         raise RuntimeError("gsc_setup_verify_contribution: device error (%d)" % rc)
+    return rc == 1
+
+
+SIGMA_CONTRIBUTION_BYTES = 224
+
+
+def pedersen_verify(pk: bytes, vk: bytes) -> bool:
+    """gsc_pedersen_verify: does the pair's one commitment key hold the Pedersen relation e(BasisExpSigma_j, G) e(Basis_j, GSigmaNeg) = 1?  A
+    refusal names its rule on stdout (a pair without a commitment key: rule 1).  Raises RuntimeError on a device error."""
+    s1, k1 = _slice(pk)
+    s2, k2 = _slice(vk)
+    rc = lib().gsc_pedersen_verify(s1, s2)
+    if rc < 0:
+        raise RuntimeError("gsc_pedersen_verify: device error (%d)" % rc)
+    return rc == 1
+
+
+def setup_contribute_sigma(pk: bytes, vk: bytes, seed: bytes = None):
+    """gsc_setup_contribute_sigma: one contribution to the Pedersen sigma of a key pair with a commitment (include/libprove.h) -> (pk', vk',
+    record).  seed (32 bytes) fixes the secrets and needs the test hooks; None = the OS CSPRNG.  Raises RuntimeError with the return code
+    (-1 seed without hooks, -2 refused keys, -3 device error; the reason is on stdout)."""
+    s1, k1 = _slice(pk)
+    s2, k2 = _slice(vk)
+    p, v, np_, nv = C.c_void_p(), C.c_void_p(), C.c_size_t(), C.c_size_t()
+    rec = C.create_string_buffer(SIGMA_CONTRIBUTION_BYTES)
+    rc = lib().gsc_setup_contribute_sigma(s1, s2, seed, C.byref(p), C.byref(np_), C.byref(v), C.byref(nv), rec)
+    if rc != 0:
+        raise RuntimeError("gsc_setup_contribute_sigma failed: %d (see stdout)" % rc)
+    out = C.string_at(p.value, np_.value), C.string_at(v.value, nv.value), rec.raw
+    lib().Free(p); lib().Free(v)
+    return out
+
+
+def setup_verify_sigma_contribution(pk_prev: bytes, vk_prev: bytes, pk_next: bytes, vk_next: bytes, record: bytes) -> bool:
+    """gsc_setup_verify_sigma_contribution: is (pk_next, vk_next) a sigma contribution to (pk_prev, vk_prev) that `record` proves?  prev's own
+    Pedersen relation is not re-checked: a chain starts from a pair that passed pedersen_verify or setup_verify_from_srs.  A refusal names its
+    rule on stdout.  Raises RuntimeError on a device error."""
+    if len(record) != SIGMA_CONTRIBUTION_BYTES:
+        return False
+    keep = [_slice(b) for b in (pk_prev, vk_prev, pk_next, vk_next)]
+    rc = lib().gsc_setup_verify_sigma_contribution(keep[0][0], keep[1][0], keep[2][0], keep[3][0], record)
+    if rc < 0:
+        raise RuntimeError("gsc_setup_verify_sigma_contribution: device error (%d)" % rc)
+    return rc == 1
+
+
+def setup_verify_from_srs(r1cs: bytes, srs: bytes, pk: bytes, vk: bytes) -> bool:
+    """gsc_setup_verify_from_srs: is (pk, vk) what setup_from_srs makes of (r1cs, srs) — byte for byte outside the commitment key's sigma and g,
+    which every run draws afresh, and with the Pedersen relation on those?  A refusal names its rule on stdout.  Raises RuntimeError with the
+    return code (-2 refused r1cs / file / L too small, -3 device error)."""
+    keep = [_slice(b) for b in (r1cs, srs, pk, vk)]
+    rc = lib().gsc_setup_verify_from_srs(keep[0][0], keep[1][0], keep[2][0], keep[3][0])
+    if rc < 0:
+        raise RuntimeError("gsc_setup_verify_from_srs failed: %d (see stdout)" % rc)
     return rc == 1
 
 

@@ -14,6 +14,7 @@
 #include "json.hpp"
 #include "setup.hpp"
 #include "phase2_gpu.hpp"
+#include "sigma_gpu.hpp"
 #include "srs_gpu.hpp"
 #include "srs_contrib.hpp"
 #include "srs_contrib_gpu.hpp"
@@ -545,6 +546,45 @@ int gsc_setup_from_srs(GoSlice r1cs, GoSlice srs, const uint8_t* seed32, void** 
         return 0;
     } catch (const SrsRefused& e) { printf("gsc_setup_from_srs: %s\n", e.what()); return -2; }
     catch (const std::exception& e) { printf("gsc_setup_from_srs: %s\n", e.what()); return -3; }
+}
+int gsc_pedersen_verify(GoSlice pk, GoSlice vk) {
+    if (!pk.data || pk.len <= 0 || !vk.data || vk.len <= 0) { printf("gsc_pedersen_verify: rule 1: empty key\n"); return 0; }
+    try { return pedersen_verify((const uint8_t*)pk.data, (size_t)pk.len, (const uint8_t*)vk.data, (size_t)vk.len); }
+    catch (const std::exception& e) { printf("gsc_pedersen_verify: %s\n", e.what()); return -3; }
+}
+int gsc_setup_contribute_sigma(GoSlice pk, GoSlice vk, const uint8_t* seed32, void** pk_out, size_t* pk_len, void** vk_out, size_t* vk_len, uint8_t* record) {
+    if (!pk_out || !pk_len || !vk_out || !vk_len || !record) return -2;
+    *pk_out = *vk_out = nullptr; *pk_len = *vk_len = 0; memset(record, 0, GSC_SIGMA_CONTRIBUTION_BYTES);
+    if (seed32 && hooks_refused("gsc_setup_contribute_sigma with a caller-supplied seed")) return -1;      // deterministic secrets: test keys only
+    if (!pk.data || pk.len <= 0 || !vk.data || vk.len <= 0) { printf("gsc_setup_contribute_sigma: empty key\n"); return -2; }
+    try {
+        SigmaStep step;
+        const int rc = sigma_contribute((const uint8_t*)pk.data, (size_t)pk.len, (const uint8_t*)vk.data, (size_t)vk.len, seed32, step);
+        if (rc) return rc;
+        void* a = malloc(step.pk.size()); void* b = malloc(step.vk.size());
+        if (!a || !b) { free(a); free(b); return -3; }
+        memcpy(a, step.pk.data(), step.pk.size()); memcpy(b, step.vk.data(), step.vk.size());
+        *pk_out = a; *pk_len = step.pk.size(); *vk_out = b; *vk_len = step.vk.size();
+        memcpy(record, step.record, GSC_SIGMA_CONTRIBUTION_BYTES);
+        return 0;
+    } catch (const std::exception& e) { printf("gsc_setup_contribute_sigma: %s\n", e.what()); return -3; }
+}
+int gsc_setup_verify_sigma_contribution(GoSlice pk_prev, GoSlice vk_prev, GoSlice pk_next, GoSlice vk_next, const uint8_t* record) {
+    for (const GoSlice* k : {&pk_prev, &vk_prev, &pk_next, &vk_next}) if (!k->data || k->len <= 0) { printf("gsc_setup_verify_sigma_contribution: rule 1: empty key\n"); return 0; }
+    if (!record) { printf("gsc_setup_verify_sigma_contribution: rule 3: no record\n"); return 0; }
+    try {
+        return sigma_verify((const uint8_t*)pk_prev.data, (size_t)pk_prev.len, (const uint8_t*)vk_prev.data, (size_t)vk_prev.len,
+                            (const uint8_t*)pk_next.data, (size_t)pk_next.len, (const uint8_t*)vk_next.data, (size_t)vk_next.len, record);
+    } catch (const std::exception& e) { printf("gsc_setup_verify_sigma_contribution: %s\n", e.what()); return -3; }
+}
+int gsc_setup_verify_from_srs(GoSlice r1cs, GoSlice srs, GoSlice pk, GoSlice vk) {
+    if (!r1cs.data || r1cs.len <= 0 || !srs.data || srs.len <= 0) { printf("gsc_setup_verify_from_srs: empty r1cs or powers file\n"); return -2; }
+    if (!pk.data || pk.len <= 0 || !vk.data || vk.len <= 0) { printf("gsc_setup_verify_from_srs: rule 1: empty key\n"); return 0; }
+    try {
+        return setup_verify_from_srs((const uint8_t*)r1cs.data, (size_t)r1cs.len, (const uint8_t*)srs.data, (size_t)srs.len, (const uint8_t*)pk.data, (size_t)pk.len,
+                                     (const uint8_t*)vk.data, (size_t)vk.len);
+    } catch (const SrsRefused& e) { printf("gsc_setup_verify_from_srs: %s\n", e.what()); return -2; }
+    catch (const std::exception& e) { printf("gsc_setup_verify_from_srs: %s\n", e.what()); return -3; }
 }
 int gsc_debug_group_idft(int group, int L, const uint8_t* pts, uint8_t* out, uint8_t* out_inf) {
     if (hooks_refused("gsc_debug_group_idft") || !pts || !out || !out_inf) return -1;

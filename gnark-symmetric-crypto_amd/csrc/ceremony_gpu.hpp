@@ -6,6 +6,7 @@
 #include "phase2_kernels.hpp"
 #include "verify_kernels.hpp"
 #include "srs.hpp"
+#include "phase2.hpp"
 #include "host_field.hpp"
 #include <sys/random.h>
 #include <cerrno>
@@ -16,6 +17,7 @@
 #include <vector>
 
 int gsc_verify_device_impl();                                                                                        // verify_gpu.cpp
+void gsc_verify_draw_rho_impl(uint32_t* out, size_t n);                                                               // verify_gpu.cpp
 
 namespace gsc {
 namespace cer {
@@ -66,6 +68,8 @@ inline std::vector<uint32_t> random_rho(size_t n) {
     for (size_t i = 0; i < n; i++) while (!(rho[4 * i] | rho[4 * i + 1] | rho[4 * i + 2] | rho[4 * i + 3])) os_random(&rho[4 * i], 16);
     return rho;
 }
+// the same through the verifier's draw_randomizers: the OS CSPRNG unless gsc_debug_verify_randomizers (a test hook) says otherwise
+inline std::vector<uint32_t> verifier_rho(size_t n) { std::vector<uint32_t> rho(4 * n); gsc_verify_draw_rho_impl(rho.data(), n); return rho; }
 
 // Decodes n1 G1 slots (64 B) and n2 G2 slots (128 B) with the verifier's key-point kernel.  Returns the index of the first refused
 // point (G1 slots count first, then G2), or -1 when every point is accepted.
@@ -85,6 +89,19 @@ inline long long decode_slots_first_bad(const std::vector<uint8_t>& s1, size_t n
 // false when a point is refused (st < 0)
 inline bool decode_slots(const std::vector<uint8_t>& s1, size_t n1, const std::vector<uint8_t>& s2, size_t n2, vfy::VP1* o1, vfy::VP2* o2, hipStream_t s) {
     return decode_slots_first_bad(s1, n1, s2, n2, o1, o2, s) < 0;
+}
+// the decoded points of one key file on the device
+struct DevKey {
+    phase2::Walk w; size_t n1 = 0, n2 = 0;
+    Buf g1, g2;
+    DevKey(const phase2::Walk& walk) : w(walk), n1(walk.g1.size()), n2(walk.g2.size()), g1(sizeof(vfy::VP1) * walk.g1.size()), g2(sizeof(vfy::VP2) * walk.g2.size()) {}
+    vfy::VP1* p1() const { return g1.as<vfy::VP1>(); }
+    vfy::VP2* p2() const { return g2.as<vfy::VP2>(); }
+};
+inline bool decode_file(const uint8_t* b, DevKey& k, hipStream_t s) {
+    std::vector<uint8_t> s1, s2;
+    phase2::slots(b, k.w.g1, 32, s1); phase2::slots(b, k.w.g2, 64, s2);
+    return decode_slots(s1, k.n1, s2, k.n2, k.p1(), k.p2(), s);
 }
 // raw big-endian bytes (and infinity flags) of n decoded points
 template <class P> void download(const P* p, size_t n, uint8_t* out, uint8_t* inf, hipStream_t s) {

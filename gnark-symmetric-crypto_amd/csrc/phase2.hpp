@@ -34,6 +34,10 @@ struct Walk {
     std::vector<Elem> g1, g2;
     size_t d1 = 0, d2 = 0;                      // G1.Delta in g1, G2.Delta in g2
     size_t z0 = 0, nz = 0, k0 = 0, nk = 0;      // pk: G1.Z = g1[z0, z0 + nz), G1.K = g1[k0, k0 + nk); a vk has neither (its K is gamma's, untouched)
+    // the one commitment key, when the file has it (sigma.hpp).  pk: Basis = g1[pb0, pb0 + npb), BasisExpSigma =
+    // g1[ps0, ps0 + npb); vk: G = g2[pg], GSigmaNeg = g2[pgsn]
+    bool ped = false, vk = false;               // vk: walk_vk made this walk
+    size_t pb0 = 0, ps0 = 0, npb = 0, pg = 0, pgsn = 0;
 };
 
 namespace detail {
@@ -85,8 +89,10 @@ inline bool walk_pk(const uint8_t* b, size_t n, Walk& w, std::string& err) {
     if (nck > 1) return detail::fail(err, "pk: more than one commitment key is not supported");
     if (nck == 1) {
         size_t c0, c1;
-        if (!c.slice(32, w.g1, c0) || !c.slice(32, w.g1, c1)) return detail::fail(err, "pk: truncated");
+        w.pb0 = w.g1.size(); if (!c.slice(32, w.g1, c0)) return detail::fail(err, "pk: truncated");
+        w.ps0 = w.g1.size(); if (!c.slice(32, w.g1, c1)) return detail::fail(err, "pk: truncated");
         if (c0 != c1) return detail::fail(err, "pk: commitment key size mismatch");
+        w.ped = true; w.npb = c0;
     }
     if (c.i != n) return detail::fail(err, "pk: trailing bytes");
     if (fa != na || fb != nb || nb != nb2 || w.nz != domain - 1) return detail::fail(err, "pk: inconsistent slice sizes");
@@ -95,7 +101,7 @@ inline bool walk_pk(const uint8_t* b, size_t n, Walk& w, std::string& err) {
 
 // groth16.VerifyingKey.WriteTo / WriteRawTo layout, with the refusals of verify_common.cpp parse_vk_layout
 inline bool walk_vk(const uint8_t* b, size_t n, Walk& w, std::string& err) {
-    w = Walk(); detail::Cur c(b, n);
+    w = Walk(); w.vk = true; detail::Cur c(b, n);
     size_t nk;
     if (!c.point(32, w.g1) || !c.point(32, w.g1) || !c.point(64, w.g2) || !c.point(64, w.g2)) return detail::fail(err, "vk: truncated");
     w.d1 = w.g1.size(); w.d2 = w.g2.size();
@@ -108,7 +114,10 @@ inline bool walk_vk(const uint8_t* b, size_t n, Walk& w, std::string& err) {
     const uint64_t nck = c.be(4);
     if (!c.ok) return detail::fail(err, "vk: truncated");
     if (nck != outer) return detail::fail(err, "vk: commitment key count");
-    if (nck && (!c.point(64, w.g2) || !c.point(64, w.g2))) return detail::fail(err, "vk: truncated");
+    if (nck) {
+        w.pg = w.g2.size(); w.pgsn = w.pg + 1; w.ped = true;
+        if (!c.point(64, w.g2) || !c.point(64, w.g2)) return detail::fail(err, "vk: truncated");
+    }
     if (c.i != n) return detail::fail(err, "vk: trailing bytes");
     return true;
 }
@@ -122,22 +131,34 @@ inline void slots(const uint8_t* b, const std::vector<Elem>& el, size_t cb, std:
     for (size_t i = 0; i < el.size(); i++) memcpy(out.data() + 2 * cb * i, b + el[i].off, el[i].size);
 }
 
-// Rule 2 of a step: outside the rewritten elements, next equals prev byte for byte, with the same element counts.  (So a key whose
-// untouched points were re-encoded — raw for compressed or back — is refused although it holds the same points.)
-inline bool same_outside(const uint8_t* a, size_t an, const Walk& wa, const uint8_t* b, size_t bn, const Walk& wb) {
+// Outside the elements that a step rewrites — in1(w, i) for g1[i], in2(w, i) for g2[i] — b equals a byte for byte, with the same element
+// counts and marks.  (So a key whose untouched points were re-encoded — raw for compressed or back — is refused although it holds the same
+// points.)
+template <class In1, class In2>
+inline bool same_outside_of(const uint8_t* a, size_t an, const Walk& wa, const uint8_t* b, size_t bn, const Walk& wb, In1 in1, In2 in2) {
     if (wa.g1.size() != wb.g1.size() || wa.g2.size() != wb.g2.size() || wa.nz != wb.nz || wa.nk != wb.nk || wa.z0 != wb.z0 || wa.k0 != wb.k0 ||
-        wa.d1 != wb.d1 || wa.d2 != wb.d2) return false;
-    // the rewritten elements in file order cut each file into the same number of gaps; every gap must match
+        wa.d1 != wb.d1 || wa.d2 != wb.d2 || wa.ped != wb.ped || wa.vk != wb.vk || wa.pb0 != wb.pb0 || wa.ps0 != wb.ps0 || wa.npb != wb.npb || wa.pg != wb.pg ||
+        wa.pgsn != wb.pgsn) return false;
+    // the rewritten elements in file order cut each file into the same number of gaps; every gap must match.  Each group's elements lie in
+    // file order; the two groups interleave (a pk: G1 sets, G2 sets, the commitment key's G1 sets), so the two lists are merged by offset.
     std::vector<Elem> ca, cb;
-    for (size_t i = 0; i < wa.g1.size(); i++) if (rewritten_g1(wa, i)) { ca.push_back(wa.g1[i]); cb.push_back(wb.g1[i]); }
-    // (G2.Delta lies behind every rewritten G1 element of a pk and of a vk)
-    ca.push_back(wa.g2[wa.d2]); cb.push_back(wb.g2[wb.d2]);
+    size_t i1 = 0, i2 = 0;
+    const size_t n1 = wa.g1.size(), n2 = wa.g2.size();
+    while (i1 < n1 || i2 < n2) {
+        const bool first = i2 >= n2 || (i1 < n1 && wa.g1[i1].off < wa.g2[i2].off);
+        if (first) { if (in1(wa, i1)) { ca.push_back(wa.g1[i1]); cb.push_back(wb.g1[i1]); } i1++; }
+        else { if (in2(wa, i2)) { ca.push_back(wa.g2[i2]); cb.push_back(wb.g2[i2]); } i2++; }
+    }
     size_t ia = 0, ib = 0;
     for (size_t k = 0; k < ca.size(); k++) {
         if (ca[k].off < ia || cb[k].off < ib || ca[k].off - ia != cb[k].off - ib || memcmp(a + ia, b + ib, ca[k].off - ia)) return false;
         ia = ca[k].off + ca[k].size; ib = cb[k].off + cb[k].size;
     }
     return an - ia == bn - ib && !memcmp(a + ia, b + ib, an - ia);
+}
+// Rule 2 of a delta step: the rewritten elements are G1.Delta, Z, K and G2.Delta
+inline bool same_outside(const uint8_t* a, size_t an, const Walk& wa, const uint8_t* b, size_t bn, const Walk& wb) {
+    return same_outside_of(a, an, wa, b, bn, wb, rewritten_g1, [](const Walk& w, size_t i) { return i == w.d2; });
 }
 
 // (p-1)/2 big-endian: a compressed point carries the "larger y" flag iff y > (p-1)/2
@@ -184,13 +205,16 @@ inline Record decode_record(const uint8_t in[kRecordBytes]) {
     Record r; memcpy(r.h_prev, in, 32); memcpy(r.h_next, in + 32, 32); memcpy(r.delta, in + 64, 64); memcpy(r.T, in + 128, 64); memcpy(r.z, in + 192, 32);
     return r;
 }
-// c as 32 big-endian bytes (byte 0 is zero: c < 2^248 < r)
-inline void challenge(const uint8_t h_prev[32], const uint8_t delta_prev[64], const uint8_t delta_next[64], const uint8_t T[64], uint8_t c_be[32]) {
-    static const char tag[] = "gsc-phase2-v1";
-    uint8_t msg[13 + 32 + 3 * 64], h[32];
-    memcpy(msg, tag, 13); memcpy(msg + 13, h_prev, 32); memcpy(msg + 45, delta_prev, 64); memcpy(msg + 109, delta_next, 64); memcpy(msg + 173, T, 64);
-    sha256_digest(msg, sizeof msg, h);
+// c as 32 big-endian bytes (byte 0 is zero: c < 2^248 < r): the first 31 bytes of SHA-256(tag | h_prev | base | next | T), tag at most 16 bytes
+inline void challenge_tagged(const char* tag, const uint8_t h_prev[32], const uint8_t base[64], const uint8_t next[64], const uint8_t T[64], uint8_t c_be[32]) {
+    uint8_t msg[16 + 32 + 3 * 64], h[32];
+    size_t ln = strlen(tag); if (ln > 16) ln = 16;
+    memcpy(msg, tag, ln); memcpy(msg + ln, h_prev, 32); memcpy(msg + ln + 32, base, 64); memcpy(msg + ln + 96, next, 64); memcpy(msg + ln + 160, T, 64);
+    sha256_digest(msg, ln + 32 + 3 * 64, h);
     c_be[0] = 0; memcpy(c_be + 1, h, 31);
+}
+inline void challenge(const uint8_t h_prev[32], const uint8_t delta_prev[64], const uint8_t delta_next[64], const uint8_t T[64], uint8_t c_be[32]) {
+    challenge_tagged("gsc-phase2-v1", h_prev, delta_prev, delta_next, T, c_be);
 }
 // a scalar of a seeded (TEST) contribution: SHA-256(label | seed32) as a big-endian integer mod r; false when that is zero
 inline bool seeded_scalar(const char* label, const uint8_t seed32[32], hostf::Fr& out) {

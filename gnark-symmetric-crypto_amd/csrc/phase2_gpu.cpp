@@ -28,19 +28,6 @@ struct Secrets {
     ~Secrets() { explicit_bzero(&x, sizeof x); explicit_bzero(&x_inv, sizeof x_inv); explicit_bzero(&k, sizeof k); explicit_bzero(&t, sizeof t); explicit_bzero(words, sizeof words); }
 };
 
-// the decoded points of one key file on the device
-struct DevKey {
-    P2::Walk w; size_t n1 = 0, n2 = 0;
-    Buf g1, g2;
-    DevKey(const P2::Walk& walk) : w(walk), n1(walk.g1.size()), n2(walk.g2.size()), g1(sizeof(VP1) * walk.g1.size()), g2(sizeof(VP2) * walk.g2.size()) {}
-    VP1* p1() const { return g1.as<VP1>(); }
-    VP2* p2() const { return g2.as<VP2>(); }
-};
-bool decode_file(const uint8_t* b, DevKey& k, hipStream_t s) {
-    std::vector<uint8_t> s1, s2;
-    P2::slots(b, k.w.g1, 32, s1); P2::slots(b, k.w.g2, 64, s2);
-    return decode_slots(s1, k.n1, s2, k.n2, k.p1(), k.p2(), s);
-}
 // G1.Delta (64 B) and G2.Delta (128 B) of a decoded file; false when either is the point at infinity
 bool deltas(const DevKey& k, uint8_t d1[64], uint8_t d2[128], hipStream_t s) {
     uint8_t i1 = 0, i2 = 0;

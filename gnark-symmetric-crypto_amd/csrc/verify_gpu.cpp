@@ -600,6 +600,13 @@ int gsc_verify_debug_randomizers_impl(const uint8_t* seed32, int all_ones) {
     return 0;
 }
 
+// n randomizers of four words each for the key ceremony's random combinations (sigma_gpu.cpp), drawn as the verifier draws its own
+void gsc_verify_draw_rho_impl(uint32_t* out, size_t n) {
+    std::vector<uint32_t> rnd((size_t)kRandWords * n);
+    draw_randomizers(rnd.data(), n, false, 0);
+    for (size_t i = 0; i < n; i++) memcpy(out + 4 * i, rnd.data() + (size_t)kRandWords * i, 16);
+}
+
 // the verifier's device, for the key ceremony (phase2_gpu.cpp): GSC_DEVICE, or the first of GSC_DEVICES
 int gsc_verify_device_impl() { return verify_device(); }
 

@@ -375,7 +375,8 @@ extern int gsc_srs_verify(GoSlice srs);
  * beta = 1 and every party multiplies the scalars by secrets of its own; the final tau, alpha, beta are products that nobody knows unless
  * every party colludes (or kept its secrets).  The full chain to a proving key, with no test hook on the way: gsc_srs_initial ->
  * gsc_srs_contribute (each party; everybody checks every link with gsc_srs_verify_contribution) -> gsc_setup_from_srs ->
- * gsc_setup_contribute (each party; gsc_setup_verify_contribution).
+ * gsc_setup_contribute (each party; gsc_setup_verify_contribution) and, for a key with a commitment (AES-V2), gsc_setup_contribute_sigma
+ * (each party; gsc_setup_verify_sigma_contribution), from the pair everybody checked with gsc_setup_verify_from_srs.
  * The starting file for N = 2^L, 1 <= L <= 24, in the layout above: every G1 element the G1 generator, every G2 element the G2 generator,
  * raw.  Host only (no device, no test hooks) and deterministic: a verifier of a chain makes the start itself and compares the published one
  * byte for byte.  0 on success: *srs malloc'd (release with Free); -2: L out of range, the outputs NULL / 0. */
@@ -416,12 +417,60 @@ extern int gsc_debug_scale_powers(int group, const uint8_t *pts, const uint8_t *
  * A KEY WITH DELTA = 1 IS FORGEABLE BY ANYONE.  It becomes usable only after at least one gsc_setup_contribute; a deployment verifies the file
  * (gsc_srs_verify) and every link of the chain (gsc_setup_verify_contribution).  Without a commitment (ChaCha20-V3) the key is a deterministic
  * function of (r1cs, file).  With one (AES-V2) the Pedersen sigma and g come from the OS CSPRNG and are wiped before the call returns:
- * WHOEVER RUNS THIS CALL HOLDS SIGMA; a distributed sigma is not part of this library.  Public committed wires are refused, as by gsc_setup.
+ * whoever runs this call held sigma for that moment, so sigma is re-randomised like delta: gsc_setup_contribute_sigma (each party;
+ * gsc_setup_verify_sigma_contribution), from a pair that gsc_setup_verify_from_srs accepts.  Public committed wires are refused, as by gsc_setup.
  * seed32 != NULL (TEST HOOKS only): gamma, delta, sigma, g = gsc_setup's seeded scalars, applied to the unscaled points, so that the result
  * equals gsc_setup(r1cs, seed32) byte for byte when the file holds the same seed's tau, alpha, beta (gsc_debug_srs_generate).
  * 0 on success: *pk / *vk malloc'd (release with Free).  -1: a seed given without test hooks; -2: malformed r1cs, a file that gsc_srs_verify
  * refuses, or L < log2 n (one line on stdout); -3: device error.  On failure the outputs are NULL / 0 and nothing stays allocated. */
 extern int gsc_setup_from_srs(GoSlice r1cs, GoSlice srs, const uint8_t *seed32, void **pk, size_t *pk_len, void **vk, size_t *vk_len);
+/* ---- key ceremony: the Pedersen sigma of a commitment key, distributed (an addition).  A key with a BSB22 commitment
+ * (AES-128-V2, AES-256-V2) carries pk.Basis_j = K_j / gamma over the committed wires, pk.BasisExpSigma_j = sigma Basis_j, vk.G = g G_2,
+ * vk.GSigmaNeg = -sigma g G_2.  Whoever knows sigma forges the proof of knowledge PoK = sigma D of a commitment D it cannot open: sigma is
+ * toxic waste like delta.  The PEDERSEN RELATION of a pair: e(BasisExpSigma_j, G) e(Basis_j, GSigmaNeg) = 1 for every j.
+ * A sigma contribution draws a secret x in [1, r) and makes BasisExpSigma'_j = x BasisExpSigma_j (pk) and GSigmaNeg' = x GSigmaNeg (vk): the
+ * key of sigma x.  Every other byte of both files is copied (G too: the relation is homogeneous in g, and g's discrete logarithm opens
+ * nothing); the rewritten points are written compressed, infinity stays infinity.  A delta contribution copies the commitment key and a
+ * sigma contribution copies delta, Z and K: THE TWO KINDS OF LINK MAY INTERLEAVE IN ONE CHAIN.
+ * The record (GSC_SIGMA_CONTRIBUTION_BYTES, this project's own format, the phase-2 record's layout): SHA-256(pk_prev) | SHA-256(pk_next) |
+ * new raw X | Y (next's BasisExpSigma[j0]; j0: the lowest index whose element is finite) | T = k base raw (base: prev's BasisExpSigma[j0]) |
+ * z = k + c x mod r, big-endian; c = the first 31 bytes, as a big-endian integer, of SHA-256("gsc-sigma-v1" | SHA-256(pk_prev) | base raw |
+ * new raw | T raw).  The tag is not phase 2's: a delta record never passes as a sigma record.
+ * x and k come from the OS CSPRNG; with seed32 (TEST HOOKS only) x = SHA-256("gsc-sigma-x" | seed32) mod r, k = SHA-256("gsc-sigma-k" | seed32) mod r.
+ * None of the four calls needs an initialised algorithm; all run on GSC_DEVICE, or the first of GSC_DEVICES, and are thread-safe; every
+ * refusal prints one line, "<function>: rule k: ...", on stdout. */
+#define GSC_SIGMA_CONTRIBUTION_BYTES 224
+/* Does the pair hold the Pedersen relation?  (1) both files parse, each holds exactly one commitment key ("no commitment key" otherwise), every
+ * point of both decodes as for InitAlgorithm / gsc_verify_init (canonical, on the curve, G2 in the subgroup), G and GSigmaNeg are finite, Basis
+ * and BasisExpSigma have the same length and their infinities at the same positions, at least one element is finite; (2) with fresh non-zero
+ * 128-bit rho_j from the OS CSPRNG, e(sum rho_j BasisExpSigma_j, G) = e(-sum rho_j Basis_j, GSigmaNeg).  A wrong pair is accepted with
+ * probability about 2^-128.  1 accepted, 0 refused, -3 device error. */
+extern int gsc_pedersen_verify(GoSlice pk, GoSlice vk);
+/* One sigma contribution.  0 on success: *pk_out / *vk_out malloc'd (release with Free), record filled.  -1: seed given without test hooks
+ * (before the keys are looked at or a device is asked for); -2: a key that does not parse, has no commitment key or fails rule 1 of
+ * gsc_pedersen_verify, or a seed that gives a zero scalar; -3: device error.  On failure the outputs are NULL / 0, the record is zeroed,
+ * nothing stays allocated. */
+extern int gsc_setup_contribute_sigma(GoSlice pk, GoSlice vk, const uint8_t *seed32,
+                                      void **pk_out, size_t *pk_len, void **vk_out, size_t *vk_len,
+                                      uint8_t record[GSC_SIGMA_CONTRIBUTION_BYTES]);
+/* One link (prev, next, record) is accepted iff (1) rule 1 of gsc_pedersen_verify holds on both pairs; (2) outside pk's BasisExpSigma and vk's
+ * GSigmaNeg next equals prev BYTE FOR BYTE with the same counts (Basis, G, delta, Z, K untouched; a re-encoded key is refused); (3) the
+ * record's hashes are the files', BasisExpSigma has its infinities at the same positions in prev and next (for next this is rule 1's clause
+ * on the infinities, reported here), new is next's element at j0; (4) z < r, T is a finite raw point of the curve, z base == T + c new;
+ * (5) rule 2 of gsc_pedersen_verify holds on NEXT.  Rule 5 makes next the key of some sigma''; rule 4 makes BasisExpSigma'[j0] a multiple x,
+ * known to the contributor, of prev's; given the relation on prev, sigma'' = x sigma.
+ * PREV'S RELATION IS DELIBERATELY NOT RE-CHECKED: a chain is verified from a start pair that passed gsc_pedersen_verify or
+ * gsc_setup_verify_from_srs, link by link, and each prev is the next of the link before it (which rule 5 checked); a verifier who starts in
+ * the middle runs gsc_pedersen_verify on its first prev itself.
+ * 1 accepted, 0 refused (the line names the first rule that failed), -3 device error. */
+extern int gsc_setup_verify_sigma_contribution(GoSlice pk_prev, GoSlice vk_prev, GoSlice pk_next, GoSlice vk_next,
+                                               const uint8_t record[GSC_SIGMA_CONTRIBUTION_BYTES]);
+/* Is (pk, vk) what gsc_setup_from_srs makes of (r1cs, srs)?  Runs that call's production path (no seed) and accepts iff (1) the given pair
+ * equals the recomputed one byte for byte outside pk's BasisExpSigma and vk's G and GSigmaNeg (every run draws sigma and g afresh; for a circuit
+ * without a commitment that is the whole of both files); (2) with a commitment, rules 1 and 2 of gsc_pedersen_verify hold on the given pair.
+ * The start of a verified chain for every algorithm.  1 accepted, 0 refused (with the rule), -2 malformed r1cs, a file gsc_srs_verify
+ * refuses, or L < log2 n; -3 device error. */
+extern int gsc_setup_verify_from_srs(GoSlice r1cs, GoSlice srs, GoSlice pk, GoSlice vk);
 /* TEST HOOK: the powers file for tau, alpha, beta = gsc_setup's seeded toxic(seed32, "tau" | "alpha" | "beta"), 1 <= L <= 20: whoever holds
  * the seed holds the scalars.  0 on success: *srs malloc'd (release with Free); -1 on error / hooks disabled, outputs NULL / 0. */
 extern int gsc_debug_srs_generate(int L, const uint8_t *seed32, void **srs, size_t *len);

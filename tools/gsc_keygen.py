@@ -30,7 +30,22 @@ multiplies the scalars by secrets of its own; anyone checks every link, from the
       prints ACCEPTED (exit status 0) or REFUSED (exit status 1; the library's line above it names the rule that failed)
   python tools/gsc_keygen.py --from-srs SRS R1CS PK VK
       checks the file, then writes a key pair with delta = gamma = 1.  SUCH A KEY IS FORGEABLE BY ANYONE: it becomes usable only after at
-      least one --contribute, and a deployment verifies the file and every link of the chain"""
+      least one --contribute, and a deployment verifies the file and every link of the chain
+  python tools/gsc_keygen.py --verify-from-srs SRS R1CS PK VK
+      is (PK, VK) what --from-srs makes of (SRS, R1CS)?  Byte for byte, but for the commitment key's sigma and g, which every run draws afresh
+      and which must hold the Pedersen relation.  Prints ACCEPTED (exit status 0) or REFUSED (exit status 1): the start of a verified chain
+
+Key ceremony, the Pedersen sigma: a key with a commitment (AES-128-V2, AES-256-V2) carries a second secret, sigma, which
+whoever ran Setup held.  Every party re-randomises it like delta; sigma and delta links may interleave in one chain.
+
+  python tools/gsc_keygen.py --contribute-sigma PK VK --out-dir D
+      writes D/<name of PK>, D/<name of VK> and D/sigma_contribution.record (224 bytes); the secret comes from the OS CSPRNG and is gone when
+      the command returns
+  python tools/gsc_keygen.py --verify-sigma-contribution PREV_PK PREV_VK NEXT_PK NEXT_VK RECORD
+      prints ACCEPTED (exit status 0) or REFUSED (exit status 1; the library's line above it names the rule that failed).  PREV's own
+      Pedersen relation is not re-checked: verify a chain from a pair that passed --verify-from-srs or --verify-pedersen, link by link
+  python tools/gsc_keygen.py --verify-pedersen PK VK
+      prints ACCEPTED (exit status 0) or REFUSED (exit status 1): does the pair's commitment key hold the Pedersen relation?"""
 import lzma
 import os
 import sys
@@ -43,16 +58,16 @@ def _read(path):
     return lzma.open(path).read() if path.endswith(".xz") else open(path, "rb").read()
 
 
-def contribute(g, args):
+def contribute(g, args, sigma=False):
     if len(args) != 4 or args[2] != "--out-dir":
         raise SystemExit(__doc__)
     pk_path, vk_path, out = args[0], args[1], args[3]
     names = [os.path.basename(p)[:-3] if p.endswith(".xz") else os.path.basename(p) for p in (pk_path, vk_path)]
     if os.path.isdir(out) and any(os.path.abspath(os.path.join(out, n)) == os.path.abspath(p) for n, p in zip(names, (pk_path, vk_path))):
         raise SystemExit("--out-dir holds the input keys: choose another directory")
-    pk, vk, record = g.setup_contribute(_read(pk_path), _read(vk_path))
+    pk, vk, record = (g.setup_contribute_sigma if sigma else g.setup_contribute)(_read(pk_path), _read(vk_path))
     os.makedirs(out, exist_ok=True)
-    for name, b in zip(names + ["contribution.record"], (pk, vk, record)):
+    for name, b in zip(names + ["sigma_contribution.record" if sigma else "contribution.record"], (pk, vk, record)):
         open(os.path.join(out, name), "wb").write(b)
     print("pk %d bytes, vk %d bytes, record %d bytes -> %s" % (len(pk), len(vk), len(record), out))
 
@@ -61,6 +76,14 @@ def verify_contribution(g, args):
     if len(args) != 5:
         raise SystemExit(__doc__)
     ok = g.setup_verify_contribution(*[_read(p) for p in args])
+    print("ACCEPTED" if ok else "REFUSED")
+    raise SystemExit(0 if ok else 1)
+
+
+def verdict(call, args, count):
+    if len(args) != count:
+        raise SystemExit(__doc__)
+    ok = call(*[_read(p) for p in args])
     print("ACCEPTED" if ok else "REFUSED")
     raise SystemExit(0 if ok else 1)
 
@@ -124,6 +147,15 @@ def main():
         return verify_srs_contribution(gsc_loader.load(), sys.argv[2:])
     if len(sys.argv) > 1 and sys.argv[1] == "--from-srs":
         return from_srs(gsc_loader.load(), sys.argv[2:])
+    if len(sys.argv) > 1 and sys.argv[1] == "--contribute-sigma":
+        return contribute(gsc_loader.load(), sys.argv[2:], sigma=True)
+    if len(sys.argv) > 1 and sys.argv[1] == "--verify-sigma-contribution":
+        return verdict(gsc_loader.load().setup_verify_sigma_contribution, sys.argv[2:], 5)
+    if len(sys.argv) > 1 and sys.argv[1] == "--verify-pedersen":
+        return verdict(gsc_loader.load().pedersen_verify, sys.argv[2:], 2)
+    if len(sys.argv) > 1 and sys.argv[1] == "--verify-from-srs":
+        g = gsc_loader.load()
+        return verdict(lambda srs, r1cs, pk, vk: g.setup_verify_from_srs(r1cs, srs, pk, vk), sys.argv[2:], 4)
     if len(sys.argv) > 1 and sys.argv[1] == "--contribute":
         return contribute(gsc_loader.load(), sys.argv[2:])
     if len(sys.argv) > 1 and sys.argv[1] == "--verify-contribution":
