@@ -29,7 +29,7 @@ EXPORTS = ["enforce_binding", "InitAlgorithm", "Free", "Prove", "ProveBatch", "g
            "gsc_release_algorithm", "gsc_replace_algorithm", "gsc_memory_info", "gsc_key_generation",
            "gsc_setup_contribute", "gsc_setup_verify_contribution", "gsc_debug_scale_points",
            "gsc_pedersen_verify", "gsc_setup_contribute_sigma", "gsc_setup_verify_sigma_contribution", "gsc_setup_verify_from_srs",
-           "gsc_srs_verify", "gsc_debug_srs_generate", "gsc_debug_group_idft", "gsc_debug_column_sums", "gsc_setup_from_srs", "gsc_debug_msm", "gsc_debug_solve", "gsc_debug_assemble", "gsc_debug_quotient",
+           "gsc_srs_verify", "gsc_debug_srs_generate", "gsc_debug_group_idft", "gsc_debug_column_sums", "gsc_setup_from_srs", "gsc_debug_msm", "gsc_debug_solve", "gsc_debug_assemble", "gsc_debug_quotient", "gsc_debug_verify_g1",
            "gsc_srs_initial", "gsc_srs_contribute", "gsc_srs_verify_contribution", "gsc_debug_scale_powers"]
 
 
@@ -74,6 +74,13 @@ class DebugAssembleArgs(C.Structure):      # struct gsc_debug_assemble_args of i
                [(s + part, C.c_char_p) for s in _ASSEMBLE_SETS for part in ("_pts", "_inf", "_lam")] + \
                [("rs", C.c_char_p), ("mask", C.c_char_p), ("glv_in", C.c_char_p)] + \
                [(n, C.c_void_p) for n in ("out", "flags", "tmp", "tmp_inf", "cpts", "commit", "W", "mask_out", "glv")]
+
+
+class DebugVerifyG1Args(C.Structure):      # struct gsc_debug_verify_g1_args of include/libprove.h
+    _fields_ = [("algorithm", C.c_uint32), ("path", C.c_uint32), ("fill", C.c_uint32), ("vk", C.c_char_p), ("vk_len", C.c_size_t),
+                ("n", C.c_size_t), ("proofs", C.c_char_p), ("lens", C.c_void_p), ("signals", C.c_char_p), ("rnd", C.c_void_p),
+                ("np", C.c_size_t), ("ends", C.c_void_p), ("key_status", C.c_void_p), ("key_status_cap", C.c_size_t)] + \
+               [(n, C.c_void_p) for n in ("table", "ctable", "ok", "g1", "g2", "okv", "fixed", "flag", "pfixed", "prho", "pflag")]
 
 
 class DebugQuotientArgs(C.Structure):      # struct gsc_debug_quotient_args of include/libprove.h
@@ -209,6 +216,8 @@ def lib():
         L.gsc_debug_msm.argtypes = [C.POINTER(DebugMsmArgs)]
         L.gsc_debug_solve.restype = C.c_int
         L.gsc_debug_solve.argtypes = [C.POINTER(DebugSolveArgs)]
+        L.gsc_debug_verify_g1.restype = C.c_int
+        L.gsc_debug_verify_g1.argtypes = [C.POINTER(DebugVerifyG1Args)]
         L.gsc_debug_assemble.restype = C.c_int
         L.gsc_debug_assemble.argtypes = [C.POINTER(DebugAssembleArgs)]
         L.gsc_debug_quotient.restype = C.c_longlong
@@ -612,6 +621,26 @@ def debug_assemble(batch: int, sets: dict, rs: bytes, nproofs: int = 0, mask: by
     res = {k: None for k in ("out", "flags", "tmp", "tmp_inf", "cpts", "commit", "W", "mask_out", "glv")}
     res.update({k: b.raw for k, b in bufs.items()})
     res["rc"] = rc
+    return res
+
+
+def debug_verify_g1(algorithm_id: int, vk: bytes, proofs: bytes, lens, signals: bytes, rnd, ends=(), path: int = 1, fill: int = 0xA5):
+    """TEST HOOK: the verifier's G1 stage on a caller's key, proofs and randomizers; see gsc_debug_verify_g1 in include/libprove.h.  proofs: 196-byte
+    slots; rnd: n x 8 words (rho, t); ends: the part ends of the claim-wise check, or none.  -> dict: rc and, when rc == 0, the outputs as bytes
+    (prho: a list of 5-word tuples), each filled with `fill` before the call."""
+    n, np = len(lens), len(ends)
+    assert len(proofs) >= 196 * n and len(signals) >= 144 * n and len(rnd) == 8 * n
+    sizes = {"key_status": 2048, "table": 144 * 256 * 65, "ctable": 32 * 256 * 65, "ok": n, "g1": 6 * 65 * n, "g2": 129 * n, "okv": n, "fixed": 5 * 65, "flag": 1,
+             "pfixed": 5 * 65 * np, "prho": 20 * np, "pflag": np}
+    bufs = {k: C.create_string_buffer(bytes([fill]) * max(1, v), max(1, v)) for k, v in sizes.items()}
+    lens_arr, rnd_arr, ends_arr = (C.c_uint32 * max(n, 1))(*lens), (C.c_uint32 * max(8 * n, 1))(*rnd), (C.c_uint64 * max(np, 1))(*ends)
+    args = DebugVerifyG1Args(algorithm=algorithm_id, path=path, fill=fill, vk=bytes(vk), vk_len=len(vk), n=n, proofs=bytes(proofs), lens=C.cast(lens_arr, C.c_void_p),
+                             signals=bytes(signals), rnd=C.cast(rnd_arr, C.c_void_p), np=np, ends=C.cast(ends_arr, C.c_void_p) if np else None, key_status_cap=sizes["key_status"])
+    for k, b in bufs.items():
+        setattr(args, k, C.cast(b, C.c_void_p))
+    res = {"rc": lib().gsc_debug_verify_g1(C.byref(args))}
+    res.update({k: b.raw[:sizes[k]] for k, b in bufs.items()})
+    res["prho"] = [tuple(int.from_bytes(res["prho"][20 * p + 4 * c:20 * p + 4 * c + 4], "little") for c in range(5)) for p in range(np)]
     return res
 
 

@@ -295,6 +295,7 @@ bool hand_over(const std::vector<uint8_t>& f, void** out, size_t* len) {
 long long gsc_verify_debug_pairing_impl(const uint8_t* g1, const uint8_t* g2, size_t n, uint8_t* out, bool few);      // verify_gpu.cpp
 int gsc_verify_debug_path_impl(int mode);                                                             // verify_gpu.cpp
 int gsc_verify_debug_randomizers_impl(const uint8_t* seed32, int all_ones);                           // verify_gpu.cpp
+int gsc_verify_debug_g1_impl(const gsc_debug_verify_g1_args& args);                                   // verify_gpu.cpp
 
 extern "C" {
 
@@ -703,6 +704,10 @@ int gsc_debug_verify_path(int mode) {
 int gsc_debug_verify_randomizers(const uint8_t* seed32, int all_ones) {
     if (hooks_refused("gsc_debug_verify_randomizers")) return -1;
     return gsc_verify_debug_randomizers_impl(seed32, all_ones);
+}
+int gsc_debug_verify_g1(const gsc_debug_verify_g1_args* args) {
+    if (hooks_refused("gsc_debug_verify_g1") || !args) return -1;
+    return gsc_verify_debug_g1_impl(*args);
 }
 int gsc_debug_glv_split(const uint8_t* k, uint8_t* out) {
     if (hooks_refused("gsc_debug_glv_split") || !k || !out) return -1;

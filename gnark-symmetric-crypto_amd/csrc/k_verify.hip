@@ -71,6 +71,23 @@ __global__ __launch_bounds__(64) void k_verify_f12_bytes(const F12* f, uint8_t* 
         for (int j = 0; j < 8; j++) for (int b = 0; b < 4; b++) o[4 * j + b] = (uint8_t)(w.l[7 - j] >> (24 - 8 * b));
     }
 }
+// test hook: n affine points `stride` bytes apart from src on (VP1, or VP2 when g2) -> canonical big-endian X | Y (G2: X.A1 | X.A0 | Y.A1 | Y.A0)
+// and an infinity byte behind them (zero coordinates for the point at infinity), `ostride` bytes apart; live (optional, int32 words
+// `lstride` bytes apart): point i is converted only where its word is not zero, its bytes stay as they were otherwise
+__global__ __launch_bounds__(64) void k_verify_point_bytes(const uint8_t* src, size_t stride, int g2, const uint8_t* live, size_t lstride, uint8_t* out, size_t ostride, size_t n) {
+    const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (live && !*(const int32_t*)(live + lstride * i)) return;
+    uint8_t* o = out + ostride * i;
+    e1 c[4]; int nc; bool inf;
+    if (g2) { const VP2& p = *(const VP2*)(src + stride * i); c[0] = p.x.a1; c[1] = p.x.a0; c[2] = p.y.a1; c[3] = p.y.a0; nc = 4; inf = p.inf != 0; }
+    else { const VP1& p = *(const VP1*)(src + stride * i); c[0] = p.x; c[1] = p.y; c[2] = c[3] = F::zero(); nc = 2; inf = p.inf != 0; }
+    for (int k = 0; k < nc; k++) {
+        const fe w = F::pack(F::from_mont(c[k]));
+        for (int j = 0; j < 8; j++) for (int b = 0; b < 4; b++) o[32 * k + 4 * j + b] = inf ? 0 : (uint8_t)(w.l[7 - j] >> (24 - 8 * b));
+    }
+    o[32 * nc] = inf ? 1 : 0;
+}
 
 unsigned blocks(size_t n) { return (unsigned)((n + 63) / 64); }
 
@@ -96,6 +113,9 @@ void launch_verify_debug_points(const uint8_t* g1, const uint8_t* g2, ProofDev* 
 }
 void launch_verify_f12_bytes(const F12* f, uint8_t* out, size_t n, hipStream_t s) {
     if (n) hipLaunchKernelGGL(k_verify_f12_bytes, dim3(blocks(n)), dim3(64), 0, s, f, out, n);
+}
+void launch_verify_point_bytes(const void* src, size_t stride, bool g2, const void* live, size_t lstride, uint8_t* out, size_t ostride, size_t n, hipStream_t s) {
+    if (n) hipLaunchKernelGGL(k_verify_point_bytes, dim3(blocks(n)), dim3(64), 0, s, (const uint8_t*)src, stride, g2 ? 1 : 0, (const uint8_t*)live, lstride, out, ostride, n);
 }
 
 }  // namespace gsc

@@ -20,6 +20,7 @@
 #include <algorithm>
 #include <atomic>
 #include <cerrno>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -127,8 +128,8 @@ bool g_dir_tried = false;
 const char* kFiles[3] = {"vk.chacha20", "vk.aes128", "vk.aes256"};
 
 // the key on `device` with chunk buffers for `cap` proofs per pass (a verifier's key: verify_device(), kChunk; a prover replica's check context:
-// the replica's device and its largest lane)
-std::shared_ptr<GpuKey> build_key(int algo, const uint8_t* b, size_t n, int device, size_t cap) {
+// the replica's device and its largest lane).  point_status (optional, gsc_debug_verify_g1): k_verify_key_points' answer per key point, G1 then G2
+std::shared_ptr<GpuKey> build_key(int algo, const uint8_t* b, size_t n, int device, size_t cap, std::vector<int8_t>* point_status = nullptr) {
     V::VkLayout lay; std::string err;
     if (!V::parse_vk_layout(b, n, lay, &err)) { printf("%s\n", err.c_str()); return nullptr; }
     auto k = std::make_shared<GpuKey>();
@@ -163,6 +164,7 @@ std::shared_ptr<GpuKey> build_key(int algo, const uint8_t* b, size_t n, int devi
     ck(hipMemcpyAsync(h2, p2.p, n2 * sizeof(VP2), hipMemcpyDeviceToHost, s), "copy");
     ck(hipStreamSynchronize(s), "key points");
     for (int8_t v : hs) if (v < 0) { printf("vk: bad point\n"); return nullptr; }
+    if (point_status) *point_status = hs;
     k->has_commitment = lay.has_commitment;
     k->fits = V::key_fits(algo, lay.K.size(), lay.has_commitment);
     KeyDev& kd = k->kd;
@@ -644,6 +646,85 @@ long long gsc_verify_debug_pairing_impl(const uint8_t* g1, const uint8_t* g2, si
         ck(hipStreamSynchronize(s), "debug pairing");
         return (long long)n;
     } catch (const std::exception& e) { printf("gsc_debug_pairing: %s\n", e.what()); return -1; }
+}
+
+// gsc_debug_verify_g1's body (include/libprove.h): a key of its own from build_key, prep_chunk, then the production launchers on the caller's
+// randomizers; every output is collected on the host first, so a call that fails has written nothing
+int gsc_verify_debug_g1_impl(const gsc_debug_verify_g1_args& a) {
+    constexpr size_t kG1 = 65, kG2 = 129;
+    auto refuse = [](const char* why) { printf("gsc_debug_verify_g1: %s\n", why); return -1; };
+    if (a.algorithm > 2 || !a.vk || !a.vk_len) return refuse("algorithm is 0 .. 2 with a key");
+    if (a.n < 1 || a.n > kFewChunk || !a.proofs || !a.lens || !a.signals || !a.rnd) return refuse("n is 1 .. 8192 with proofs, lens, signals and rnd");
+    if (a.path != kPathThread && a.path != kPathFew) return refuse("path is 1 or 2");
+    if (a.fill > 255) return refuse("fill is a byte");
+    if (a.np && !a.ends) return refuse("parts without ends");
+    for (size_t j = 0; j < a.np; j++) if (a.ends[j] <= (j ? a.ends[j - 1] : 0) || a.ends[j] > a.n) return refuse("part ends are strictly increasing up to n");
+    if (a.np && a.ends[a.np - 1] != a.n) return refuse("the last part ends at n");
+    try {
+        const size_t n = a.n, np = a.np;
+        std::vector<int8_t> status;
+        auto key = build_key((int)a.algorithm, a.vk, a.vk_len, verify_device(), n, &status);
+        if (!key) return -2;
+        GpuKey& k = *key;
+        if (!k.fits) { printf("gsc_debug_verify_g1: the key is not one of the algorithm's circuit\n"); return -3; }
+        std::lock_guard<std::mutex> l(k.mu);
+        ck(hipSetDevice(k.device), "hipSetDevice");
+        hipStream_t s = k.stream;
+        const bool few = a.path == kPathFew, com = k.has_commitment;
+        if (few && !k.few_lines.p) { Tallying tallying(&k.bytes, k.device); k.few_lines.alloc(k.few_cap() * kLineSteps); }
+        // one device image per output, filled first; the host copies below are what the caller gets
+        struct Out { DevBuf<uint8_t> d; std::vector<uint8_t> h; };
+        auto make = [&](Out& o, size_t bytes) { o.d.alloc(bytes); o.h.resize(bytes); ck(hipMemsetAsync(o.d.p, (int)a.fill, bytes, s), "fill"); };
+        auto fetch = [&](Out& o) { if (!o.h.empty()) ck(hipMemcpyAsync(o.h.data(), o.d.p, o.h.size(), hipMemcpyDeviceToHost, s), "copy"); };
+        Out table, ctable, g1, g2, fixed, pfixed;
+        make(table, V::kWindows * 256 * kG1); make(ctable, kCommitWindows * 256 * kG1); make(g1, n * 6 * kG1); make(g2, n * kG2);
+        make(fixed, kBatchFixed * kG1); make(pfixed, std::max<size_t>(np, 1) * kBatchFixed * kG1);
+        launch_verify_point_bytes(k.table.p, sizeof(VP1), false, nullptr, 0, table.d.p, kG1, V::kWindows * 256, s);
+        if (com) launch_verify_point_bytes(k.ctable.p, sizeof(VP1), false, nullptr, 0, ctable.d.p, kG1, kCommitWindows * 256, s);
+
+        std::vector<uint8_t> win(n * V::kWindows), pre(n);
+        prep_chunk(k, a.proofs, a.lens, a.signals, 0, n, win, pre);
+        ck(hipMemcpyAsync(k.rnd.p, a.rnd, n * kRandWords * sizeof(uint32_t), hipMemcpyHostToDevice, s), "copy");
+        launch_verify_batch(k.kd, k.pd.p, k.rnd.p, n, k.bufs(), few ? k.few_lines.p : nullptr, s);
+        ck(hipGetLastError(), "k_verify_batch");
+        std::vector<ProofDev> pd(n);
+        std::vector<uint8_t> okv(n), ok(n), pflag(np, (uint8_t)a.fill);
+        std::vector<uint32_t> prho(5 * np);
+        uint8_t flag = 0;
+        ck(hipMemcpyAsync(pd.data(), k.pd.p, n * sizeof(ProofDev), hipMemcpyDeviceToHost, s), "copy");
+        ck(hipMemcpyAsync(okv.data(), k.bok.p, n, hipMemcpyDeviceToHost, s), "copy");
+        ck(hipMemcpyAsync(&flag, k.bflag.p, 1, hipMemcpyDeviceToHost, s), "copy");
+        const uint8_t* pdb = (const uint8_t*)k.pd.p;
+        const size_t live = offsetof(ProofDev, ok);
+        const size_t at[5] = {offsetof(ProofDev, A), offsetof(ProofDev, C), offsetof(ProofDev, L), offsetof(ProofDev, D), offsetof(ProofDev, pok)};
+        for (int j = 0; j < 5; j++) if (j != 3 || com) launch_verify_point_bytes(pdb + at[j], sizeof(ProofDev), false, pdb + live, sizeof(ProofDev), g1.d.p + kG1 * j, 6 * kG1, n, s);
+        launch_verify_point_bytes(k.ra.p, sizeof(VP1), false, nullptr, 0, g1.d.p + kG1 * 5, 6 * kG1, n, s);
+        launch_verify_point_bytes(pdb + offsetof(ProofDev, B), sizeof(ProofDev), true, pdb + live, sizeof(ProofDev), g2.d.p, kG2, n, s);
+        launch_verify_point_bytes(k.fixed.p, sizeof(VP1), false, nullptr, 0, fixed.d.p, kG1, kBatchFixed, s);
+        if (np) {
+            const ClaimBufs cb = k.claim_bufs();
+            std::vector<claims::Part> parts(np);
+            for (size_t j = 0; j < np; j++) parts[j] = claims::Part{(uint32_t)(j ? a.ends[j - 1] : 0), (uint32_t)a.ends[j]};
+            ck(hipMemcpyAsync(cb.parts, parts.data(), np * sizeof(claims::Part), hipMemcpyHostToDevice, s), "copy");
+            launch_verify_claims(k.kd, k.pd.p, k.rnd.p, n, np, k.bufs(), cb, few ? k.few_lines.p : nullptr, s);
+            ck(hipGetLastError(), "k_verify_claims");
+            for (int j = 0; j < (com ? kBatchFixed : 3); j++) launch_verify_point_bytes(cb.fixed + j, kBatchFixed * sizeof(VP1), false, nullptr, 0, pfixed.d.p + kG1 * j, kBatchFixed * kG1, np, s);
+            ck(hipMemcpyAsync(prho.data(), cb.rho, 5 * np * sizeof(uint32_t), hipMemcpyDeviceToHost, s), "copy");
+            ck(hipMemcpyAsync(pflag.data(), cb.flag, np, hipMemcpyDeviceToHost, s), "copy");
+            ck(hipStreamSynchronize(s), "verify claims");      // parts is read by the copy above
+        }
+        ck(hipGetLastError(), "k_verify_point_bytes");
+        fetch(table); fetch(ctable); fetch(g1); fetch(g2); fetch(fixed); fetch(pfixed);
+        ck(hipStreamSynchronize(s), "debug verify g1");
+        for (size_t i = 0; i < n; i++) ok[i] = pd[i].ok ? 1 : 0;
+        auto give = [](void* dst, const void* src, size_t bytes) { if (dst && bytes) memcpy(dst, src, bytes); };
+        give(a.key_status, status.data(), std::min(a.key_status_cap, status.size()));
+        give(a.table, table.h.data(), table.h.size()); give(a.ctable, ctable.h.data(), ctable.h.size());
+        give(a.ok, ok.data(), n); give(a.g1, g1.h.data(), g1.h.size()); give(a.g2, g2.h.data(), g2.h.size()); give(a.okv, okv.data(), n);
+        give(a.fixed, fixed.h.data(), fixed.h.size()); give(a.flag, &flag, 1);
+        give(a.pfixed, pfixed.h.data(), np * kBatchFixed * kG1); give(a.prho, prho.data(), 5 * np * sizeof(uint32_t)); give(a.pflag, pflag.data(), np);
+        return 0;
+    } catch (const std::exception& e) { printf("gsc_debug_verify_g1: %s\n", e.what()); return -1; }
 }
 
 // ---- the prover's self-check (prove_check.hpp): a key as above on an engine replica's device, fed from a lane's output buffers ----

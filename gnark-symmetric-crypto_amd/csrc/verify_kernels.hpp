@@ -11,4 +11,7 @@ void launch_verify_prep(const vfy::KeyDev& k, const uint8_t* proofs, const uint8
 void launch_verify_pairing(const vfy::KeyDev& k, const vfy::ProofDev* pd, uint8_t* verdict, vfy::F12* fout, size_t n, hipStream_t s);
 void launch_verify_debug_points(const uint8_t* g1, const uint8_t* g2, vfy::ProofDev* pd, size_t n, hipStream_t s);
 void launch_verify_f12_bytes(const vfy::F12* f, uint8_t* out, size_t n, hipStream_t s);
+// test hook (gsc_debug_verify_g1): n VP1 / VP2 images `stride` bytes apart -> 65 / 129 bytes each, `ostride` apart: canonical big-endian
+// coordinates and an infinity byte; live (optional): int32 words `lstride` apart, a point whose word is zero is left alone
+void launch_verify_point_bytes(const void* src, size_t stride, bool g2, const void* live, size_t lstride, uint8_t* out, size_t ostride, size_t n, hipStream_t s);
 }  // namespace gsc

@@ -632,6 +632,36 @@ struct gsc_debug_solve_args {
     uint32_t *status; uint32_t *flag; uint32_t *info; char *why;
 };
 extern int gsc_debug_solve(const struct gsc_debug_solve_args *args);
+/* TEST HOOK: the verifier's G1 stage alone, everything between a proof's bytes and the first Miller loop, on a caller's key, proofs and
+ * randomizers.  The hook builds a key of its own with the verifier's build_key (chunk buffers for n proofs; the loaded keys are not touched),
+ * runs prep_chunk (the host pre-check, the public-input windows, k_verify_prep), then launch_verify_batch on the caller's randomizers and, with
+ * parts, launch_verify_claims, and reads back what they left behind.  The randomizer mode of gsc_debug_verify_randomizers is neither read nor
+ * changed.
+ *   algorithm: 0 .. 2;  vk / vk_len: the key's bytes, either point encoding;  n: 1 .. 8192 proofs in 196-byte slots with lens[n] and
+ *   n x 144 signal bytes;  rnd: n x 8 words, rho (four little-endian words) then t, used as given;  np / ends: 0, or np part ends, strictly
+ *   increasing, the last one n (part j = proofs [ends[j-1], ends[j]));  path: 1 the per-thread Miller kernels, 2 the few-proof ones;
+ *   fill: the byte every output holds before the first kernel.
+ * A G1 point is 65 bytes, canonical big-endian X | Y and an infinity byte (1: infinity, coordinates zero); a G2 point 129 bytes, X.A1 | X.A0 | Y.A1 |
+ * Y.A0 and the byte.  Outputs (each may be NULL):
+ *   key_status: one int8 per key point as k_verify_key_points left it (0 finite, 1 infinity), alpha, beta1, delta1, K ..., then beta, gamma, delta
+ *   (ped_g, ped_gsn) in G2: key_status_cap entries at most;
+ *   table: 144 x 256 G1 points, the public-input window tables;  ctable: 32 x 256 (a key with a commitment; else left alone);
+ *   ok: n bytes, ProofDev::ok;  g1: n x 6 G1 points A, C, L, D, PoK, rho A (the first five left alone for a proof without ok, D also for a key
+ *   without a commitment);  g2: n G2 points B (left alone without ok);  okv: n bytes, the batched check's;
+ *   fixed: 5 G1 points, the chunk's fixed pairs;  flag: the chunk's byte;
+ *   pfixed: np x 5 G1 points (the Pedersen pairs left alone for a key without a commitment);  prho: np x 5 words, the part's sum of rho;
+ *   pflag: np bytes.
+ * 0 on success; -1 (one line on stdout): hooks disabled, an argument outside the above, a device error; -2: the key is refused (it does not
+ * parse, or a point of it does not decode); -3: the key is not one of the algorithm's circuit.  Nothing is written unless 0 is returned. */
+struct gsc_debug_verify_g1_args {
+    uint32_t algorithm, path, fill;
+    const uint8_t *vk; size_t vk_len;
+    size_t n; const uint8_t *proofs; const uint32_t *lens; const uint8_t *signals; const uint32_t *rnd;
+    size_t np; const uint64_t *ends;
+    int8_t *key_status; size_t key_status_cap;
+    uint8_t *table, *ctable, *ok, *g1, *g2, *okv, *fixed, *flag, *pfixed; uint32_t *prho; uint8_t *pflag;
+};
+extern int gsc_debug_verify_g1(const struct gsc_debug_verify_g1_args *args);
 
 #ifdef __cplusplus
 }
